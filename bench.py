@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Throughput bench of the voice-detector hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: this script starts its own N ranks, one per GPU, over RCCL)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                         (N > 1: this script starts its own N ranks, one per GPU, over RCCL)
 
 Headline workload (BASELINE.json configs[2], "C3", the largest single-GPU configuration): per GPU 100 x 10 min 16 kHz mono PCM16
 recordings = 100 500 windows, at the reference's precision (scores within 1e-4 of its fp32 CPU path).  One step = one pass of the
@@ -22,9 +23,14 @@ metric = audio-seconds processed per wall-second, whole job (sum over ranks), we
     f16x2 (default)  fp32-accurate on the f16 matrix cores: every operand is two f16 halves, three products per term, fp32 accumulate
     fp32             fp32 operands on the fp32 matrix instructions (exact fp32 FMA chains)
     bf16             throughput mode (scores differ from the reference by up to ~0.1: NOT the parity mode)
-Both parity modes are timed in every 1-GPU run (`value` is the chosen one, the other is `secondary.c3_<mode>`).
+With --full both parity modes are timed in a 1-GPU run (`value` is the chosen one, the other is `secondary.c3_<mode>`).
 
-One JSON line on stdout (rank 0).  Extra objects:
+A plain run sets up, warms up, times the K steps and prints the headline: `value`, `ms_per_step` (one timed step) and the figures
+that come with the timed steps for free (windows, device time of the last run, cold start).  `--dump-outputs DIR` then writes what
+the last timed step computed as DIR/*.npy (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
+
+One JSON line on stdout (rank 0).  Extra objects, measured only with --full (null otherwise; --no-cpu-baseline / --no-secondary drop
+parts of them):
   roofline     dominant kernel instantiation of the headline step (largest share of device time in a profiled pass, HIP events on the
                library's stream; names are rocprofv3's): `achieved` / `frac` = ALGORITHMIC FLOPs per launch (2 x the layers'
                multiply-adds) / measured duration against the dense f16 peak; `frac_issued` beside it counts the
@@ -66,6 +72,8 @@ TRAFFIC_MAX_DRIFT = 0.10         # a traffic figure is printed only while the pr
 C5_BYTES_PER_WINDOW = 576000 + 128 * 256 * 4                # 707 072 B (48 kHz stereo PCM16 source)
 REC_S, REC_SR = 600.0, 16000
 N_DISTINCT = 4                   # distinct synthetic recordings; the job's files repeat them (tools/scale_check.py c4 does the same)
+DUMP_MAX_BYTES = 60 * 2 ** 20    # --dump-outputs: all arrays together stay under 64 MB
+DUMP_LOGIT_WINDOWS = 4096
 
 
 def traffic_of(kernel, avg_us, windows_per_launch, algorithmic_bytes_per_launch, prefix=False):
@@ -129,6 +137,34 @@ def make_recordings(n_files):
     files = [base[k % len(base)] for k in range(n_files)]
     frames = np.array([len(f) for f in files], dtype=np.int64)
     return base, files, frames
+
+
+def dump_outputs(out_dir, ctx, n_files, rows):
+    """What the last timed step computed, for comparing two builds output for output (at most DUMP_MAX_BYTES in all):
+        rows.npy           float64 (n, 3)   the detection rows the step returned: file index, start s, end s (every rank's, on rank 0)
+        window_logits.npy  float32 (m, 256) the logits of a fixed sample (seed 0) of DUMP_LOGIT_WINDOWS of the job's windows
+        avg.npy            float64 (k,)     the averaged per-bin scores the rows were thresholded from, all files back to back;
+                                            a fixed sample (seed 1) of them where the whole would not fit under the cap
+    Must run before anything else reuses `ctx`: its results are those of the last job it ran."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.asarray(rows if rows is not None else np.zeros((0, 3)), dtype=np.float64)
+    np.save(os.path.join(out_dir, "rows.npy"), rows)
+    wins = np.array([ctx.num_windows(k) for k in range(n_files)], dtype=np.int64)
+    base = np.concatenate([[0], np.cumsum(wins)])
+    pick = np.sort(np.random.default_rng(0).choice(int(base[-1]), size=min(DUMP_LOGIT_WINDOWS, int(base[-1])), replace=False))
+    logits = []
+    for k in range(n_files):
+        sel = pick[(pick >= base[k]) & (pick < base[k + 1])] - base[k]
+        if len(sel):
+            logits.append(ctx.window_logits(k)[sel, 0, :])
+    logits = np.concatenate(logits) if logits else np.zeros((0, 256), np.float32)
+    np.save(os.path.join(out_dir, "window_logits.npy"), logits)
+    avg = np.concatenate([ctx.avg(k)[0] for k in range(n_files)])
+    room = max(0, (DUMP_MAX_BYTES - rows.nbytes - logits.nbytes) // avg.itemsize)
+    if len(avg) > room:
+        avg = avg[np.sort(np.random.default_rng(1).choice(len(avg), size=room, replace=False))]
+    np.save(os.path.join(out_dir, "avg.npy"), avg)
 
 
 def cpu_baseline(sd_np, recordings):
@@ -272,11 +308,16 @@ def main():
     ap.add_argument("--precision", default="f16x2", choices=["f16x2", "fp32", "bf16"])
     ap.add_argument("--files", type=int, default=100, help="10-minute recordings per GPU (C3: 100)")
     ap.add_argument("--chunk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / STFT-stage profiled passes, the secondary workloads and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (rank 0)")
     ap.add_argument("--rehearse", action="store_true",
                     help="launcher / rendezvous / gather path only, on the CPU with gloo (tests/test_parallel.py): no device work, value null")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if a.gpus > 1 and world_env is None:                 # the documented `python bench.py --gpus N`: start the ranks ourselves
@@ -316,7 +357,6 @@ def main():
 
     base, files, frames = make_recordings(a.files)
     n_files = len(files)
-    pcm = np.concatenate(files)
     dev = torch.device("cuda", local_rank) if (dist is None or backend == "nccl") else torch.device("cpu")
     audio_s_per_step = float(frames.sum()) / REC_SR
     # ---- the job's files as RIFF/WAVE images in page-locked host memory (what a loader thread would have read from disk), and two
@@ -328,7 +368,7 @@ def main():
         h = ctx.host_alloc(len(img))
         h[:] = np.frombuffer(img, dtype=np.uint8)
         wavs.append(h)
-    stage_cap = int(pcm.nbytes) + 4096
+    stage_cap = 2 * int(frames.sum()) + 4096            # PCM16 mono
     stage = [ctx.device_alloc(stage_cap), ctx.device_alloc(stage_cap)]
     d_pcm = stage[0]
     uploaded = {"turn": 0, "infos": None}                # the upload in flight (or landed) and the slot it went to
@@ -410,12 +450,14 @@ def main():
         mem_in_use = round((total_b - free_b) / 2 ** 30, 1)
     except Exception:
         pass
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ctx, n_files, rows)
 
     # ---- roofline: profiled pass of the same path (HIP events around every launch on the library's stream) ----
     roof = stft = None
     kernels, layer_table = [], []
     ctx.upload_wait()                                    # (stage[0] holds a landed upload from here on: the blocks below read it as resident PCM)
-    if rank == 0:
+    if rank == 0 and a.full:
         prof = native.Context(blob, local_rank, precision=a.precision, profile=True, chunk=a.chunk or None)
         pf = min(n_files, 10)                           # 10 recordings: 10 050 windows in 10 passes of 1005 (the job's passes are 1015-1016)
 
@@ -515,10 +557,10 @@ def main():
 
     # ---- secondary blocks (1-GPU runs only: other ranks would wait) ----
     secondary = {}
-    if rank == 0 and world == 1 and not a.no_secondary:
+    if rank == 0 and world == 1 and a.full and not a.no_secondary:
         # the headline's job with the PCM already resident in HBM (no header walk, no H2D in the step): round 2's headline
         ctx.upload_wait()
-        ctx.device_upload(d_pcm, pcm)
+        ctx.device_upload(d_pcm, np.concatenate(files))
         nres = min(a.steps, 5)
         dtr, _ = timed(ctx, 1, nres, submit_resident)
         secondary["c3_resident"] = {"workload": f"C3, PCM resident in HBM before the clock starts (round 2's headline): {n_files} x 10 min, {a.precision}",
@@ -595,11 +637,11 @@ def main():
                                     "kernels_ms_per_pass": {k: round(v["total_ms"] / 2, 3) for k, v in ks.items()}}
         fc.device_free(d5); fc.close()
 
-    if rank == 0 and world == 1 and not a.no_secondary:
+    if rank == 0 and world == 1 and a.full and not a.no_secondary:
         secondary["worker_dropin"] = worker_dropin(base, a.precision)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:       # the CPU baseline is a 1-GPU-run item (other ranks would wait on it)
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:       # the CPU baseline is a 1-GPU-run item (other ranks would wait on it)
         cpu = cpu_baseline(sd_np, base)
 
     if rank == 0:
@@ -609,7 +651,7 @@ def main():
         out = {
             "metric": "audio-seconds processed/sec (whole node), 16 kHz mono",
             "value": round(total_audio / dt, 2), "unit": "audio-seconds/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3),
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3), "full": a.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": a.precision, "data": "synthetic",
             "config": {"workload": f"C3: {n_files} x {REC_S / 60:g} min {REC_SR} Hz mono PCM16 recordings per GPU ({N_DISTINCT} distinct ones, repeated), "
@@ -626,7 +668,8 @@ def main():
             "device_ms_last_run": round(device_ms, 3),
             "hbm_in_use_gib": mem_in_use,
             "rows_last_step": int(len(rows)) if rows is not None else 0,
-            "roofline": roof, "stft_stage": stft, "cpu_baseline": cpu, "secondary": secondary, "kernels": kernels, "layers": layer_table,
+            "roofline": roof, "stft_stage": stft, "cpu_baseline": cpu, "secondary": secondary if a.full else None,
+            "kernels": kernels if a.full else None, "layers": layer_table if a.full else None,
         }
         if t_first is not None:
             out["cold_start"] = {"create_ms": round(1e3 * t_create, 1), "first_step_ms": round(1e3 * t_first, 1),
