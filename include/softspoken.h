@@ -248,6 +248,67 @@ int ss_get_regions(ss_ctx* ctx, int file_id, ss_region* out, int64_t cap, int64_
  * back in out (either may be NULL; *n_out = total). */
 int ss_get_regions_batch(ss_ctx* ctx, int first_file, int n_files, int64_t* counts, ss_region* out, int64_t cap, int64_t* n_out);
 
+/* ---- streaming detection: one recording's PCM arriving in pieces, its final regions returned early -----------------------
+ * A stream is one recording in one enum ss_pcm_format encoding, rate and channel count (the limits of ss_add_pcm), pushed in pieces
+ * of any size down to one frame; its threshold and break are fixed when it is opened.  Each step takes every stream of the context as
+ * far as its pushed audio allows -- decode + mixdown + resample with carried state, every window that has become complete (in passes
+ * of up to ss_set_chunk_windows windows, mixed across streams), the averaging of the bins that became final, the regions -- and
+ * returns what became final.  Equality: the concatenation of every region and every averaged bin a stream returned equals what
+ * ss_add_pcm + ss_run(threshold, break_s) give for the same frames on a context of the same precision (regions as ss_region values,
+ * averages as doubles, bit for bit), for any split into pieces, any cadence of steps and whichever streams shared the passes.
+ * Returned results are final (never changed or withdrawn).
+ *
+ * Latency bound B.  A bin at audio time t (seconds from the recording's start, bin_time - 3) is returned by the first step after the
+ * stream holds audio past t + B, and a region whose last above-threshold bin lies at t_end by the first step after it holds audio
+ * past t_end + break_s + B, where
+ *     B = 3 s + 2 x (3 / 256) s + half / sample_rate,        half = ceil(32 / min(1, 22050 / sample_rate)) (0 at 22 050 Hz):
+ * the last window over a bin ends at most 3 s of audio after it (plus half a bin of the rounded start round(51.2 i)), the gap test
+ * of a region needs one more bin past t_end + break_s (the 4-decimal rounding of bin times is below a bin), and a resampled sample
+ * waits for `half` input frames after it.  16 kHz: 3.0254 s; 44.1 / 48 kHz: 3.0249 s; 8 kHz: 3.0274 s.  The bins and regions of
+ * the last seconds are final at close, as in ss_run (the plan's window and bin counts depend on the total duration).
+ *
+ * State.  Between steps a stream holds the 22 050 Hz samples from its first window not yet run (< 3.6 s), its resampler's input
+ * history (< 2 half + 1 frames), the logits of the <= 6 windows over its non-final bins, its open region and counters: a size that
+ * does not grow with the stream.  Pushed pieces wait in library-owned host staging until a step takes them.
+ * Streams and the job calls share a context without touching each other: a step reads none of the files, results or getters of
+ * the last ended run, ss_run / ss_reset leave the streams alone; a step while ss_run_begin is in flight is SS_ERR_STATE. */
+typedef struct ss_stream_info {
+    int64_t frames_pushed;     /* frames pushed so far (stepped and staged) */
+    int64_t frames_staged;     /* of them: waiting for the next step */
+    int64_t windows_run;       /* windows of the recording run so far */
+    int64_t windows_ready;     /* windows the next step would run (> 0: the stream takes part in it) */
+    double final_until_s;      /* audio time before which every bin is final (returned) */
+    int32_t closed;            /* ss_stream_close was called */
+    int32_t finished;          /* closed and the last step has run: every result is out */
+    int64_t state_bytes;       /* bytes the stream carries between steps (device samples, logits, host record), staging excluded */
+} ss_stream_info;
+
+/* Open a stream; *stream_id names it on this context.  Needs a context with weights. */
+int ss_stream_open(ss_ctx* ctx, int format, int sample_rate, int channels, double threshold, double break_s, int* stream_id);
+/* Copy `frames` interleaved frames from host memory into the stream's staging (any number, 0 included).  Not after close. */
+int ss_stream_push(ss_ctx* ctx, int stream_id, const void* pcm, int64_t frames);
+/* End of input: the next step runs the windows that read the end padding, finalises the last bins and regions, and finishes it. */
+int ss_stream_close(ss_ctx* ctx, int stream_id);
+/* One step over every stream of the context (see above).  Each stream's results of the previous step are replaced by this
+ * step's (empty when it had nothing new), so nothing accumulates when a caller does not read.  f16x2: a step whose passes set the
+ * range flag returns SS_ERR_RANGE and commits nothing -- every stream is as it was before the step, its staged input kept
+ * (ss_stream_export it into an fp32 context and step there). */
+int ss_stream_step(ss_ctx* ctx);
+/* The regions the last step finalised for the stream: seconds from the recording's start, the reference's -3 s applied, like
+ * ss_get_regions.  *n_out = count; SS_ERR_CAPACITY when it exceeds cap (out may be NULL to ask for the count). */
+int ss_stream_regions(ss_ctx* ctx, int stream_id, ss_region* out, int64_t cap, int64_t* n_out);
+/* The averaged bins the last step finalised (covered bins only, ascending), with the bin numbers ss_get_avg gives them for the
+ * whole recording.  Either pointer may be NULL. */
+int ss_stream_avg(ss_ctx* ctx, int stream_id, double* avg, int64_t* bin_idx, int64_t cap, int64_t* n_out);
+int ss_stream_get_info(ss_ctx* ctx, int stream_id, ss_stream_info* out);
+/* Release a stream, at any time. */
+int ss_stream_free(ss_ctx* ctx, int stream_id);
+/* A stream's whole state (staging included, the last step's results excluded) as a byte image: *n_out = its size (buf may be NULL
+ * to ask); SS_ERR_CAPACITY when cap is smaller.  ss_stream_import makes a new stream of another (or the same) context from it --
+ * of any precision: what the f16x2 fallback and a feed that moves to another device need. */
+int ss_stream_export(ss_ctx* ctx, int stream_id, void* buf, int64_t cap, int64_t* n_out);
+int ss_stream_import(ss_ctx* ctx, const void* buf, int64_t n, int* stream_id);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */
 int ss_sync(ss_ctx* ctx);

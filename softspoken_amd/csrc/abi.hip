@@ -93,6 +93,7 @@ extern "C" void ss_destroy(ss_ctx* c) {
     if (c->h_range_flag) hipHostFree(c->h_range_flag);
     if (c->d_above) hipFree(c->d_above);
     if (c->d_cov) hipFree(c->d_cov);
+    free_streams(c);
     delete c;
 }
 
@@ -134,7 +135,7 @@ static double bessel_i0(double x) {
     return s;
 }
 
-static int get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps) {
+int ss::get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps) {
     auto gcd = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
     const int g = gcd(sr_in, SS_SAMPLE_RATE);
     L = SS_SAMPLE_RATE / g; M = sr_in / g;
@@ -174,7 +175,7 @@ static int add_pcm_common(ss_ctx* c, const void* d_pcm, int format, int sr, int 
     return ss_add_pcm_batch_device(c, d_pcm, format, sr, ch, &frames, 1, file_id);
 }
 
-static int check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames) {
+int ss::check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
     if ((!pcm && frames > 0) || format < SS_PCM_U8 || format > SS_PCM_F64BE || sr <= 0 || sr > 768000 || ch < 1 || ch > 64 || frames < 0 ||
         frames > ((int64_t)1 << 36))          // (99 h at 192 kHz; keeps frames * channels * bytes and frames * 22050 inside 64 bits)

@@ -86,6 +86,8 @@ struct FileRec {
     int64_t bin_off = 0; int n_bins = 0;
 };
 
+struct StreamSet;                                         // stream.hip: the context's streams and their step buffers
+
 struct KStat { std::string name; int64_t launches = 0; double ms = 0, flops = 0, bytes = 0, issued = 0; };
 struct PendingEvt { int sid; hipEvent_t a, b; };
 
@@ -175,6 +177,9 @@ struct ss_ctx {
     bool logits_valid = false; int64_t total_windows = 0;
     hipEvent_t ev_run0 = nullptr, ev_run1 = nullptr; double last_run_ms = 0;
 
+    // streaming detection (stream.hip): separate from the job above -- ss_reset / ss_run do not touch it
+    ss::StreamSet* streams = nullptr;
+
     // profiling
     std::vector<ss::KStat> stats; std::vector<ss::PendingEvt> pending; std::vector<hipEvent_t> evpool;
 };
@@ -229,6 +234,11 @@ int run_poll(ss_ctx* c, ss_progress_fn progress, void* user, int block, const vo
 int run_end(ss_ctx* c);
 void ensure_regions(ss_ctx* c);
 int upload_winoff(ss_ctx* c, const std::vector<int64_t>& off);
+// abi.hip
+int check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames);
+int get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps);    // polyphase table of sr_in -> 22 050 Hz (cached)
+// stream.hip
+void free_streams(ss_ctx* c);
 // host.hip
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
 std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);

@@ -1089,6 +1089,23 @@ hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, in
 // Overlap averaging (NNDetector.py:168-186): window i adds its 256 logits at bin start[i] = round(51.2 i);
 // float64 sum in window order, divided by the count; bins never covered keep count 0 and are dropped later.
 // =========================================================================================================
+// One bin's average: the windows i < W whose 256 bins [start(i), start(i) + 256) hold bin j, their logit(i, j - start(i)) summed in
+// float64 in window order, divided by their count c (0.0 and c = 0 when none does).  Shared by the whole-file and the streaming kernel.
+template <class StartOf, class LogitOf>
+__device__ __forceinline__ double average_bin(int j, int W, StartOf start, LogitOf logit, int& c) {
+    int lo = (int)((double)(j - 255) / 51.2) - 1;
+    if (lo < 0) lo = 0;
+    int hi = (int)((double)j / 51.2) + 1;
+    if (hi > W - 1) hi = W - 1;
+    double s = 0.0;
+    c = 0;
+    for (int i = lo; i <= hi; ++i) {
+        const int d = j - start(i);
+        if (d >= 0 && d < 256) { s += (double)logit(i, d); ++c; }
+    }
+    return c ? s / (double)c : 0.0;
+}
+
 __global__ __launch_bounds__(256) void average_kernel(const float* __restrict__ logits, const AvgFile* __restrict__ files,
                                                       const int32_t* __restrict__ starts, double* __restrict__ avg,
                                                       int32_t* __restrict__ count) {
@@ -1096,17 +1113,9 @@ __global__ __launch_bounds__(256) void average_kernel(const float* __restrict__ 
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= fi.n_bins) return;
     const int32_t* st = starts + fi.start_off;
-    int lo = (int)((double)(j - 255) / 51.2) - 1;
-    if (lo < 0) lo = 0;
-    int hi = (int)((double)j / 51.2) + 1;
-    if (hi > fi.W - 1) hi = fi.W - 1;
-    double s = 0.0;
     int c = 0;
-    for (int i = lo; i <= hi; ++i) {
-        const int d = j - st[i];
-        if (d >= 0 && d < 256) { s += (double)logits[(fi.logit_off + i) * 256 + d]; ++c; }
-    }
-    avg[fi.bin_off + j] = c ? s / (double)c : 0.0;
+    avg[fi.bin_off + j] = average_bin(j, fi.W, [&](int i) { return st[i]; },
+                                      [&](int i, int d) { return logits[(fi.logit_off + i) * 256 + d]; }, c);
     count[fi.bin_off + j] = c;
 }
 
@@ -1135,6 +1144,103 @@ hipError_t launch_average(const float* logits, const AvgFile* files, int n_files
     if (n_files <= 0 || max_bins <= 0) return hipSuccess;
     hipLaunchKernelGGL(average_kernel, dim3((unsigned)((max_bins + 255) / 256), (unsigned)n_files), dim3(256), 0, s, logits, files,
                        starts, avg, count);
+    return hipGetLastError();
+}
+
+// =========================================================================================================
+// Streaming detection (stream.hip): the same per-output arithmetic as the whole-file kernels above, over the live pieces of many
+// streams in one launch each.  Every launch takes a descriptor per stream (blockIdx.y, strided past 65535) and walks its
+// elements with the grid's x dimension.
+// =========================================================================================================
+// carried state into the next step's arena (src == nullptr: zeros -- the 3 s of padding in front of and behind a stream)
+__global__ __launch_bounds__(256) void stream_copy_kernel(const StreamCopy* __restrict__ segs, int n_segs) {
+    for (int k = blockIdx.y; k < n_segs; k += gridDim.y) {
+        const StreamCopy sg = segs[k];
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < sg.n; i += (int64_t)gridDim.x * 256)
+            sg.dst[i] = sg.src ? sg.src[i] : 0.f;
+    }
+}
+
+// decode + channel mean of the frames pushed since the last step: decode_mono_batch_kernel's arithmetic (decode_sample, __fadd_rn in
+// channel order, __fdiv_rn by the channel count)
+__global__ __launch_bounds__(256) void stream_decode_kernel(const unsigned char* __restrict__ pcm, const StreamDecode* __restrict__ ds, int n) {
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamDecode d = ds[k];
+        const unsigned char* base = pcm + d.pcm_off;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.frames; i += (int64_t)gridDim.x * 256) {
+            float acc = decode_sample(base, d.format, i * d.channels);
+            for (int c = 1; c < d.channels; ++c) acc = __fadd_rn(acc, decode_sample(base, d.format, i * d.channels + c));
+            d.dst[i] = d.channels > 1 ? __fdiv_rn(acc, (float)d.channels) : acc;
+        }
+    }
+}
+
+// outputs [m0, m0 + n) of a stream from its decoded input history mono[idx - mono_base] (idx < frames; zeros past the end once the
+// stream is closed -- the host only asks for outputs whose taps lie inside the input before that): resample_batch_kernel's arithmetic,
+// tap order, float32 multiply then add, no contraction, so every output equals the whole-file resampler's bit for bit
+__global__ __launch_bounds__(256) void stream_resample_kernel(const StreamResample* __restrict__ rs, int n) {
+#pragma clang fp contract(off)
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamResample r = rs[k];
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < r.n; t += (int64_t)gridDim.x * 256) {
+            const int64_t m = r.m0 + t;
+            const int64_t pos = m * r.M;
+            const int64_t base = pos / r.L;
+            const int phase = (int)(pos - base * r.L);
+            const float* tp = r.taps + (size_t)phase * (2 * r.half);
+            float acc = 0.f;
+            for (int j = 0; j < 2 * r.half; ++j) {
+                const int64_t idx = base + j - r.half + 1;
+                const float sv = (idx >= r.mono_base && idx < r.frames) ? r.mono[idx - r.mono_base] : 0.f;
+                { const float pr = tp[j] * sv; acc = acc + pr; }   // two roundings, as the oracle
+            }
+            r.out[t] = acc;
+        }
+    }
+}
+
+// the bins [b0, b0 + nb) of a stream that became final: average_bin over the stream's windows [w0, W) whose logits lie back to back
+// from `logits` (window w0 first), start(i) = round(51.2 i) (= (512 i + 5) div 10: 256 i / 5 is never a tie), then the two bits
+// bin_masks_kernel makes of a bin with the stream's threshold (1: covered by a window, 2: average above the threshold)
+__global__ __launch_bounds__(256) void stream_average_kernel(const StreamAvg* __restrict__ as, int n, double* __restrict__ avg,
+                                                             unsigned char* __restrict__ flags) {
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamAvg a = as[k];
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < a.nb; t += (int64_t)gridDim.x * 256) {
+            const int j = (int)(a.b0 + t);
+            int c = 0;
+            const double v = average_bin(j, a.W, [](int i) { return (int)(((int64_t)512 * i + 5) / 10); },
+                                         [&](int i, int d) { return i >= a.w0 ? a.logits[(int64_t)(i - a.w0) * 256 + d] : __builtin_nanf(""); }, c);
+            const bool cov = c >= 1, abv = cov && v > a.threshold;
+            avg[a.out_off + t] = v;
+            flags[a.out_off + t] = (unsigned char)((cov ? 1 : 0) | (abv ? 2 : 0));
+        }
+    }
+}
+
+static dim3 stream_grid(int n, int64_t max_elems) {
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_elems + 255) / 256, 1024));
+    return dim3(gx, (unsigned)std::min(n, 65535));
+}
+
+hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s) {
+    if (n <= 0 || max_n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_copy_kernel, stream_grid(n, max_n), dim3(256), 0, s, d, n);
+    return hipGetLastError();
+}
+hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s) {
+    if (n <= 0 || max_frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_decode_kernel, stream_grid(n, max_frames), dim3(256), 0, s, (const unsigned char*)pcm, d, n);
+    return hipGetLastError();
+}
+hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s) {
+    if (n <= 0 || max_n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_resample_kernel, stream_grid(n, max_n), dim3(256), 0, s, d, n);
+    return hipGetLastError();
+}
+hipError_t launch_stream_average(const StreamAvg* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s) {
+    if (n <= 0 || max_bins <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_average_kernel, stream_grid(n, max_bins), dim3(256), 0, s, d, n, avg, flags);
     return hipGetLastError();
 }
 

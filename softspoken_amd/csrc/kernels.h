@@ -163,4 +163,16 @@ hipError_t launch_average(const float* logits, const AvgFile* files, int n_files
 hipError_t launch_bin_masks(const double* avg, const int32_t* count, int64_t total_bins, double threshold, unsigned long long* above,
                             unsigned long long* covered, hipStream_t s);
 
+// ---- streaming detection (stream.hip): one launch per step for all streams, a descriptor per stream ----------------------------
+struct StreamCopy { const float* src; float* dst; int64_t n; };                       // src == nullptr: n zeros
+struct StreamDecode { int64_t pcm_off; int64_t frames; float* dst; int32_t format, channels; };
+// outputs [m0, m0 + n) -> out[0 .. n); input sample idx is mono[idx - mono_base] for mono_base <= idx < frames, zero past `frames`
+struct StreamResample { const float* mono; int64_t mono_base, frames; const float* taps; float* out; int64_t m0, n; int32_t L, M, half, pad; };
+// bins [b0, b0 + nb) from the windows [w0, W) whose logits lie back to back at `logits`; results at avg / flags [out_off ..)
+struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, nb, out_off; double threshold; };
+hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s);
+hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s);
+hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s);
+hipError_t launch_stream_average(const StreamAvg* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s);
+
 }  // namespace ss

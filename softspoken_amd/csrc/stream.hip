@@ -1,0 +1,566 @@
+// Streaming detection (include/softspoken.h, ss_stream_*): recordings whose PCM arrives in pieces, stepped together.  A step plans
+// every stream on the host, uploads all staged pieces and its descriptors in one copy, and rebuilds the streams' carried state in the
+// other half of a double-buffered arena:
+//   copy (carried samples / logits, padding zeros) -> decode + mixdown -> resample -> windows (forward_chunk, passes across streams)
+//   -> new logits behind the carried ones -> averaging of the bins that became final -> regions continued on the host.
+// Nothing of the stream state changes before the step has completed without SS_ERR_RANGE: the arena half the streams live in is only
+// read, and the host records are updated at the end (commit), so a refused step leaves every stream as it was.
+#include "engine.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+
+namespace ss {
+
+namespace {
+
+constexpr int64_t kPad = SS_WINDOW_SAMPLES;          // 3 s of zeros in front of and behind the recording (worker.py:58-62)
+constexpr int64_t kStep = SS_STEP_SAMPLES;
+
+int64_t win_start_bin(int64_t i) { return (512 * i + 5) / 10; }     // round(51.2 i), NNDetector.py:175 (256 i / 5 is never a tie)
+
+struct StreamRec {
+    int format = 0, sr = 0, ch = 0;
+    double thr = 0, brk = 0;
+    int L = 1, M = 1, half = 0;                       // 22 050 Hz: decoded straight into the signal (no resampler)
+    float* d_taps = nullptr;
+    int64_t frames_in = 0;                            // frames decoded so far
+    std::vector<unsigned char> staged; int64_t staged_frames = 0;
+    bool closed = false, finished = false;
+    // carried state, in the current arena half (float offsets) -- or in the host vectors after an import (on_host)
+    int64_t mono_off = 0, mono_base = 0, mono_n = 0;  // decoded input frames [mono_base, mono_base + mono_n)
+    int64_t sig_off = 0, sig_base = 0, sig_n = 0;     // padded 22 050 Hz samples [sig_base, sig_base + sig_n)
+    int64_t lg_off = 0, lg_w0 = 0, lg_n = 0;          // logits of windows [lg_w0, lg_w0 + lg_n)
+    bool on_host = false; std::vector<float> h_mono, h_sig, h_lg;
+    int64_t m_next = 0;                               // next resampled output (index into the unpadded signal)
+    int64_t win_run = 0, bins_done = 0;
+    // region walk (engine.hip ensure_regions, carried across steps)
+    bool have = false, run_open = false; ss_region cur{0, 0}; int64_t run_first = 0, run_last = 0;
+    // the last step's results
+    std::vector<ss_region> r_out; std::vector<double> a_out; std::vector<int64_t> b_out;
+};
+
+// what the next step does with a stream (host arithmetic only)
+struct StreamPlan {
+    int64_t F = 0;                                    // frames decoded after the step
+    bool closing = false;
+    int64_t kb = 0, mono_keep = 0;                    // mono history kept: [kb, frames_in), then the new frames
+    int64_t m_end = 0;                                // outputs [m_next, m_end) are computed
+    int64_t base_new = 0, sig_keep = 0, pre = 0, post = 0;   // signal: carried [base_new, +sig_keep), pre zeros, outputs, post zeros
+    int64_t i_end = 0;                                // windows [win_run, i_end) run
+    int64_t b_end = 0; int W_avg = 0;                 // bins [bins_done, b_end) become final
+    int64_t lw0 = 0;                                  // logits in the step's arena: windows [lw0, i_end)
+    // offsets in the next arena half
+    int64_t mono_off = 0, sig_off = 0, lg_off = 0, up_off = 0, host_off = 0;
+    int64_t mono_len() const { return F - kb; }
+    int64_t sig_len() const { return sig_keep + pre + (m_end - m_next_) + post; }
+    int64_t m_next_ = 0;
+};
+
+int64_t n22_of(const StreamRec& s, int64_t F) { return ss_resampled_length(F, s.sr); }
+
+// run_begin's plan of a file of F frames: window count (clamped to the padded signal) and bin count
+void file_plan(const StreamRec& s, int64_t F, int64_t& W, int64_t& n_bins) {
+    const int64_t n_padded = n22_of(s, F) + 2 * kPad;
+    W = ss_plan_windows((double)F / (double)s.sr, nullptr, 0);
+    while (W > 0 && (W - 1) * kStep + SS_WINDOW_SAMPLES > n_padded) --W;
+    n_bins = (int64_t)std::nearbyint((double)n_padded / 22050.0 * 256.0 / 3.0);
+}
+
+StreamPlan plan_stream(const StreamRec& s) {
+    StreamPlan p;
+    p.m_next_ = s.m_next;
+    p.F = s.frames_in + s.staged_frames;
+    p.closing = s.closed;
+    const bool direct = s.sr == SS_SAMPLE_RATE;
+    // outputs whose taps all lie inside the input (or past a closed stream's end)
+    int64_t m_end;
+    if (direct) m_end = p.F;
+    else if (p.closing) m_end = n22_of(s, p.F);
+    else {
+        const int64_t X = p.F - s.half;               // output m needs input frames up to floor(m M / L) + half
+        m_end = X > 0 ? std::min((X * s.L + s.M - 1) / s.M, n22_of(s, p.F)) : 0;
+    }
+    p.m_end = std::max(m_end, s.m_next);
+    if (!direct) {
+        const int64_t k0 = std::max<int64_t>(0, (s.m_next * s.M) / s.L - s.half + 1);   // first input the next outputs read
+        p.kb = std::min(std::max(k0, s.mono_base), s.frames_in);
+        p.mono_keep = s.frames_in - p.kb;
+    }
+    p.base_new = s.win_run * kStep;
+    const int64_t sig_end = s.sig_base + s.sig_n;
+    p.sig_keep = sig_end - p.base_new;
+    p.pre = sig_end < kPad ? kPad - sig_end : 0;      // a new stream: the 3 s in front
+    int64_t W_plan, nb_plan;
+    file_plan(s, p.F, W_plan, nb_plan);
+    if (p.closing) {
+        p.post = kPad;
+        p.i_end = W_plan;
+        p.b_end = nb_plan;
+    } else {
+        // window i reads the unpadded samples [i 13230 - 66150, i 13230); the plan of F frames is a lower bound of the final one
+        p.i_end = std::min(p.m_end / kStep + 1, W_plan);
+        p.b_end = std::min(win_start_bin(p.i_end), nb_plan);       // every window that starts at or before such a bin has run
+    }
+    p.i_end = std::max(p.i_end, s.win_run);
+    p.b_end = std::max(p.b_end, s.bins_done);
+    p.W_avg = (int)p.i_end;
+    p.lw0 = s.lg_n > 0 ? s.lg_w0 : s.win_run;
+    return p;
+}
+
+// windows whose logits the bins from b on still need: start(i) + 256 > b
+int64_t first_window_for_bin(int64_t b) {
+    int64_t i = std::max<int64_t>(0, (b - 256) * 10 / 512 - 1);
+    while (win_start_bin(i) + 256 <= b) ++i;
+    return i;
+}
+
+}  // namespace
+
+struct StreamSet {
+    std::map<int, StreamRec> s;
+    int next_id = 0;
+    float* arena[2] = {nullptr, nullptr}; size_t arena_cap[2] = {0, 0}; int cur = 0;
+    unsigned char* d_up = nullptr; size_t up_cap = 0;                    // the step's upload: PCM, host carries, descriptors, window offsets
+    unsigned char* h_up = nullptr; size_t h_up_cap = 0;                  // pinned
+    float* d_newlg = nullptr; size_t newlg_cap = 0;
+    double* d_avg = nullptr; size_t avg_cap = 0;
+    unsigned char* d_flags = nullptr; size_t flags_cap = 0;
+    std::vector<double> h_avg; std::vector<unsigned char> h_flags;
+};
+
+void free_streams(ss_ctx* c) {
+    StreamSet* S = c->streams;
+    if (!S) return;
+    for (float* a : S->arena) if (a) hipFree(a);
+    void* ds[] = {S->d_up, S->d_newlg, S->d_avg, S->d_flags};
+    for (void* p : ds) if (p) hipFree(p);
+    if (S->h_up) hipHostFree(S->h_up);
+    delete S;
+    c->streams = nullptr;
+}
+
+}  // namespace ss
+
+using namespace ss;
+
+static StreamSet& streams_of(ss_ctx* c) {
+    if (!c->streams) c->streams = new StreamSet();
+    return *c->streams;
+}
+
+static StreamRec* find_stream(ss_ctx* c, int id) {
+    if (!c || !c->streams) return nullptr;
+    auto it = c->streams->s.find(id);
+    return it == c->streams->s.end() ? nullptr : &it->second;
+}
+
+static int64_t state_bytes(const StreamRec& s) {
+    return (int64_t)sizeof(StreamRec) + 4 * (s.mono_n + s.sig_n + s.lg_n * 256);
+}
+
+static int init_rates(ss_ctx* c, StreamRec& s) {
+    if (s.sr == SS_SAMPLE_RATE) { s.L = s.M = 1; s.half = 0; s.d_taps = nullptr; return SS_OK; }
+    return get_taps(c, s.sr, s.L, s.M, s.half, &s.d_taps);
+}
+
+extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, int* id) {
+    static const unsigned char one[8] = {0};
+    int rc = check_pcm_args(c, one, format, sr, ch, 0);
+    if (rc) return rc;
+    if (!id || !std::isfinite(threshold) || !std::isfinite(break_s)) return fail(c, SS_ERR_ARG, "ss_stream_open: bad argument");
+    if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
+    hipSetDevice(c->device);
+    StreamRec s;
+    s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.brk = break_s;
+    if ((rc = init_rates(c, s))) return rc;
+    StreamSet& S = streams_of(c);
+    *id = S.next_id++;
+    S.s.emplace(*id, std::move(s));
+    return SS_OK;
+}
+
+extern "C" int ss_stream_push(ss_ctx* c, int id, const void* pcm, int64_t frames) {
+    StreamRec* s = find_stream(c, id);
+    if (!s) return fail(c, SS_ERR_ARG, "ss_stream_push: no such stream");
+    if (s->closed) return fail(c, SS_ERR_STATE, "ss_stream_push: the stream is closed");
+    int rc = check_pcm_args(c, pcm, s->format, s->sr, s->ch, frames);
+    if (rc) return rc;
+    if (s->frames_in + s->staged_frames + frames > ((int64_t)1 << 36)) return fail(c, SS_ERR_ARG, "ss_stream_push: stream too long");
+    const size_t nb = (size_t)frames * s->ch * pcm_bytes_per_sample(s->format);
+    if (nb) s->staged.insert(s->staged.end(), (const unsigned char*)pcm, (const unsigned char*)pcm + nb);
+    s->staged_frames += frames;
+    return SS_OK;
+}
+
+extern "C" int ss_stream_close(ss_ctx* c, int id) {
+    StreamRec* s = find_stream(c, id);
+    if (!s) return fail(c, SS_ERR_ARG, "ss_stream_close: no such stream");
+    s->closed = true;
+    return SS_OK;
+}
+
+extern "C" int ss_stream_free(ss_ctx* c, int id) {
+    if (!find_stream(c, id)) return fail(c, SS_ERR_ARG, "ss_stream_free: no such stream");
+    c->streams->s.erase(id);
+    return SS_OK;
+}
+
+extern "C" int ss_stream_get_info(ss_ctx* c, int id, ss_stream_info* out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !out) return fail(c, SS_ERR_ARG, "ss_stream_get_info: bad argument");
+    memset(out, 0, sizeof(*out));
+    out->frames_pushed = s->frames_in + s->staged_frames;
+    out->frames_staged = s->staged_frames;
+    out->windows_run = s->win_run;
+    out->windows_ready = s->finished ? 0 : plan_stream(*s).i_end - s->win_run;
+    out->final_until_s = (double)s->bins_done * 3.0 / 256.0 - 3.0;
+    out->closed = s->closed; out->finished = s->finished;
+    out->state_bytes = state_bytes(*s);
+    return SS_OK;
+}
+
+extern "C" int ss_stream_regions(ss_ctx* c, int id, ss_region* out, int64_t cap, int64_t* n_out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_regions: bad argument");
+    *n_out = (int64_t)s->r_out.size();
+    if (!out) return SS_OK;
+    if (cap < *n_out) return fail(c, SS_ERR_CAPACITY, "ss_stream_regions: capacity < " + std::to_string(*n_out));
+    if (*n_out) memcpy(out, s->r_out.data(), s->r_out.size() * sizeof(ss_region));
+    return SS_OK;
+}
+
+extern "C" int ss_stream_avg(ss_ctx* c, int id, double* avg, int64_t* bin_idx, int64_t cap, int64_t* n_out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_avg: bad argument");
+    *n_out = (int64_t)s->a_out.size();
+    if (!avg && !bin_idx) return SS_OK;
+    if (cap < *n_out) return fail(c, SS_ERR_CAPACITY, "ss_stream_avg: capacity < " + std::to_string(*n_out));
+    if (*n_out && avg) memcpy(avg, s->a_out.data(), s->a_out.size() * 8);
+    if (*n_out && bin_idx) memcpy(bin_idx, s->b_out.data(), s->b_out.size() * 8);
+    return SS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// the step
+// ------------------------------------------------------------------------------------------------------
+// the region walk of engine.hip ensure_regions over bins in order, one bin at a time: a run opens at a bin above the threshold and
+// closes at the next covered bin that is not; runs merge while s0 - cur.end <= break_s.  A merged region is final once a covered
+// bin lies more than break_s after its end (bin times never decrease, so no later run can merge into it).
+static void walk_bin(StreamRec& s, int64_t j, unsigned char f) {
+    if (!(f & 1)) return;                                 // not covered: absent from the reference's series
+    if (f & 2) {
+        if (!s.run_open) { s.run_open = true; s.run_first = j; }
+        s.run_last = j;
+        return;
+    }
+    if (s.run_open) {
+        const double s0 = bin_time(s.run_first), e0 = bin_time(s.run_last);
+        if (s.have && s0 - s.cur.end <= s.brk) s.cur.end = e0;
+        else { if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.cur.start = s0; s.cur.end = e0; s.have = true; }
+        s.run_open = false;
+    }
+    if (s.have && bin_time(j) - s.cur.end > s.brk) { s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.have = false; }
+}
+
+static void finish_regions(StreamRec& s) {
+    if (s.run_open) {
+        const double s0 = bin_time(s.run_first), e0 = bin_time(s.run_last);
+        if (s.have && s0 - s.cur.end <= s.brk) s.cur.end = e0;
+        else { if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.cur.start = s0; s.cur.end = e0; s.have = true; }
+        s.run_open = false;
+    }
+    if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0});
+    s.have = false;
+}
+
+static int ensure_pinned(ss_ctx* c, unsigned char** p, size_t* cap, size_t need) {
+    if (need <= *cap && *p) return SS_OK;
+    if (*p) { HIPCHK(c, hipHostFree(*p)); *p = nullptr; *cap = 0; }
+    const size_t nc = std::max(need + need / 2, (size_t)1 << 16);
+    HIPCHK(c, hipHostMalloc((void**)p, nc, hipHostMallocDefault));
+    *cap = nc;
+    return SS_OK;
+}
+
+namespace {
+struct ArenaSwap {                                        // forward_chunk reads windows from c->d_arena: the stream arena for the passes
+    ss_ctx* c; float* saved;
+    ArenaSwap(ss_ctx* c_, float* a) : c(c_), saved(c_->d_arena) { c->d_arena = a; }
+    ~ArenaSwap() { c->d_arena = saved; }
+};
+}  // namespace
+
+extern "C" int ss_stream_step(ss_ctx* c) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the pinned upload buffer is rewritten below)
+    StreamSet& S = streams_of(c);
+    int rc;
+    // ---- plan every unfinished stream (host only; nothing is changed before the commit) ----
+    std::vector<std::pair<StreamRec*, StreamPlan>> act;
+    for (auto& kv : S.s) if (!kv.second.finished) act.emplace_back(&kv.second, plan_stream(kv.second));
+    // arena layout of the next half, upload layout, descriptors
+    const int nxt = S.cur ^ 1;
+    float* cur_arena = S.arena[S.cur];
+    auto al = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
+    int64_t arena_need = 0, up_bytes = 0, total_w = 0, total_b = 0;
+    for (auto& [sp, p] : act) {
+        const StreamRec& s = *sp;
+        if (s.sr != SS_SAMPLE_RATE) { p.mono_off = arena_need; arena_need = al(arena_need + p.mono_len(), 64); }
+        p.sig_off = arena_need; arena_need = al(arena_need + p.sig_len() + 64, 64);    // (+ 64: slack behind the last window, as the file arena)
+        p.lg_off = arena_need; arena_need = al(arena_need + (p.i_end - p.lw0) * 256, 64);
+        p.up_off = up_bytes; up_bytes = al(up_bytes + (int64_t)s.staged.size(), 16);
+        p.host_off = up_bytes;
+        if (s.on_host) up_bytes = al(up_bytes + 4 * (int64_t)(s.h_mono.size() + s.h_sig.size() + s.h_lg.size()), 16);
+        total_w += p.i_end - s.win_run;
+        total_b += p.b_end - s.bins_done;
+    }
+    std::vector<StreamCopy> pre, post;
+    std::vector<StreamDecode> dec;
+    std::vector<StreamResample> res;
+    std::vector<StreamAvg> avg;
+    std::vector<int64_t> winoff;
+    int64_t max_copy = 0, max_dec = 0, max_res = 0, max_bins = 0;
+    if ((rc = ensure(c, &S.arena[nxt], &S.arena_cap[nxt], (size_t)std::max<int64_t>(arena_need, 64)))) return rc;
+    float* A = S.arena[nxt];
+    const size_t desc_off = (size_t)al(up_bytes, 64);
+    // descriptors behind the data (they hold device addresses of the upload's copy, so its buffer is sized first): at most 5 copies
+    // before the passes, one after, one decode, one resample, one averaging per stream, the window offsets, 64-byte alignment of each
+    const size_t n_desc_bytes = act.size() * (6 * sizeof(StreamCopy) + sizeof(StreamDecode) + sizeof(StreamResample) + sizeof(StreamAvg)) +
+                                (size_t)total_w * 8 + 6 * 64;
+    const size_t up_total = desc_off + n_desc_bytes;
+    if ((rc = ensure(c, &S.d_up, &S.up_cap, up_total))) return rc;
+    if ((rc = ensure_pinned(c, &S.h_up, &S.h_up_cap, up_total))) return rc;
+    if ((rc = ensure(c, &S.d_newlg, &S.newlg_cap, (size_t)std::max<int64_t>(total_w, 1) * 256))) return rc;
+    if ((rc = ensure(c, &S.d_avg, &S.avg_cap, (size_t)std::max<int64_t>(total_b, 1)))) return rc;
+    if ((rc = ensure(c, &S.d_flags, &S.flags_cap, (size_t)std::max<int64_t>(total_b, 1)))) return rc;
+    int64_t w_at = 0, b_at = 0;
+    for (auto& [sp, p] : act) {
+        const StreamRec& s = *sp;
+        unsigned char* hu = S.h_up;
+        if (!s.staged.empty()) memcpy(hu + p.up_off, s.staged.data(), s.staged.size());
+        const float* hm = nullptr; const float* hs = nullptr; const float* hl = nullptr;
+        if (s.on_host) {
+            float* h = (float*)(hu + p.host_off);
+            memcpy(h, s.h_mono.data(), s.h_mono.size() * 4);
+            memcpy(h + s.h_mono.size(), s.h_sig.data(), s.h_sig.size() * 4);
+            memcpy(h + s.h_mono.size() + s.h_sig.size(), s.h_lg.data(), s.h_lg.size() * 4);
+            const float* dh = (const float*)(S.d_up + p.host_off);
+            hm = dh; hs = dh + s.h_mono.size(); hl = hs + s.h_sig.size();
+        } else {
+            hm = cur_arena + s.mono_off; hs = cur_arena + s.sig_off; hl = cur_arena + s.lg_off;
+        }
+        const bool direct = s.sr == SS_SAMPLE_RATE;
+        // carried mono history [kb, frames_in), then the new frames
+        if (!direct && p.mono_keep > 0) {
+            pre.push_back(StreamCopy{hm + (p.kb - s.mono_base), A + p.mono_off, p.mono_keep});
+            max_copy = std::max(max_copy, p.mono_keep);
+        }
+        // signal: carried [base_new, sig_end), the leading zeros of a new stream, outputs, the trailing zeros at close
+        if (p.sig_keep > 0) { pre.push_back(StreamCopy{hs + (p.base_new - s.sig_base), A + p.sig_off, p.sig_keep}); max_copy = std::max(max_copy, p.sig_keep); }
+        if (p.pre > 0) { pre.push_back(StreamCopy{nullptr, A + p.sig_off + p.sig_keep, p.pre}); max_copy = std::max(max_copy, p.pre); }
+        float* out0 = A + p.sig_off + p.sig_keep + p.pre;   // = padded index kPad + m_next
+        const int64_t n_new_out = p.m_end - s.m_next;
+        pre.push_back(StreamCopy{nullptr, out0 + n_new_out, p.post + 64});      // (+ 64: the slack behind the signal is zero, as in the file arena)
+        max_copy = std::max(max_copy, p.post + 64);
+        // logits carried [lw0, win_run)
+        if (s.lg_n > 0) { pre.push_back(StreamCopy{hl, A + p.lg_off, s.lg_n * 256}); max_copy = std::max(max_copy, s.lg_n * 256); }
+        if (s.staged_frames > 0) {
+            float* dst = direct ? out0 : A + p.mono_off + p.mono_keep;
+            dec.push_back(StreamDecode{(int64_t)p.up_off, s.staged_frames, dst, s.format, s.ch});
+            max_dec = std::max(max_dec, s.staged_frames);
+        }
+        if (!direct && n_new_out > 0) {
+            res.push_back(StreamResample{A + p.mono_off, p.kb, p.F, s.d_taps, out0, s.m_next, n_new_out, s.L, s.M, s.half, 0});
+            max_res = std::max(max_res, n_new_out);
+        }
+        // windows [win_run, i_end): arena offsets, their logits behind the carried ones
+        const int64_t nw = p.i_end - s.win_run;
+        for (int64_t i = s.win_run; i < p.i_end; ++i) winoff.push_back(p.sig_off + (i * kStep - p.base_new));
+        if (nw > 0) post.push_back(StreamCopy{S.d_newlg + (size_t)w_at * 256, A + p.lg_off + (s.win_run - p.lw0) * 256, nw * 256});
+        w_at += nw;
+        const int64_t nb = p.b_end - s.bins_done;
+        if (nb > 0) {
+            avg.push_back(StreamAvg{A + p.lg_off, p.lw0, p.W_avg, 0, s.bins_done, nb, b_at, s.thr});
+            max_bins = std::max(max_bins, nb);
+        }
+        b_at += nb;
+    }
+    // pack the descriptors behind the data
+    size_t at = desc_off;
+    auto put = [&](const void* src, size_t bytes) -> size_t { const size_t o = at; if (bytes) memcpy(S.h_up + at, src, bytes); at = (size_t)al((int64_t)(at + bytes), 64); return o; };
+    const size_t o_pre = put(pre.data(), pre.size() * sizeof(StreamCopy));
+    const size_t o_post = put(post.data(), post.size() * sizeof(StreamCopy));
+    const size_t o_dec = put(dec.data(), dec.size() * sizeof(StreamDecode));
+    const size_t o_res = put(res.data(), res.size() * sizeof(StreamResample));
+    const size_t o_avg = put(avg.data(), avg.size() * sizeof(StreamAvg));
+    const size_t o_win = put(winoff.data(), winoff.size() * 8);
+    if (at > up_total) return fail(c, SS_ERR_STATE, "ss_stream_step: upload layout overflow");   // (cannot happen: sized above)
+    // ---- device work ----
+    HIPCHK(c, hipMemcpyAsync(S.d_up, S.h_up, at, hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedLaunch sl(c, "stream_copy", 0.0, 8.0 * max_copy * pre.size());
+        HIPCHK(c, launch_stream_copy((const StreamCopy*)(S.d_up + o_pre), (int)pre.size(), max_copy, c->stream));
+    }
+    {
+        ScopedLaunch sl(c, "stream_decode", 0.0, 0.0);
+        HIPCHK(c, launch_stream_decode(S.d_up, (const StreamDecode*)(S.d_up + o_dec), (int)dec.size(), max_dec, c->stream));
+    }
+    {
+        ScopedLaunch sl(c, "stream_resample", 0.0, 0.0);
+        HIPCHK(c, launch_stream_resample((const StreamResample*)(S.d_up + o_res), (int)res.size(), max_res, c->stream));
+    }
+    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    if (total_w > 0) {
+        // passes of equal size, as run_begin
+        const int64_t n_pass = std::max<int64_t>(1, (total_w + c->chunk - 1) / c->chunk);
+        const int ch = (int)std::max<int64_t>(1, (total_w + n_pass - 1) / n_pass);
+        if ((rc = ensure_workspace(c, ch))) return rc;
+        ArenaSwap sw(c, A);
+        const int64_t* d_win = (const int64_t*)(S.d_up + o_win);
+        for (int64_t i0 = 0; i0 < total_w; i0 += ch) {
+            const int m = (int)std::min<int64_t>(ch, total_w - i0);
+            if ((rc = forward_chunk(c, d_win + i0, m, S.d_newlg + (size_t)i0 * 256, nullptr, nullptr))) return rc;
+        }
+    }
+    {
+        int64_t mx = 0; for (const StreamCopy& p : post) mx = std::max(mx, p.n);
+        ScopedLaunch sl(c, "stream_copy", 0.0, 8.0 * mx * post.size());
+        HIPCHK(c, launch_stream_copy((const StreamCopy*)(S.d_up + o_post), (int)post.size(), mx, c->stream));
+    }
+    {
+        ScopedLaunch sl(c, "stream_average", 0.0, (double)total_b * 1024 * 5 / 51.2 + (double)total_b * 9);
+        HIPCHK(c, launch_stream_average((const StreamAvg*)(S.d_up + o_avg), (int)avg.size(), max_bins, S.d_avg, S.d_flags, c->stream));
+    }
+    S.h_avg.resize((size_t)total_b); S.h_flags.resize((size_t)total_b);
+    if (total_b) {
+        HIPCHK(c, hipMemcpyAsync(S.h_avg.data(), S.d_avg, (size_t)total_b * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.h_flags.data(), S.d_flags, (size_t)total_b, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (c->d_range_flag) HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resolve_events(c);
+    if (c->h_range_flag && *c->h_range_flag)
+        return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; nothing of the step is committed: "
+                                     "move the streams that had windows in it to an fp32 context (ss_stream_export / ss_stream_import)");
+    // ---- commit ----
+    for (auto& kv : S.s) { kv.second.r_out.clear(); kv.second.a_out.clear(); kv.second.b_out.clear(); }
+    b_at = 0;
+    for (auto& [sp, p] : act) {
+        StreamRec& s = *sp;
+        const int64_t nb = p.b_end - s.bins_done;
+        for (int64_t k = 0; k < nb; ++k) {
+            const int64_t j = s.bins_done + k;
+            const unsigned char f = S.h_flags[(size_t)(b_at + k)];
+            if (f & 1) { s.a_out.push_back(S.h_avg[(size_t)(b_at + k)]); s.b_out.push_back(j); }
+            walk_bin(s, j, f);
+        }
+        b_at += nb;
+        const bool direct = s.sr == SS_SAMPLE_RATE;
+        const int64_t sig_end = p.base_new + p.sig_len();
+        s.frames_in = p.F; s.m_next = p.m_end; s.win_run = p.i_end; s.bins_done = p.b_end;
+        s.staged.clear(); s.staged.shrink_to_fit(); s.staged_frames = 0;
+        s.on_host = false; s.h_mono.clear(); s.h_sig.clear(); s.h_lg.clear();
+        if (p.closing) {
+            finish_regions(s);
+            s.finished = true;
+            s.mono_n = s.sig_n = s.lg_n = 0; s.mono_base = s.frames_in; s.sig_base = sig_end; s.lg_w0 = s.win_run;
+            continue;
+        }
+        // what the next step needs, inside the segments this step wrote
+        if (!direct) {
+            const int64_t k0 = std::min(std::max(p.kb, (p.m_end * s.M) / s.L - s.half + 1), p.F);
+            s.mono_base = k0; s.mono_n = p.F - k0; s.mono_off = p.mono_off + (k0 - p.kb);
+        }
+        s.sig_base = p.i_end * kStep; s.sig_n = sig_end - s.sig_base; s.sig_off = p.sig_off + (s.sig_base - p.base_new);
+        const int64_t w0 = std::min(std::max(first_window_for_bin(p.b_end), p.lw0), p.i_end);
+        s.lg_w0 = w0; s.lg_n = p.i_end - w0; s.lg_off = p.lg_off + (w0 - p.lw0) * 256;
+    }
+    S.cur = nxt;
+    return SS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// export / import: a stream's whole state as a byte image
+// ------------------------------------------------------------------------------------------------------
+namespace {
+struct ImageHdr {
+    char magic[8];
+    int32_t format, sr, ch, closed, finished, have, run_open, pad;
+    double thr, brk, cur_start, cur_end;
+    int64_t frames_in, staged_frames, staged_bytes, mono_base, mono_n, sig_base, sig_n, lg_w0, lg_n, m_next, win_run, bins_done, run_first, run_last;
+};
+constexpr char kMagic[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '1'};
+}  // namespace
+
+extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64_t* n_out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_export: bad argument");
+    const int64_t need = (int64_t)sizeof(ImageHdr) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
+    *n_out = need;
+    if (!buf) return SS_OK;
+    if (cap < need) return fail(c, SS_ERR_CAPACITY, "ss_stream_export: capacity < " + std::to_string(need));
+    ImageHdr h{};
+    memcpy(h.magic, kMagic, 8);
+    h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->have; h.run_open = s->run_open;
+    h.thr = s->thr; h.brk = s->brk; h.cur_start = s->cur.start; h.cur_end = s->cur.end;
+    h.frames_in = s->frames_in; h.staged_frames = s->staged_frames; h.staged_bytes = (int64_t)s->staged.size();
+    h.mono_base = s->mono_base; h.mono_n = s->mono_n; h.sig_base = s->sig_base; h.sig_n = s->sig_n; h.lg_w0 = s->lg_w0; h.lg_n = s->lg_n;
+    h.m_next = s->m_next; h.win_run = s->win_run; h.bins_done = s->bins_done; h.run_first = s->run_first; h.run_last = s->run_last;
+    unsigned char* o = (unsigned char*)buf;
+    memcpy(o, &h, sizeof h); o += sizeof h;
+    if (!s->staged.empty()) memcpy(o, s->staged.data(), s->staged.size());
+    o += s->staged.size();
+    float* f = (float*)o;                                 // (unaligned host memory is fine for memcpy / hipMemcpy)
+    if (s->on_host) {
+        memcpy(f, s->h_mono.data(), s->mono_n * 4); memcpy(f + s->mono_n, s->h_sig.data(), s->sig_n * 4);
+        memcpy(f + s->mono_n + s->sig_n, s->h_lg.data(), s->lg_n * 1024);
+        return SS_OK;
+    }
+    hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const float* a = c->streams->arena[c->streams->cur];
+    if (s->mono_n) HIPCHK(c, hipMemcpy(f, a + s->mono_off, s->mono_n * 4, hipMemcpyDeviceToHost));
+    if (s->sig_n) HIPCHK(c, hipMemcpy(f + s->mono_n, a + s->sig_off, s->sig_n * 4, hipMemcpyDeviceToHost));
+    if (s->lg_n) HIPCHK(c, hipMemcpy(f + s->mono_n + s->sig_n, a + s->lg_off, s->lg_n * 1024, hipMemcpyDeviceToHost));
+    return SS_OK;
+}
+
+extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) {
+    if (!c || !buf || !id || n < (int64_t)sizeof(ImageHdr)) return fail(c, SS_ERR_ARG, "ss_stream_import: bad argument");
+    if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
+    ImageHdr h;
+    memcpy(&h, buf, sizeof h);
+    static const unsigned char one[8] = {0};
+    if (memcmp(h.magic, kMagic, 8) != 0 || check_pcm_args(c, one, h.format, h.sr, h.ch, 0) != SS_OK || h.staged_bytes < 0 || h.mono_n < 0 ||
+        h.sig_n < 0 || h.lg_n < 0 || h.lg_n > 64 || h.mono_n > ((int64_t)1 << 32) || h.sig_n > ((int64_t)1 << 32) ||
+        n != (int64_t)sizeof h + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) ||
+        h.staged_bytes != h.staged_frames * h.ch * (int64_t)pcm_bytes_per_sample(h.format))
+        return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
+    hipSetDevice(c->device);
+    StreamRec s;
+    s.format = h.format; s.sr = h.sr; s.ch = h.ch; s.closed = h.closed; s.finished = h.finished; s.have = h.have; s.run_open = h.run_open;
+    s.thr = h.thr; s.brk = h.brk; s.cur = ss_region{h.cur_start, h.cur_end};
+    s.frames_in = h.frames_in; s.staged_frames = h.staged_frames;
+    s.mono_base = h.mono_base; s.mono_n = h.mono_n; s.sig_base = h.sig_base; s.sig_n = h.sig_n; s.lg_w0 = h.lg_w0; s.lg_n = h.lg_n;
+    s.m_next = h.m_next; s.win_run = h.win_run; s.bins_done = h.bins_done; s.run_first = h.run_first; s.run_last = h.run_last;
+    int rc = init_rates(c, s);
+    if (rc) return rc;
+    const unsigned char* p = (const unsigned char*)buf + sizeof h;
+    s.staged.assign(p, p + h.staged_bytes); p += h.staged_bytes;
+    s.h_mono.resize(h.mono_n); s.h_sig.resize(h.sig_n); s.h_lg.resize(h.lg_n * 256);
+    memcpy(s.h_mono.data(), p, h.mono_n * 4); p += h.mono_n * 4;
+    memcpy(s.h_sig.data(), p, h.sig_n * 4); p += h.sig_n * 4;
+    memcpy(s.h_lg.data(), p, h.lg_n * 1024);
+    s.on_host = true;
+    StreamSet& S = streams_of(c);
+    *id = S.next_id++;
+    S.s.emplace(*id, std::move(s));
+    return SS_OK;
+}

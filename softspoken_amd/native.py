@@ -50,6 +50,11 @@ class KernelStat(C.Structure):
                 ("bytes", C.c_double), ("issued_flops", C.c_double)]
 
 
+class StreamInfo(C.Structure):
+    _fields_ = [("frames_pushed", C.c_int64), ("frames_staged", C.c_int64), ("windows_run", C.c_int64), ("windows_ready", C.c_int64),
+                ("final_until_s", C.c_double), ("closed", C.c_int32), ("finished", C.c_int32), ("state_bytes", C.c_int64)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
 
 # every symbol include/softspoken.h declares: (restype, argtypes)
@@ -104,6 +109,16 @@ _SIGS = {
     "ss_get_kernel_stats": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "ss_last_run_device_ms": (C.c_double, [_P]),
     "ss_workspace_bytes": (C.c_int64, [_P]),
+    "ss_stream_open": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]),
+    "ss_stream_push": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
+    "ss_stream_close": (C.c_int, [_P, C.c_int]),
+    "ss_stream_step": (C.c_int, [_P]),
+    "ss_stream_regions": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_avg": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_get_info": (C.c_int, [_P, C.c_int, C.POINTER(StreamInfo)]),
+    "ss_stream_free": (C.c_int, [_P, C.c_int]),
+    "ss_stream_export": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_import": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
 }
 EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
@@ -470,3 +485,62 @@ class Context:
 
     def last_run_device_ms(self) -> float:
         return lib().ss_last_run_device_ms(self._h)
+
+    # ---- streaming detection (ss_stream_*): one recording's PCM in pieces; see include/softspoken.h ----------------------------
+    def stream_open(self, fmt: int, sr: int, channels: int, threshold: float = 0.1, break_s: float = 0.5) -> int:
+        sid = C.c_int(-1)
+        self._ck(lib().ss_stream_open(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s), C.byref(sid)))
+        return sid.value
+
+    def stream_push(self, sid: int, pcm: np.ndarray, frames: int | None = None, channels: int = 1, fmt: int | None = None):
+        """pcm: interleaved samples of the stream's encoding (any dtype whose bytes are that encoding); frames defaults to
+        pcm.nbytes // (channels x bytes per sample) when fmt is given, else to len(pcm) // channels."""
+        a = np.ascontiguousarray(pcm)
+        if frames is None:
+            frames = a.nbytes // (int(channels) * _BPS[fmt]) if fmt is not None else (a.shape[0] if a.ndim > 1 else a.size // int(channels))
+        if fmt is not None:
+            self._need_bytes(a, fmt, channels, frames)
+        self._ck(lib().ss_stream_push(self._h, int(sid), _ptr(a) if a.size else None, int(frames)))
+
+    def stream_close(self, sid: int):
+        self._ck(lib().ss_stream_close(self._h, int(sid)))
+
+    def stream_step(self):
+        self._ck(lib().ss_stream_step(self._h))
+
+    def stream_regions(self, sid: int):
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_regions(self._h, int(sid), None, 0, C.byref(n)))
+        arr = (Region * max(1, n.value))()
+        self._ck(lib().ss_stream_regions(self._h, int(sid), arr, n.value, C.byref(n)))
+        return [(arr[i].start, arr[i].end) for i in range(n.value)]
+
+    def stream_avg(self, sid: int):
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_avg(self._h, int(sid), None, None, 0, C.byref(n)))
+        a = np.empty(n.value, dtype=np.float64)
+        idx = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._ck(lib().ss_stream_avg(self._h, int(sid), _ptr(a), _ptr(idx), n.value, C.byref(n)))
+        return a, idx
+
+    def stream_info(self, sid: int) -> dict:
+        info = StreamInfo()
+        self._ck(lib().ss_stream_get_info(self._h, int(sid), C.byref(info)))
+        return {k: getattr(info, k) for k, _ in StreamInfo._fields_}
+
+    def stream_free(self, sid: int):
+        self._ck(lib().ss_stream_free(self._h, int(sid)))
+
+    def stream_export(self, sid: int) -> bytes:
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_export(self._h, int(sid), None, 0, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        self._ck(lib().ss_stream_export(self._h, int(sid), _ptr(buf), n.value, C.byref(n)))
+        return buf.tobytes()
+
+    def stream_import(self, image: bytes) -> int:
+        a = np.frombuffer(image, dtype=np.uint8)
+        sid = C.c_int(-1)
+        self._ck(lib().ss_stream_import(self._h, _ptr(a), a.size, C.byref(sid)))
+        return sid.value

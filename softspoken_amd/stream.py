@@ -1,0 +1,122 @@
+"""Streaming detection on one device: many recordings whose PCM arrives in pieces, stepped together (ss_stream_* of
+include/softspoken.h).  Every region and averaged bin a stream returns is final, and their concatenation equals what the whole-file
+run gives for the same frames.
+
+    det = StreamDetector(blob, precision="f16x2")
+    s = det.open(PCM_S16, 16000, 1, threshold=0.1, break_s=0.5)
+    s.push(samples)                    # any number of frames, as they arrive
+    for stream, (regions, avg, bin_idx) in det.step().items(): ...
+    s.close(); det.step()              # the last results
+
+The f16x2 mode reports SS_ERR_RANGE for a step whose passes met a value without an f16 representation (a NaN or Inf sample of a
+float stream), and commits nothing of it.  The rule of the drop-in (SpecUNet_2D.range_refused): the first such step says nothing about
+the checkpoint -- the streams that had windows in it move to an fp32 context of the same weights (ss_stream_export / import) and
+finish there, the others stay; a second one does, and every stream, open or new, moves to fp32 with one log line.
+"""
+from __future__ import annotations
+
+import logging
+
+import numpy as np
+
+from . import native as _native
+
+
+class Stream:
+    """One recording of a StreamDetector.  Hashable: step() returns its results keyed by it."""
+
+    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int):
+        self._det, self._ctx, self._sid = det, ctx, sid
+        self.format, self.sample_rate, self.channels = fmt, sr, channels
+
+    def push(self, pcm: np.ndarray):
+        """Interleaved samples in the stream's encoding (int16 for PCM_S16, float32 for PCM_F32, raw bytes for 24-bit, ...)."""
+        a = np.ascontiguousarray(pcm)
+        frames = a.nbytes // (self.channels * _native._BPS[self.format])
+        self._ctx.stream_push(self._sid, a, frames=frames)
+
+    def close(self):
+        self._ctx.stream_close(self._sid)
+
+    def info(self) -> dict:
+        return self._ctx.stream_info(self._sid)
+
+    @property
+    def precision(self) -> str:
+        return self._ctx.precision
+
+
+class StreamDetector:
+    def __init__(self, blob=None, device: int = 0, precision: str = "f16x2", chunk: int | None = None, context_factory=None):
+        """context_factory(precision) -> a native.Context (or a stand-in with its stream_* methods); default: one of `blob`'s weights
+        on `device`."""
+        self._factory = context_factory or (lambda p: _native.Context(blob, device, precision=p, chunk=chunk))
+        self._main = self._factory(precision)
+        self._fp32 = self._main if precision == "fp32" else None
+        self._streams: list[Stream] = []
+        self._refused_steps = 0
+        self._switched = False
+
+    @property
+    def precision(self) -> str:
+        return "fp32" if self._switched else self._main.precision
+
+    def _fp32_ctx(self):
+        if self._fp32 is None:
+            self._fp32 = self._factory("fp32")
+        return self._fp32
+
+    def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5) -> Stream:
+        ctx = self._fp32_ctx() if self._switched else self._main
+        s = Stream(self, ctx, ctx.stream_open(fmt, sr, channels, threshold, break_s), fmt, sr, channels)
+        self._streams.append(s)
+        return s
+
+    def free(self, s: Stream):
+        s._ctx.stream_free(s._sid)
+        self._streams.remove(s)
+
+    def _move(self, s: Stream):
+        image = s._ctx.stream_export(s._sid)
+        ctx = self._fp32_ctx()
+        sid = ctx.stream_import(image)
+        s._ctx.stream_free(s._sid)
+        s._ctx, s._sid = ctx, sid
+
+    def _step_main(self):
+        """Step the first context; on SS_ERR_RANGE apply the range rule and step it again without the streams that moved."""
+        while True:
+            try:
+                self._main.stream_step()
+                return
+            except _native.NativeError as e:
+                if e.code != _native.SS_ERR_RANGE or self._main is self._fp32 or self._switched:
+                    raise
+                self._refused_steps += 1
+                on_main = [s for s in self._streams if s._ctx is self._main]
+                if self._refused_steps >= 2:
+                    logging.warning("f16x2 mode refused a second streaming step (%s): every stream moves to the fp32 mode", e)
+                    self._switched = True
+                    for s in on_main:
+                        self._move(s)
+                    return
+                for s in on_main:
+                    if s.info()["windows_ready"] > 0:
+                        self._move(s)
+
+    def step(self) -> dict:
+        """One step over every stream -> {stream: (regions [(start, end)], avg float64[n], bin_idx int64[n])}: what became final."""
+        if not self._switched:
+            self._step_main()
+        if self._fp32 is not None and self._fp32 is not self._main:
+            self._fp32.stream_step()
+        out = {}
+        for s in self._streams:
+            a, idx = s._ctx.stream_avg(s._sid)
+            out[s] = (s._ctx.stream_regions(s._sid), a, idx)
+        return out
+
+    def close(self):
+        for c in {id(c): c for c in (self._main, self._fp32) if c is not None}.values():
+            if hasattr(c, "close"):
+                c.close()
