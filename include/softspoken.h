@@ -19,6 +19,9 @@
  *   ss_get_avg                             NNDetector.py:153-190 average_overlapping_detections
  *   ss_get_regions / ss_find_regions       NNDetector.py:103-143 find_speech_regions + worker.py:100
  *   ss_format_csv_rows                     worker.py:103-125 + root/code/frontend/silencer_ui.py:816-817 (DataFrame.to_csv text)
+ *   ss_separation_plan / _maps /           silencer_ui.py:974-998 (SilenceWorker.run) with the spec head the reference computes and drops:
+ *   ss_separate_pcm                        pytorch_neural_nets.py:125-130,184-185 (spec_output_conv, "env / speech separation"),
+ *                                          NNDetector.py:84-101 (process_batch's speech_pred), worker.py:78-79; averaging NNDetector.py:168-186
  *
  * Conventions: every function returns an int status (SS_OK == 0) unless stated; the caller owns all
  * host buffers passed in and they only need to stay alive for the duration of the call; the library
@@ -308,6 +311,76 @@ int ss_stream_free(ss_ctx* ctx, int stream_id);
  * of any precision: what the f16x2 fallback and a feed that moves to another device need. */
 int ss_stream_export(ss_ctx* ctx, int stream_id, void* buf, int64_t cap, int64_t* n_out);
 int ss_stream_import(ss_ctx* ctx, const void* buf, int64_t n, int* stream_id);
+
+/* ---- separation silencer: remove the speech part of the spectrum inside the erased intervals ---------------------------
+ * The second silencing method.  ss_silence_pcm zeroes every reviewed interval (silencer_ui.py:974-998), and with it whatever
+ * environmental sound overlaps the voice.  This one rebuilds the audio inside the same intervals from an STFT at the file's native
+ * rate with the speech part removed.  The mask is a per-band gain from the network's second head, spec_output_conv
+ * (pytorch_neural_nets.py:125-130,184-185: "env / speech separation", a ReLU'd (2, 128, 256) map per window that process_batch
+ * returns as speech_pred, NNDetector.py:84-101, and worker.py:78-79 drops).  Outside the intervals the output is bit for bit
+ * ss_silence_pcm's.  Definition, step by step:
+ *  1. Windows and bins follow the detector: ss_plan_windows' windows over the ss_add_pcm signal, window i covers the bins
+ *     round(51.2 i) .. + 255 (NNDetector.py:168-186), bin j is centred at (j + 0.5) 3 / 256 - 3 s (the reference's 3 / 256 s bin;
+ *     the true hop is 256 / 22050 s).  The spec head runs on every window that covers a needed bin (step 3) and on no other.
+ *     Each needed bin averages both channels over the windows that cover it: a float64 sum in ascending window order divided by
+ *     the count, stored as float32 -- equal to a whole-file average bit for bit.
+ *  2. Band gains: P_c = 10^(y_c^2) - 1 (inverse of the front-end's sqrt(log10(x + 1))), G = P_env / (P_env + P_speech) evaluated as
+ *     a logistic of the log-power difference (finite for any finite y), G = 1 where both are 0, G' = max(G, min_gain).
+ *  3. STFT at the native rate: N = 2^round(log2(sr 512 / 22050)) clamped to [256, 8192], hop N / 4, periodic Hann analysis and
+ *     synthesis windows, overlap-add divided by sum w^2 = 1.5; frame k is centred on sample k hop (its support
+ *     [k hop - N/2, k hop + N/2), samples outside the file are zeros).  Only frames whose support meets a merged interval run.
+ *     STFT bin f = q sr / N Hz of frame k gets sum_m T_m(f) G'_m / sum_m T_m(f), T_m the front-end's HTK triangles (0 .. 8000 Hz,
+ *     128 bands, no norm), band 0's gain at f = 0, 1 (SS_ABOVE_FMAX_KEEP) or min_gain (SS_ABOVE_FMAX_MUTE) at f >= 8000 Hz;
+ *     in time, linear between the two bin centres around k hop / sr, clamped to the first / last bin that has a window.
+ *     Every channel has its own STFT; all share the gain map of the mono mix the model sees.  The overlap-add is a gather in
+ *     fixed frame order: two calls give identical bytes.
+ *  4. Inside a merged interval [a, b): y = x + w (p - x), x the decoded sample, p the resynthesis, w a raised-cosine ramp
+ *     w(d) = (1 - cos(pi (d + 0.5) / F)) / 2 over the F = round(fade_s sr) samples at each end (d = n - a at the start, b - 1 - n at
+ *     the end, the smaller of the two), 1 in between.  Encoded as ss_silence_pcm encodes: lrintf(y * 32767), no clipping.
+ * With min_gain 0, SS_ABOVE_FMAX_MUTE, fade_s 0 and a network whose speech map dominates everywhere, the output is ss_silence_pcm's. */
+#define SS_ABOVE_FMAX_MUTE 0   /* STFT bins at or above 8000 Hz (the model's f_max) get min_gain */
+#define SS_ABOVE_FMAX_KEEP 1   /* ... or pass unchanged */
+
+typedef struct ss_separation_params {
+    double fade_s;            /* >= 0; default 0.01 */
+    double min_gain;          /* in [0, 1]; default 0 */
+    int32_t above_fmax;       /* SS_ABOVE_FMAX_MUTE (default) or SS_ABOVE_FMAX_KEEP */
+    int32_t speech_channel;   /* channel of the spec head that holds speech: 0 or 1; default 1 (the reference's "env / speech" order;
+                                 the checkpoint itself is not at hand to confirm it) */
+} ss_separation_params;       /* NULL params: the defaults */
+
+typedef struct ss_separation_range {   /* one merged interval (silence_ranges' merge and rounding, as ss_silence_pcm) */
+    int64_t frame_begin, frame_end;    /* [a, b) in frames of the file */
+    int64_t stft_first, stft_last;     /* STFT frames k (inclusive) whose support meets [a, b); k may be negative */
+    int64_t bin_first, bin_last;       /* averaged bins (inclusive) their gains read */
+    int64_t win_first, win_last;       /* windows (inclusive) that cover any of those bins */
+} ss_separation_range;
+
+typedef struct ss_separation_plan_info {
+    int32_t n_fft, hop;                /* N and N / 4 */
+    int64_t n_windows;                 /* windows of the whole file (ss_plan_windows, clamped to the resampled signal as ss_run does) */
+    int64_t n_bins;                    /* bins 0 .. n_bins - 1 have a window (the whole-file average's covered bins) */
+    int64_t windows_run;               /* windows the spec head runs on: the union of the ranges' window ranges */
+    int64_t n_ranges;                  /* out: merged intervals */
+    int64_t cap_ranges;                /* in: entries `ranges` holds; SS_ERR_CAPACITY (n_ranges still set) when too few */
+    ss_separation_range* ranges;       /* in: caller's array (NULL when cap_ranges == 0) */
+} ss_separation_plan_info;
+
+/* Host only: the plan of ss_separate_pcm for a file of `frames` frames at sample_rate (the limits of ss_add_pcm).  SS_ERR_ARG for
+ * bad parameters: speech_channel not 0 / 1, fade_s < 0 or not finite, min_gain outside [0, 1], an unknown above_fmax. */
+int ss_separation_plan(int sample_rate, int64_t frames, const ss_region* regions, int64_t n_regions, const ss_separation_params* params,
+                       ss_separation_plan_info* out);
+/* Averaged spec-head maps (step 1) of bins [first_bin, first_bin + n_bins) of a file already added: out[2][n_bins][128] float32,
+ * channel-major as the head emits them.  Runs the spec head on exactly the windows that cover these bins (passes of
+ * ss_set_chunk_windows).  SS_ERR_ARG when a bin has no window; SS_ERR_RANGE under SS_FLAG_F16X2 as ss_infer_windows. */
+int ss_separation_maps(ss_ctx* ctx, int file_id, int64_t first_bin, int64_t n_bins, float* out);
+/* The separation silencer (above): interleaved PCM in (any enum ss_pcm_format, rate and channel count ss_add_pcm takes), interleaved
+ * 16-bit PCM out (frames * channels int16, as ss_silence_pcm).  Needs a context with weights (SS_ERR_STATE on an audio-only one or
+ * while a run is in flight).  It acts as ss_reset + ss_add_pcm of this file -- ss_reset_generation counts it, earlier file ids and
+ * the last run's results are gone --; streams are untouched.  SS_ERR_RANGE under SS_FLAG_F16X2 when the spec head's passes leave the
+ * f16 range (run the file in an fp32 context), with `out` not to be used. */
+int ss_separate_pcm(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, const ss_region* regions,
+                    int64_t n_regions, const ss_separation_params* params, int16_t* out);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */

@@ -94,6 +94,7 @@ extern "C" void ss_destroy(ss_ctx* c) {
     if (c->d_above) hipFree(c->d_above);
     if (c->d_cov) hipFree(c->d_cov);
     free_streams(c);
+    free_separation(c);
     delete c;
 }
 
@@ -231,6 +232,53 @@ extern "C" int ss_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, in
     HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // `ranges` and the caller's buffers are free again
     return SS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// separation silencer (separate.hip): silencer_ui.py:974-998 with the spec head of pytorch_neural_nets.py:125-130,184-185
+// ------------------------------------------------------------------------------------------------------
+extern "C" int ss_separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n_regions, const ss_separation_params* params,
+                                  ss_separation_plan_info* out) {
+    std::string err;
+    if (!out || (!regions && n_regions > 0) || n_regions < 0 || sr <= 0 || sr > 768000 || frames < 0 || frames > ((int64_t)1 << 36) ||
+        (out->cap_ranges > 0 && !out->ranges) || out->cap_ranges < 0)
+        return fail(nullptr, SS_ERR_ARG, "ss_separation_plan: bad argument");
+    if (int rc = check_separation_params(params, err)) return fail(nullptr, rc, "ss_separation_plan: " + err);
+    SepPlan pl;
+    separation_plan(sr, frames, regions, n_regions, pl);
+    out->n_fft = pl.N; out->hop = pl.hop; out->n_windows = pl.W; out->n_bins = pl.n_bins; out->windows_run = pl.windows_run;
+    out->n_ranges = (int64_t)pl.ranges.size();
+    if (out->n_ranges > out->cap_ranges)
+        return fail(nullptr, SS_ERR_CAPACITY, "ss_separation_plan: " + std::to_string(out->n_ranges) + " ranges, room for " + std::to_string(out->cap_ranges));
+    if (!pl.ranges.empty()) memcpy(out->ranges, pl.ranges.data(), pl.ranges.size() * sizeof(ss_separation_range));
+    return SS_OK;
+}
+
+static int check_model_idle(ss_ctx* c) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    return SS_OK;
+}
+
+extern "C" int ss_separation_maps(ss_ctx* c, int file_id, int64_t first_bin, int64_t n_bins, float* out) {
+    int rc = check_model_idle(c);
+    if (rc) return rc;
+    if (file_id < 0 || file_id >= (int)c->files.size() || !out) return fail(c, SS_ERR_ARG, "ss_separation_maps: bad file_id / output");
+    hipSetDevice(c->device);
+    return separation_maps(c, file_id, first_bin, n_bins, out);
+}
+
+extern "C" int ss_separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                               int64_t n_regions, const ss_separation_params* params, int16_t* out) {
+    int rc = check_model_idle(c);
+    if (rc) return rc;
+    if ((rc = check_pcm_args(c, pcm, format, sr, ch, frames))) return rc;
+    if ((!regions && n_regions > 0) || n_regions < 0 || (!out && frames > 0)) return fail(c, SS_ERR_ARG, "ss_separate_pcm: bad argument");
+    std::string err;
+    if ((rc = check_separation_params(params, err))) return fail(c, rc, "ss_separate_pcm: " + err);
+    hipSetDevice(c->device);
+    return separate_pcm(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 // ------------------------------------------------------------------------------------------------------

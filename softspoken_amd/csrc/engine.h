@@ -87,6 +87,14 @@ struct FileRec {
 };
 
 struct StreamSet;                                         // stream.hip: the context's streams and their step buffers
+struct SepState;                                          // separate.hip: the separation silencer's tables and buffers
+
+// separate.hip: ss_separation_plan's result (host only)
+struct SepPlan {
+    int N = 0, hop = 0;
+    int64_t W = 0, n_bins = 0, windows_run = 0;
+    std::vector<ss_separation_range> ranges;
+};
 
 struct KStat { std::string name; int64_t launches = 0; double ms = 0, flops = 0, bytes = 0, issued = 0; };
 struct PendingEvt { int sid; hipEvent_t a, b; };
@@ -179,6 +187,8 @@ struct ss_ctx {
 
     // streaming detection (stream.hip): separate from the job above -- ss_reset / ss_run do not touch it
     ss::StreamSet* streams = nullptr;
+    // separation silencer (separate.hip): per-rate FFT / band tables and its device buffers, allocated when first used
+    ss::SepState* sep = nullptr;
 
     // profiling
     std::vector<ss::KStat> stats; std::vector<ss::PendingEvt> pending; std::vector<hipEvent_t> evpool;
@@ -239,6 +249,15 @@ int check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64
 int get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps);    // polyphase table of sr_in -> 22 050 Hz (cached)
 // stream.hip
 void free_streams(ss_ctx* c);
+// separate.hip
+int sep_fft_size(int sr);
+int check_separation_params(const ss_separation_params* p, std::string& err);
+ss_separation_params separation_defaults();
+void separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n_regions, SepPlan& pl);
+int separation_maps(ss_ctx* c, int file_id, int64_t first_bin, int64_t n_bins, float* out);
+int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
+                 const ss_separation_params* params, int16_t* out);
+void free_separation(ss_ctx* c);
 // host.hip
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
 std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);

@@ -4,6 +4,7 @@
 // Reference: root/code/backend/voice_activity.py:32-69 (load_audio), root/code/backend/pytorch_neural_nets.py:92-99,
 // 144-153 (torchaudio MelSpectrogram(n_fft=2048, win_length=512, hop=256, n_mels=128, f_max=8000) then
 // sqrt(log10(.+1)) and [:, :, :256]), root/code/frontend/NNDetector.py:153-190 (averaging).
+#include "dsp.h"
 #include "kernels.h"
 #include <algorithm>
 #include <cstdlib>
@@ -31,41 +32,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // and log scaling follow from LDS.  A block = 4 waves = 32 consecutive frames of one window; the
 // [128 mel][32 frame] tile is staged in LDS and written as 64-byte row segments.
 // Nothing but the input samples and the feature tile touches HBM (no 1025 x 259 spectrogram).
+// (cmul / radix4 / fft16, the complex float2 forms, are in dsp.h: separate.hip uses them too)
 // =========================================================================================================
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-// forward radix-4 butterfly, W4 = -i
-__device__ __forceinline__ void radix4(float2 x0, float2 x1, float2 x2, float2 x3, float2& y0, float2& y1, float2& y2, float2& y3) {
-    const float2 s02 = cadd(x0, x2), d02 = csub(x0, x2), s13 = cadd(x1, x3), d13 = csub(x1, x3);
-    y0 = cadd(s02, s13);
-    y2 = csub(s02, s13);
-    y1 = make_float2(d02.x + d13.y, d02.y - d13.x);   // d02 - i d13
-    y3 = make_float2(d02.x - d13.y, d02.y + d13.x);   // d02 + i d13
-}
-
-// 16-point forward DFT in registers, natural order in and out (4 x 4 Cooley-Tukey).
-__device__ __forceinline__ void fft16(float2 (&v)[16]) {
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R2 = 0.70710678118654752f;
-    float2 t[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) radix4(v[j], v[j + 4], v[j + 8], v[j + 12], t[j][0], t[j][1], t[j][2], t[j][3]);
-    // twiddles W16^(j b)
-    t[1][1] = cmul(t[1][1], make_float2(C1, -S1));
-    t[1][2] = cmul(t[1][2], make_float2(R2, -R2));
-    t[1][3] = cmul(t[1][3], make_float2(S1, -C1));
-    t[2][1] = cmul(t[2][1], make_float2(R2, -R2));
-    t[2][2] = make_float2(t[2][2].y, -t[2][2].x);                 // W16^4 = -i
-    t[2][3] = cmul(t[2][3], make_float2(-R2, -R2));
-    t[3][1] = cmul(t[3][1], make_float2(S1, -C1));
-    t[3][2] = cmul(t[3][2], make_float2(-R2, -R2));
-    t[3][3] = cmul(t[3][3], make_float2(-C1, S1));               // W16^9
-#pragma unroll
-    for (int b = 0; b < 4; ++b) radix4(t[0][b], t[1][b], t[2][b], t[3][b], v[b], v[b + 4], v[b + 8], v[b + 12]);
-}
-
-// The same in packed fp32: a complex number is a 64-bit register pair, and an add, a subtract, a multiplication by -i (operand
+// The packed fp32 form of dsp.h's complex helpers: a complex number is a 64-bit register pair, and an add, a subtract, a multiplication by -i (operand
 // halves swapped, one negated) and each half of a complex product are single v_pk_*_f32 instructions -- the front-end kernel is
 // bound by vector-instruction issue, and this form has 0.6x the instructions of the scalar one (the compiler folds the swaps and
 // signs into op_sel / neg modifiers; built without the SLP vectoriser, which paired scalars with v_mov instead).
@@ -647,37 +617,9 @@ hipError_t launch_frontend(const float* arena, const int64_t* win_off, int n, co
 }
 
 // =========================================================================================================
-// PCM -> float32 mono.  libsndfile's float conversion (x / 2^(bits-1); unsigned 8-bit is offset by 128),
+// PCM -> float32 mono.  libsndfile's float conversion (x / 2^(bits-1); unsigned 8-bit is offset by 128: dsp.h decode_sample),
 // then librosa.to_mono == mean over channels in float32 (voice_activity.py:37-38, 61-62).
 // =========================================================================================================
-__device__ __forceinline__ float decode_sample(const unsigned char* p, int format, int64_t idx) {
-    switch (format) {
-        case 1: return ((float)p[idx] - 128.0f) / 128.0f;
-        case 2: return (float)((const short*)p)[idx] / 32768.0f;
-        case 3: {
-            const unsigned char* b = p + idx * 3;
-            int v = (int)b[0] | ((int)b[1] << 8) | ((int)b[2] << 16);
-            if (v & 0x800000) v -= 0x1000000;
-            return (float)v / 8388608.0f;
-        }
-        case 4: return (float)((double)((const int*)p)[idx] / 2147483648.0);
-        case 5: return ((const float*)p)[idx];
-        case 6: return (float)((const double*)p)[idx];
-        // AIFF / AIFF-C: big-endian samples, 8-bit ones signed; the same float conversion
-        case 7: return (float)(signed char)p[idx] / 128.0f;
-        case 8: { const unsigned char* b = p + idx * 2; return (float)(short)((unsigned)b[0] << 8 | b[1]) / 32768.0f; }
-        case 9: {
-            const unsigned char* b = p + idx * 3;
-            int v = (int)b[2] | ((int)b[1] << 8) | ((int)b[0] << 16);
-            if (v & 0x800000) v -= 0x1000000;
-            return (float)v / 8388608.0f;
-        }
-        case 10: return (float)((double)(int)__builtin_bswap32(((const uint32_t*)p)[idx]) / 2147483648.0);
-        case 11: return __builtin_bit_cast(float, __builtin_bswap32(((const uint32_t*)p)[idx]));
-        default: return (float)__builtin_bit_cast(double, __builtin_bswap64(((const uint64_t*)p)[idx]));
-    }
-}
-
 // =========================================================================================================
 // Polyphase Kaiser-windowed-sinc resampler to 22 050 Hz (stands where librosa.resample -> soxr_hq stands,
 // voice_activity.py:65-67).  out[m] = sum_j taps[(m M) mod L][j] * in[(m M) div L + j - half + 1].

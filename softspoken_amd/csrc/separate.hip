@@ -1,0 +1,587 @@
+// The separation silencer (include/softspoken.h "separation silencer"): inside the erased intervals, an STFT at the file's native rate
+// whose bins are scaled by a gain from the network's spec head (pytorch_neural_nets.py:125-130,184-185, "env / speech separation";
+// NNDetector.py:84-101 returns it as speech_pred, worker.py:78-79 drops it); outside them, ss_silence_pcm's transcode.
+//
+//   host   plan: merged intervals (silence_ranges) -> STFT frames -> averaged bins they read -> windows that cover those bins
+//   1      spec head over those windows (forward_chunk, passes of ss_set_chunk_windows) -> sep_accumulate_kernel after each pass:
+//          float64 sums per (bin, channel, band) in ascending window order, carried in memory across passes
+//   2      sep_finalize_kernel: sum / count -> float32 maps, band gains G' (logistic of the log-power difference)
+//   3      sep_stft_kernel<N>: per (frame, channel pair): decode + Hann -> FFT -> gain per STFT bin (two mel triangles x two bins in
+//          time) -> inverse FFT (conj / forward / conj) -> synthesis Hann / (1.5 N), one frame per slot of a buffer
+//   4      sep_blend_kernel: per output sample of an interval, the four overlapping frames gathered in ascending order, blended with
+//          the decoded sample over the fade ramps, encoded as ss_silence_pcm encodes
+// Everything else of the file is the transcode (silence_encode_kernel with no ranges), launched first.
+#include "engine.h"
+#include "dsp.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+
+namespace ss {
+
+struct SepFrame { int64_t k; int32_t cb0, cb1; float alpha; int32_t pad; };     // an STFT frame: centre k hop, gain rows cb0 / cb1
+struct SepSeg { int64_t a, b, s0, s1, k0, rec0, out0; };                          // an interval piece: interval [a, b), samples [s0, s1),
+                                                                                  // frames k0.. in records rec0.., first output slot out0
+struct SepBand { int32_t m0, m1; float w0, w1; };                                // STFT bin -> two mel bands and weights (m0 < 0: >= 8 kHz)
+
+struct SepTables { int N = 0; float2* tw = nullptr; float* win = nullptr; SepBand* band = nullptr; };
+
+struct SepState {
+    std::map<int, SepTables> tables;                      // per sample rate
+    int32_t* d_cbin = nullptr; size_t cbin_cap = 0;
+    int32_t* d_slot = nullptr; size_t slot_cap = 0;
+    double* d_sum = nullptr; size_t sum_cap = 0;
+    int32_t* d_count = nullptr; size_t count_cap = 0;
+    float* d_map = nullptr; size_t map_cap = 0;
+    float* d_gain = nullptr; size_t gain_cap = 0;
+    SepFrame* d_frames = nullptr; size_t frames_cap = 0;
+    SepSeg* d_segs = nullptr; size_t segs_cap = 0;
+    float2* d_fout = nullptr; size_t fout_cap = 0;
+};
+
+// =========================================================================================================
+// kernels
+// =========================================================================================================
+// One pass of the spec head: spec [m][2][128][256] holds the windows whose run-list positions (win_slot) are slot_lo .. slot_lo + m - 1.
+// Thread = (compact bin cb, channel x band cm); it adds the pass's windows over bin cbin[cb] to its float64 sum in ascending window order
+// (average_bin's window walk), so that the sum over all passes is the whole-file average's sum, bit for bit.
+__global__ __launch_bounds__(256) void sep_accumulate_kernel(const float* __restrict__ spec, int slot_lo, int m, const int32_t* __restrict__ win_slot,
+                                                             int W, const int32_t* __restrict__ cbin, int ncb, double* __restrict__ sum,
+                                                             int32_t* __restrict__ count) {
+    const int cb = blockIdx.x * 256 + threadIdx.x, cm = blockIdx.y;
+    if (cb >= ncb) return;
+    const int j = cbin[cb];
+    int lo = (int)((double)(j - 255) / 51.2) - 1;
+    if (lo < 0) lo = 0;
+    int hi = (int)((double)j / 51.2) + 1;
+    if (hi > W - 1) hi = W - 1;
+    double s = sum[(size_t)cm * ncb + cb];
+    int n = 0;
+    for (int i = lo; i <= hi; ++i) {
+        const int d = j - (int)(((int64_t)512 * i + 5) / 10);             // start(i) = round(51.2 i) (no ties: 512 i is even)
+        if (d < 0 || d >= 256) continue;
+        const int slot = win_slot[i] - slot_lo;
+        if (slot < 0 || slot >= m) continue;
+        s += (double)spec[((size_t)slot * 256 + cm) * 256 + d];
+        ++n;
+    }
+    sum[(size_t)cm * ncb + cb] = s;
+    if (cm == 0) count[cb] += n;
+}
+
+// ln(10^(y^2) - 1): the log power behind a feature value y = sqrt(log10(P + 1)); -inf at y = 0, finite for every finite y
+__device__ __forceinline__ double sep_log_power(double y) {
+    const double a = y * y * 2.302585092994045684;
+    if (a == 0.0) return -INFINITY;
+    return a > 30.0 ? a + log1p(-exp(-a)) : log(expm1(a));
+}
+
+// maps [2][ncb][128] = sum / count as float32; gain (nullable) [ncb][128] = max(P_env / (P_env + P_speech), min_gain)
+__global__ __launch_bounds__(256) void sep_finalize_kernel(const double* __restrict__ sum, const int32_t* __restrict__ count, int ncb,
+                                                           float* __restrict__ map, float* __restrict__ gain, int speech_ch, double min_gain) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)ncb * 128) return;
+    const int cb = (int)(idx >> 7), band = (int)(idx & 127);
+    const int n = count[cb];
+    float y[2];
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+        y[ch] = n ? (float)(sum[(size_t)(ch * 128 + band) * ncb + cb] / (double)n) : 0.f;
+        map[((size_t)ch * ncb + cb) * 128 + band] = y[ch];
+    }
+    if (!gain) return;
+    const double le = sep_log_power((double)y[1 - speech_ch]), ls = sep_log_power((double)y[speech_ch]);
+    double g;
+    if (le == -INFINITY && ls == -INFINITY) g = 1.0;              // no power in either: nothing to remove
+    else g = 1.0 / (1.0 + exp(ls - le));                         // P_e / (P_e + P_s); 0 when only speech has power, 1 when only env
+    gain[(size_t)cb * 128 + band] = (float)fmax(g, min_gain);
+}
+
+// small forward DFTs in registers, natural order in and out
+template <int R> __device__ __forceinline__ void sep_dft(float2 (&v)[R]);
+template <> __device__ __forceinline__ void sep_dft<2>(float2 (&v)[2]) { const float2 a = v[0]; v[0] = cadd(a, v[1]); v[1] = csub(a, v[1]); }
+template <> __device__ __forceinline__ void sep_dft<4>(float2 (&v)[4]) { radix4(v[0], v[1], v[2], v[3], v[0], v[1], v[2], v[3]); }
+template <> __device__ __forceinline__ void sep_dft<8>(float2 (&v)[8]) {
+    constexpr float R2 = 0.70710678118654752f;
+    float2 A[4], B[4];
+    radix4(v[0], v[2], v[4], v[6], A[0], A[1], A[2], A[3]);
+    radix4(v[1], v[3], v[5], v[7], B[0], B[1], B[2], B[3]);
+    B[1] = cmul(B[1], make_float2(R2, -R2));
+    B[2] = make_float2(B[2].y, -B[2].x);                          // W8^2 = -i
+    B[3] = cmul(B[3], make_float2(-R2, -R2));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = cadd(A[k], B[k]); v[k + 4] = csub(A[k], B[k]); }
+}
+template <> __device__ __forceinline__ void sep_dft<16>(float2 (&v)[16]) { fft16(v); }
+
+// one FFT of N points per (256 / T) threads; T = min(256, N / 16)
+template <int N> struct SepGeomT {
+    static constexpr int T = N / 16 < 256 ? N / 16 : 256;
+    static constexpr int ITEMS = 256 / T;
+    static constexpr int PITCH = N + N / 16;                      // float2 per FFT buffer: one pad slot behind every 16
+    static constexpr int LOG2 = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : N == 2048 ? 11 : N == 4096 ? 12 : 13;
+    static constexpr int R0 = 1 << (LOG2 % 4);                    // the first stage's radix (1: none), then radix-16 stages
+};
+__device__ __forceinline__ int sep_pad(int i) { return i + (i >> 4); }   // radix-16 stride writes spread over the banks
+
+// one Stockham stage (radix R, Ns = product of the earlier radices), in place: every thread's butterflies are read into registers,
+// a barrier, then written to their autosorted places, a barrier.  Twiddles W_N^t from a host table (double -> float).
+template <int N, int R>
+__device__ __forceinline__ void sep_stage(float2* buf, int lt, int Ns, const float2* __restrict__ tw) {
+    constexpr int T = SepGeomT<N>::T, NB = N / R / T;
+    float2 v[NB][R];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = lt + b * T, jm = j & (Ns - 1);
+        const int tstep = jm * (N / (Ns * R));
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float2 x = buf[sep_pad(j + r * (N / R))];
+            v[b][r] = r == 0 ? x : cmul(x, tw[tstep * r]);
+        }
+        sep_dft<R>(v[b]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = lt + b * T, jm = j & (Ns - 1);
+        const int d = (j - jm) * R + jm;
+#pragma unroll
+        for (int r = 0; r < R; ++r) buf[sep_pad(d + r * Ns)] = v[b][r];
+    }
+    __syncthreads();
+}
+
+template <int N>
+__device__ __forceinline__ void sep_fft(float2* buf, int lt, const float2* __restrict__ tw) {
+    constexpr int R0 = SepGeomT<N>::R0;
+    int Ns = 1;
+    if constexpr (R0 > 1) { sep_stage<N, R0>(buf, lt, 1, tw); Ns = R0; }
+#pragma unroll
+    for (int s = 0; s < SepGeomT<N>::LOG2 / 4; ++s) { sep_stage<N, 16>(buf, lt, Ns, tw); Ns *= 16; }
+}
+
+// Block = ITEMS frames of one channel pair (blockIdx.y): channels 2p and 2p + 1 ride as the real and imaginary parts of one complex FFT
+// (the gain is real and even in q, so the two stay apart).  out[rec][pair][N] = synthesis-windowed frame / (1.5 N), ready to gather.
+template <int N>
+__global__ __launch_bounds__(256) void sep_stft_kernel(const unsigned char* __restrict__ pcm, int format, int channels, int64_t frames,
+                                                       const SepFrame* __restrict__ fr, int n_fr, int hop, const float* __restrict__ gain,
+                                                       const SepBand* __restrict__ band, const float2* __restrict__ tw,
+                                                       const float* __restrict__ win, float gain_hi, float2* __restrict__ out) {
+    using G = SepGeomT<N>;
+    extern __shared__ float2 sep_lds[];
+    const int item = threadIdx.x / G::T, lt = threadIdx.x % G::T;
+    float2* buf = sep_lds + item * G::PITCH;
+    float* gt = (float*)(sep_lds + G::ITEMS * G::PITCH) + item * 128;
+    const int64_t rec = (int64_t)blockIdx.x * G::ITEMS + item;
+    const bool valid = rec < n_fr;
+    const int pair = blockIdx.y, npairs = gridDim.y, c0 = 2 * pair, c1 = 2 * pair + 1;
+    SepFrame f{0, 0, 0, 0.f, 0};
+    if (valid) f = fr[rec];
+    for (int m = lt; m < 128; m += G::T)                         // band gains at this frame's time: linear between two bins
+        gt[m] = valid ? (1.0f - f.alpha) * gain[(size_t)f.cb0 * 128 + m] + f.alpha * gain[(size_t)f.cb1 * 128 + m] : 0.f;
+    const int64_t base = f.k * hop - N / 2;
+    for (int n = lt; n < N; n += G::T) {
+        const int64_t s = base + n;
+        float x0 = 0.f, x1 = 0.f;
+        if (valid && s >= 0 && s < frames) {
+            x0 = decode_sample(pcm, format, s * channels + c0);
+            if (c1 < channels) x1 = decode_sample(pcm, format, s * channels + c1);
+        }
+        const float w = win[n];
+        buf[sep_pad(n)] = make_float2(x0 * w, x1 * w);
+    }
+    __syncthreads();
+    sep_fft<N>(buf, lt, tw);
+    for (int q = lt; q < N; q += G::T) {                         // X[q] g(q), conjugated: the inverse FFT is conj(FFT(conj(.))) / N
+        const SepBand bd = band[q <= N / 2 ? q : N - q];
+        const float g = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
+        const float2 X = buf[sep_pad(q)];
+        buf[sep_pad(q)] = make_float2(X.x * g, -X.y * g);
+    }
+    __syncthreads();
+    sep_fft<N>(buf, lt, tw);
+    if (!valid) return;
+    constexpr float kScale = 1.0f / (1.5f * (float)N);
+    float2* o = out + ((size_t)rec * npairs + pair) * N;
+    for (int n = lt; n < N; n += G::T) {
+        const float2 Y = buf[sep_pad(n)];
+        const float sc = win[n] * kScale;
+        o[n] = make_float2(Y.x * sc, -Y.y * sc);
+    }
+}
+
+// Output samples of the pieces in segs (out0 ascending, `total` samples in all) x channels: p = the four frames over the sample, added in
+// ascending frame order; y = x + w (p - x) over the fade ramps; lrintf(y * 32767) as silence_encode_kernel.
+__global__ __launch_bounds__(256) void sep_blend_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
+                                                        const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
+                                                        int npairs, const float2* __restrict__ fout, int64_t F, short* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t all = total * channels;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < all; idx += (int64_t)gridDim.x * 256) {
+        const int64_t t = idx / channels;
+        const int c = (int)(idx - t * channels);
+        int lo = 0, hi = n_segs - 1;                             // last piece with out0 <= t
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (segs[mid].out0 <= t) lo = mid; else hi = mid - 1;
+        }
+        const SepSeg sg = segs[lo];
+        const int64_t n = sg.s0 + (t - sg.out0);
+        const int64_t kb = n / hop;                              // frames kb - 1 .. kb + 2 hold sample n (N = 4 hop)
+        float p = 0.f;
+        for (int64_t k = kb - 1; k <= kb + 2; ++k) {
+            const float2 v = fout[((size_t)(sg.rec0 + (k - sg.k0)) * npairs + (c >> 1)) * N + (n - k * hop + N / 2)];
+            p += (c & 1) ? v.y : v.x;
+        }
+        const float x = decode_sample(pcm, format, n * channels + c);
+        const int64_t d = std::min(n - sg.a, sg.b - 1 - n);
+        const float w = d < F ? (float)(0.5 - 0.5 * cospi(((double)d + 0.5) / (double)F)) : 1.0f;
+        const float y = x + w * (p - x);
+        out[n * channels + c] = (short)__float2int_rn(y * 32767.0f);
+    }
+}
+
+// =========================================================================================================
+// host: plan
+// =========================================================================================================
+static int64_t floordiv(int64_t a, int64_t b) { int64_t q = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) --q; return q; }
+static int64_t win_start(int64_t i) { return (512 * i + 5) / 10; }
+
+int sep_fft_size(int sr) {
+    const double l = std::log2((double)sr * 512.0 / 22050.0);
+    const long e = std::lround(l);
+    return 1 << std::min<long>(13, std::max<long>(8, e));
+}
+
+// W and covered bins of a file whose padded signal holds n_padded samples and whose header says duration_s (ss_run's plan)
+static void file_geometry(double duration_s, int64_t n_padded, int64_t& W, int64_t& n_bins) {
+    W = ss_plan_windows(duration_s, nullptr, 0);
+    while (W > 0 && (W - 1) * (int64_t)SS_STEP_SAMPLES + SS_WINDOW_SAMPLES > n_padded) --W;
+    const int64_t nb = (int64_t)std::nearbyint((double)n_padded / 22050.0 * 256.0 / 3.0);
+    n_bins = W > 0 ? std::min(nb, win_start(W - 1) + 256) : 0;
+}
+
+// the two bins around frame k's time k hop / sr (centres (j + 0.5) 3 / 256 - 3 s) and the weight of the second; exact integers:
+// u = (k hop / sr + 3) 256 / 3 - 0.5 = (512 (k hop + 3 sr) - 3 sr) / (6 sr).  Clamped to bins 0 .. n_bins - 1.
+static void frame_bins(int64_t k, int hop, int sr, int64_t n_bins, int64_t& j0, int64_t& j1, double& alpha) {
+    const int64_t num = 512 * (k * hop + 3 * (int64_t)sr) - 3 * (int64_t)sr, den = 6 * (int64_t)sr;
+    j0 = floordiv(num, den);
+    alpha = (double)(num - j0 * den) / (double)den;
+    if (j0 < 0) { j0 = j1 = 0; alpha = 0.0; }
+    else if (j0 >= n_bins - 1) { j0 = j1 = n_bins - 1; alpha = 0.0; }
+    else j1 = j0 + 1;
+}
+
+// windows (inclusive) that cover any bin of [b0, b1]
+static void covering_windows(int64_t b0, int64_t b1, int64_t W, int64_t& w0, int64_t& w1) {
+    w0 = std::max<int64_t>(0, (int64_t)((double)(b0 - 255) / 51.2) - 2);
+    while (w0 < W - 1 && win_start(w0) + 255 < b0) ++w0;
+    w1 = std::min<int64_t>(W - 1, (int64_t)((double)b1 / 51.2) + 2);
+    while (w1 > 0 && win_start(w1) > b1) --w1;
+}
+
+int check_separation_params(const ss_separation_params* p, std::string& err) {
+    if (!p) return SS_OK;
+    if (p->speech_channel != 0 && p->speech_channel != 1) { err = "speech_channel must be 0 or 1"; return SS_ERR_ARG; }
+    if (!(p->fade_s >= 0.0) || !std::isfinite(p->fade_s)) { err = "fade_s must be a finite value >= 0"; return SS_ERR_ARG; }
+    if (!(p->min_gain >= 0.0 && p->min_gain <= 1.0)) { err = "min_gain must lie in [0, 1]"; return SS_ERR_ARG; }
+    if (p->above_fmax != SS_ABOVE_FMAX_MUTE && p->above_fmax != SS_ABOVE_FMAX_KEEP) { err = "above_fmax must be SS_ABOVE_FMAX_MUTE or _KEEP"; return SS_ERR_ARG; }
+    return SS_OK;
+}
+
+ss_separation_params separation_defaults() { return ss_separation_params{0.01, 0.0, SS_ABOVE_FMAX_MUTE, 1}; }
+
+void separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n_regions, SepPlan& pl) {
+    pl.N = sep_fft_size(sr); pl.hop = pl.N / 4;
+    const int64_t n_padded = ss_resampled_length(frames, sr) + 2 * (int64_t)SS_WINDOW_SAMPLES;
+    file_geometry((double)frames / (double)sr, n_padded, pl.W, pl.n_bins);
+    pl.ranges.clear(); pl.windows_run = 0;
+    const std::vector<int64_t> r = silence_ranges(regions, n_regions, sr, frames);
+    int64_t last_win = -1;
+    for (size_t i = 0; i + 1 < r.size(); i += 2) {
+        ss_separation_range g{};
+        g.frame_begin = r[i]; g.frame_end = r[i + 1];
+        g.stft_first = floordiv(g.frame_begin - pl.N / 2, pl.hop) + 1;
+        g.stft_last = -floordiv(-(g.frame_end + pl.N / 2), pl.hop) - 1;
+        int64_t a0, a1, b0, b1; double al;
+        frame_bins(g.stft_first, pl.hop, sr, pl.n_bins, a0, a1, al);
+        frame_bins(g.stft_last, pl.hop, sr, pl.n_bins, b0, b1, al);
+        g.bin_first = a0; g.bin_last = b1;
+        covering_windows(g.bin_first, g.bin_last, pl.W, g.win_first, g.win_last);
+        const int64_t from = std::max(g.win_first, last_win + 1);
+        if (g.win_last >= from) pl.windows_run += g.win_last - from + 1;
+        last_win = std::max(last_win, g.win_last);
+        pl.ranges.push_back(g);
+    }
+}
+
+// =========================================================================================================
+// host: device work
+// =========================================================================================================
+static SepState& sep_state(ss_ctx* c) {
+    if (!c->sep) c->sep = new SepState();
+    return *c->sep;
+}
+
+void free_separation(ss_ctx* c) {
+    if (!c->sep) return;
+    SepState& s = *c->sep;
+    for (auto& kv : s.tables) { hipFree(kv.second.tw); hipFree(kv.second.win); hipFree(kv.second.band); }
+    void* p[] = {s.d_cbin, s.d_slot, s.d_sum, s.d_count, s.d_map, s.d_gain, s.d_frames, s.d_segs, s.d_fout};
+    for (void* q : p) if (q) hipFree(q);
+    delete c->sep;
+    c->sep = nullptr;
+}
+
+// HTK mel points of the front-end's filterbank recipe (weights.hip build_tables: torchaudio's, in float32)
+static std::vector<double> mel_points() {
+    std::vector<double> f(130);
+    const float mmin = 0.f, mmax = (float)(2595.0 * std::log10(1.0 + 8000.0 / 700.0));
+    const float step = (mmax - mmin) / 129.0f;
+    for (int i = 0; i < 130; ++i) {
+        const float mp = i < 65 ? mmin + step * (float)i : mmax - step * (float)(129 - i);
+        f[i] = (double)(700.0f * (powf(10.0f, mp / 2595.0f) - 1.0f));
+    }
+    return f;
+}
+
+static int sep_tables(ss_ctx* c, int sr, SepTables** out) {
+    SepState& st = sep_state(c);
+    auto it = st.tables.find(sr);
+    if (it != st.tables.end()) { *out = &it->second; return SS_OK; }
+    const int N = sep_fft_size(sr);
+    const double PI = 3.14159265358979323846;
+    std::vector<float2> tw(N);
+    std::vector<float> win(N);
+    for (int t = 0; t < N; ++t) {
+        tw[t] = make_float2((float)std::cos(-2.0 * PI * t / N), (float)std::sin(-2.0 * PI * t / N));
+        win[t] = (float)(0.5 - 0.5 * std::cos(2.0 * PI * t / N));           // periodic Hann
+    }
+    const std::vector<double> fp = mel_points();
+    std::vector<SepBand> band(N / 2 + 1);
+    for (int q = 0; q <= N / 2; ++q) {
+        const double f = (double)q * sr / N;
+        SepBand b{0, 0, 1.f, 0.f};
+        if (f >= 8000.0) b.m0 = b.m1 = -1;
+        else if (q > 0) {
+            int m0 = -1; double t0 = 0, t1 = 0;
+            for (int m = 0; m < 128; ++m) {
+                const double T = std::max(0.0, std::min((f - fp[m]) / (fp[m + 1] - fp[m]), (fp[m + 2] - f) / (fp[m + 2] - fp[m + 1])));
+                if (T > 0) { if (m0 < 0) { m0 = m; t0 = T; } else { t1 = T; break; } }
+            }
+            if (m0 < 0) b.m0 = b.m1 = f >= fp[128] ? 127 : 0;                // between the last point and 8 kHz: the edge band
+            else { b.m0 = m0; b.m1 = t1 > 0 ? m0 + 1 : m0; b.w0 = (float)(t0 / (t0 + t1)); b.w1 = (float)(t1 / (t0 + t1)); }
+        }
+        band[q] = b;
+    }
+    SepTables tb; tb.N = N;
+    HIPCHK(c, hipMalloc((void**)&tb.tw, N * sizeof(float2)));
+    HIPCHK(c, hipMalloc((void**)&tb.win, N * sizeof(float)));
+    HIPCHK(c, hipMalloc((void**)&tb.band, band.size() * sizeof(SepBand)));
+    HIPCHK(c, hipMemcpy(tb.tw, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.win, win.data(), N * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.band, band.data(), band.size() * sizeof(SepBand), hipMemcpyHostToDevice));
+    *out = &(st.tables[sr] = tb);
+    return SS_OK;
+}
+
+// Step 1 (+ 2): the spec head over the windows win_ranges (merged, ascending) of file fid, averaged over the bins bin_ranges (merged,
+// ascending) -> st.d_map [2][ncb][128]; with gains (params non-null): st.d_gain [ncb][128].  Returns SS_ERR_RANGE when an f16x2 pass
+// left the f16 range.
+static int sep_run_maps(ss_ctx* c, int fid, int64_t W, const std::vector<std::pair<int64_t, int64_t>>& bin_ranges,
+                        const std::vector<std::pair<int64_t, int64_t>>& win_ranges, const ss_separation_params* params, int64_t& ncb_out) {
+    SepState& st = sep_state(c);
+    std::vector<int32_t> cbin, slot((size_t)W, -1);
+    for (auto& r : bin_ranges) for (int64_t j = r.first; j <= r.second; ++j) cbin.push_back((int32_t)j);
+    std::vector<int64_t> off;
+    const FileRec& f = c->files[fid];
+    for (auto& r : win_ranges)
+        for (int64_t i = r.first; i <= r.second; ++i) { slot[i] = (int32_t)off.size(); off.push_back(f.off + i * SS_STEP_SAMPLES); }
+    const int ncb = (int)cbin.size(), nw = (int)off.size();
+    ncb_out = ncb;
+    if (ncb == 0 || nw == 0) return SS_OK;
+    int rc;
+    if ((rc = ensure(c, &st.d_cbin, &st.cbin_cap, (size_t)ncb))) return rc;
+    if ((rc = ensure(c, &st.d_slot, &st.slot_cap, (size_t)W))) return rc;
+    if ((rc = ensure(c, &st.d_sum, &st.sum_cap, (size_t)ncb * 256))) return rc;
+    if ((rc = ensure(c, &st.d_count, &st.count_cap, (size_t)ncb))) return rc;
+    if ((rc = ensure(c, &st.d_map, &st.map_cap, (size_t)ncb * 256))) return rc;
+    if (params && (rc = ensure(c, &st.d_gain, &st.gain_cap, (size_t)ncb * 128))) return rc;
+    HIPCHK(c, hipMemcpyAsync(st.d_cbin, cbin.data(), (size_t)ncb * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.d_slot, slot.data(), (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.d_sum, 0, (size_t)ncb * 256 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.d_count, 0, (size_t)ncb * 4, c->stream));
+    if ((rc = upload_winoff(c, off))) return rc;                  // (synchronises: cbin, slot and off are free again)
+    const int ch = std::min(nw, c->chunk);
+    if ((rc = ensure_workspace(c, ch))) return rc;
+    if ((rc = ensure(c, &c->d_logits, &c->logits_cap, (size_t)ch * 256))) return rc;
+    if ((rc = ensure(c, &c->d_spec, &c->spec_cap, (size_t)ch * 2 * 32768))) return rc;
+    c->logits_valid = false;
+    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    for (int p0 = 0; p0 < nw; p0 += ch) {
+        const int m = std::min(ch, nw - p0);
+        if ((rc = forward_chunk(c, c->d_winoff + p0, m, c->d_logits, c->d_spec, nullptr))) return rc;
+        ScopedLaunch sl(c, "sep_accumulate_kernel", 256.0 * ncb * 6, (double)ncb * 256 * 16);
+        hipLaunchKernelGGL(sep_accumulate_kernel, dim3((unsigned)((ncb + 255) / 256), 256), dim3(256), 0, c->stream, c->d_spec, p0, m, st.d_slot,
+                           (int)W, st.d_cbin, ncb, st.d_sum, st.d_count);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        const int sp = params ? params->speech_channel : 1;
+        const double mg = params ? params->min_gain : 0.0;
+        ScopedLaunch sl(c, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)));
+        hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256)), dim3(256), 0, c->stream, st.d_sum, st.d_count, ncb,
+                           st.d_map, params ? st.d_gain : nullptr, sp, mg);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (c->d_range_flag) {
+        HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (*c->h_range_flag)
+            return fail(c, SS_ERR_RANGE, "f16x2: an activation of the spec head left the f16 range (|x| > 65504) or was not finite; run this file with the fp32 mode");
+    }
+    return SS_OK;
+}
+
+int separation_maps(ss_ctx* c, int fid, int64_t first_bin, int64_t n_bins, float* out) {
+    const FileRec& f = c->files[fid];
+    int64_t W, nb;
+    file_geometry(f.duration, f.n_padded, W, nb);
+    if (n_bins < 1 || first_bin < 0 || first_bin + n_bins > nb)
+        return fail(c, SS_ERR_ARG, "ss_separation_maps: bins [" + std::to_string(first_bin) + ", " + std::to_string(first_bin + n_bins) +
+                                       ") are not all covered by a window (covered: [0, " + std::to_string(nb) + "))");
+    int64_t w0, w1, ncb;
+    covering_windows(first_bin, first_bin + n_bins - 1, W, w0, w1);
+    int rc = sep_run_maps(c, fid, W, {{first_bin, first_bin + n_bins - 1}}, {{w0, w1}}, nullptr, ncb);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, sep_state(c).d_map, (size_t)n_bins * 256 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+template <int N>
+static hipError_t launch_sep_stft(const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
+                                  const float* gain, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
+    using G = SepGeomT<N>;
+    const size_t lds = (size_t)G::ITEMS * (G::PITCH * sizeof(float2) + 128 * sizeof(float));
+    static std::atomic<uint64_t> attr_done{0};
+    if (hipError_t e = allow_full_lds((const void*)sep_stft_kernel<N>, attr_done)) return e;
+    const dim3 grid((unsigned)((n_fr + G::ITEMS - 1) / G::ITEMS), (unsigned)((channels + 1) / 2));
+    hipLaunchKernelGGL(sep_stft_kernel<N>, grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr, hop, gain,
+                       tb.band, tb.tw, tb.win, gain_hi, out);
+    return hipGetLastError();
+}
+
+static hipError_t launch_sep_stft_n(int N, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
+                                    const float* gain, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
+    switch (N) {
+        case 256: return launch_sep_stft<256>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 512: return launch_sep_stft<512>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 1024: return launch_sep_stft<1024>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 2048: return launch_sep_stft<2048>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 4096: return launch_sep_stft<4096>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 8192: return launch_sep_stft<8192>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes of resynthesised frames held at once (pieces / chunks)
+
+int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
+                 const ss_separation_params* params, int16_t* out) {
+    const ss_separation_params prm = params ? *params : separation_defaults();
+    SepPlan pl;
+    separation_plan(sr, frames, regions, n_regions, pl);
+    int rc, fid = -1;
+    if ((rc = ss_reset(c))) return rc;
+    if ((rc = ss_add_pcm(c, pcm, format, sr, ch, frames, &fid))) return rc;     // signal in the arena, samples in c->d_pcm
+    if (frames == 0) return SS_OK;
+    SepState& st = sep_state(c);
+    const size_t total = (size_t)frames * ch;
+    if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
+    {   // the transcode of the whole file: what ss_silence_pcm writes outside its ranges
+        ScopedLaunch sl(c, "sep_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
+        HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, nullptr, 0, c->d_sil_out, c->stream));
+    }
+    if (!pl.ranges.empty()) {
+        // steps 1 + 2 over the merged bin and window ranges
+        std::vector<std::pair<int64_t, int64_t>> br, wr;
+        std::vector<int64_t> cbase;                               // compact index of each interval's first bin
+        int64_t ncb_run = 0;
+        for (const auto& g : pl.ranges) {
+            if (!br.empty() && g.bin_first <= br.back().second + 1) {
+                const int64_t at = ncb_run - (br.back().second - br.back().first + 1);
+                cbase.push_back(at + (g.bin_first - br.back().first));
+                if (g.bin_last > br.back().second) { ncb_run += g.bin_last - br.back().second; br.back().second = g.bin_last; }
+            } else {
+                cbase.push_back(ncb_run);
+                br.emplace_back(g.bin_first, g.bin_last);
+                ncb_run += g.bin_last - g.bin_first + 1;
+            }
+            if (!wr.empty() && g.win_first <= wr.back().second + 1) wr.back().second = std::max(wr.back().second, g.win_last);
+            else wr.emplace_back(g.win_first, g.win_last);
+        }
+        int64_t ncb = 0;
+        if ((rc = sep_run_maps(c, fid, pl.W, br, wr, &prm, ncb))) return rc;
+        // step 3 + 4: pieces of at most `piece` samples, chunks of at most `budget` frames
+        SepTables* tb = nullptr;
+        if ((rc = sep_tables(c, sr, &tb))) return rc;
+        const int N = pl.N, hop = pl.hop, npairs = (ch + 1) / 2;
+        const int64_t budget = std::max<int64_t>(16, (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2))));
+        const int64_t piece = (budget - 8) * hop;
+        std::vector<SepFrame> fr;
+        std::vector<SepSeg> sg;
+        struct Chunk { size_t seg0, nseg, rec0, nrec; int64_t total; };
+        std::vector<Chunk> chunks;
+        for (size_t r = 0; r < pl.ranges.size(); ++r) {
+            const auto& g = pl.ranges[r];
+            for (int64_t s0 = g.frame_begin; s0 < g.frame_end; s0 += piece) {
+                const int64_t s1 = std::min(g.frame_end, s0 + piece);
+                const int64_t k0 = floordiv(s0 - N / 2, hop) + 1, k1 = -floordiv(-(s1 + N / 2), hop) - 1;
+                if (chunks.empty() || (int64_t)(fr.size() - chunks.back().rec0) + (k1 - k0 + 1) > budget)
+                    chunks.push_back(Chunk{sg.size(), 0, fr.size(), 0, 0});
+                Chunk& ck = chunks.back();
+                sg.push_back(SepSeg{g.frame_begin, g.frame_end, s0, s1, k0, (int64_t)(fr.size() - ck.rec0), ck.total});
+                for (int64_t k = k0; k <= k1; ++k) {
+                    int64_t j0, j1; double al;
+                    frame_bins(k, hop, sr, pl.n_bins, j0, j1, al);
+                    fr.push_back(SepFrame{k, (int32_t)(cbase[r] + (j0 - g.bin_first)), (int32_t)(cbase[r] + (j1 - g.bin_first)), (float)al, 0});
+                }
+                ck.nseg++; ck.nrec = fr.size() - ck.rec0; ck.total += s1 - s0;
+            }
+        }
+        if ((rc = ensure(c, &st.d_frames, &st.frames_cap, fr.size()))) return rc;
+        if ((rc = ensure(c, &st.d_segs, &st.segs_cap, sg.size()))) return rc;
+        size_t max_rec = 0;
+        for (const Chunk& ck : chunks) max_rec = std::max(max_rec, ck.nrec);
+        if ((rc = ensure(c, &st.d_fout, &st.fout_cap, max_rec * npairs * N))) return rc;
+        HIPCHK(c, hipMemcpyAsync(st.d_frames, fr.data(), fr.size() * sizeof(SepFrame), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.d_segs, sg.data(), sg.size() * sizeof(SepSeg), hipMemcpyHostToDevice, c->stream));
+        const float gain_hi = prm.above_fmax == SS_ABOVE_FMAX_KEEP ? 1.0f : (float)prm.min_gain;
+        const int64_t F = (int64_t)std::nearbyint(prm.fade_s * sr);
+        const std::string stft_name = "sep_stft_kernel<" + std::to_string(N) + ">";
+        for (const Chunk& ck : chunks) {
+            {
+                const double lg = std::log2((double)N);
+                ScopedLaunch sl(c, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
+                                (double)ck.nrec * npairs * N * (2.0 * pcm_bytes_per_sample(format) + 8.0));
+                HIPCHK(c, launch_sep_stft_n(N, c->d_pcm, format, ch, frames, st.d_frames + ck.rec0, (int)ck.nrec, hop, st.d_gain, *tb, gain_hi,
+                                            st.d_fout, c->stream));
+            }
+            const int64_t all = ck.total * ch;
+            ScopedLaunch sl(c, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
+            const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
+            hipLaunchKernelGGL(sep_blend_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch, st.d_segs + ck.seg0,
+                               (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_sil_out);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // fr / sg and the caller's buffers are free again
+    return SS_OK;
+}
+
+}  // namespace ss

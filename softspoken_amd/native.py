@@ -55,6 +55,23 @@ class StreamInfo(C.Structure):
                 ("final_until_s", C.c_double), ("closed", C.c_int32), ("finished", C.c_int32), ("state_bytes", C.c_int64)]
 
 
+class SeparationParams(C.Structure):
+    _fields_ = [("fade_s", C.c_double), ("min_gain", C.c_double), ("above_fmax", C.c_int32), ("speech_channel", C.c_int32)]
+
+
+class SeparationRange(C.Structure):
+    _fields_ = [("frame_begin", C.c_int64), ("frame_end", C.c_int64), ("stft_first", C.c_int64), ("stft_last", C.c_int64),
+                ("bin_first", C.c_int64), ("bin_last", C.c_int64), ("win_first", C.c_int64), ("win_last", C.c_int64)]
+
+
+class SeparationPlanInfo(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_windows", C.c_int64), ("n_bins", C.c_int64), ("windows_run", C.c_int64),
+                ("n_ranges", C.c_int64), ("cap_ranges", C.c_int64), ("ranges", C.POINTER(SeparationRange))]
+
+
+ABOVE_FMAX = {"mute": 0, "keep": 1}      # SS_ABOVE_FMAX_MUTE / _KEEP
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
 
 # every symbol include/softspoken.h declares: (restype, argtypes)
@@ -119,6 +136,9 @@ _SIGS = {
     "ss_stream_free": (C.c_int, [_P, C.c_int]),
     "ss_stream_export": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_stream_import": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
+    "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
+    "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
+    "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
 }
 EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
@@ -210,6 +230,33 @@ def wav_header_pcm16(sr: int, channels: int, frames: int) -> bytes:
     return buf.raw
 
 
+def _regions(regions):
+    arr = (Region * max(1, len(regions)))()
+    for i, (s, e) in enumerate(regions):
+        arr[i].start, arr[i].end = float(s), float(e)
+    return arr
+
+
+def separation_params(fade_s: float = 0.01, min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> SeparationParams:
+    """struct ss_separation_params; above_fmax: "mute" / "keep" (or the SS_ABOVE_FMAX_* code itself: unknown codes reach the library)."""
+    code = ABOVE_FMAX[above_fmax] if isinstance(above_fmax, str) else int(above_fmax)
+    return SeparationParams(float(fade_s), float(min_gain), code, int(speech_channel))
+
+
+def separation_plan(sr: int, frames: int, regions, **params) -> dict:
+    """ss_separation_plan (host only): n_fft, hop, n_windows, n_bins, windows_run and the merged ranges as a list of dicts."""
+    arr = _regions(regions)
+    p = separation_params(**params)
+    cap = max(1, len(regions))
+    rng = (SeparationRange * cap)()
+    info = SeparationPlanInfo()
+    info.cap_ranges, info.ranges = cap, C.cast(rng, C.POINTER(SeparationRange))
+    _check(lib().ss_separation_plan(int(sr), int(frames), arr, len(regions), C.byref(p), C.byref(info)))
+    out = {k: int(getattr(info, k)) for k in ("n_fft", "hop", "n_windows", "n_bins", "windows_run")}
+    out["ranges"] = [{f: int(getattr(rng[i], f)) for f, _ in SeparationRange._fields_} for i in range(info.n_ranges)]
+    return out
+
+
 # ---- context --------------------------------------------------------------------------------------
 class Context:
     """One detector context on one GPU (not thread-safe; one per device)."""
@@ -289,6 +336,24 @@ class Context:
             arr[i].start, arr[i].end = float(s), float(e)
         out = np.empty((frames, channels), dtype=np.int16)
         self._ck(lib().ss_silence_pcm(self._h, _ptr(pcm), fmt, sr, channels, frames, arr, len(regions), _ptr(out)))
+        return out
+
+    def separate_pcm(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int, regions, fade_s: float = 0.01,
+                     min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> np.ndarray:
+        """The separation silencer (ss_separate_pcm): interleaved int16 (frames, channels), the speech part of the spectrum removed
+        inside the (start_s, end_s) regions, the rest as silence_pcm writes it.  Resets the context (ss_reset + ss_add_pcm)."""
+        pcm = np.ascontiguousarray(pcm)
+        self._need_bytes(pcm, fmt, channels, frames)
+        p = separation_params(fade_s, min_gain, above_fmax, speech_channel)
+        out = np.empty((frames, channels), dtype=np.int16)
+        self._ck(lib().ss_separate_pcm(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions), C.byref(p),
+                                       _ptr(out)))
+        return out
+
+    def separation_maps(self, fid: int, first_bin: int, n_bins: int) -> np.ndarray:
+        """Averaged spec-head maps of bins [first_bin, first_bin + n_bins) of file fid: float32 [2, n_bins, 128]."""
+        out = np.empty((2, int(n_bins), 128), dtype=np.float32)
+        self._ck(lib().ss_separation_maps(self._h, int(fid), int(first_bin), int(n_bins), _ptr(out)))
         return out
 
     def stft512_magnitude(self, samples) -> np.ndarray:

@@ -4,6 +4,10 @@ erase == 1 is rewritten as `<name>_silenced.wav` with those intervals zeroed.
 
 The samples go through `ss_silence_pcm` (decode, zero, 16-bit encode in one device pass); this module
 only groups the rows, maps the file and writes header + samples.
+
+method="separate" keeps the environmental sound of the erased intervals: `ss_separate_pcm` removes only the speech part of
+their spectrum, with the gains of the model's spec head (SpecUNet_2D's spec_output_conv, "env / speech separation"; the
+reference computes it and drops it).  Everything outside the intervals is what method="zero" writes.
 """
 from __future__ import annotations
 
@@ -16,10 +20,23 @@ from . import native
 class SilenceJob:
     """Signals of the reference's worker (silencer_ui.py:908-916) as plain callbacks; `stop()` as there."""
 
+    METHODS = ("zero", "separate")
+
     def __init__(self, review_df, output_dir, ctx=None, file_started=None, file_complete=None,
-                 overall_progress=None, finished=None):
+                 overall_progress=None, finished=None, method="zero", model=None, fade_s=0.01, min_gain=0.0,
+                 above_fmax="mute", speech_channel=1):
+        """method "zero": the reference's silencer (ctx: any context, default the shared audio context).  method "separate":
+        ss_separate_pcm through `model` (a SpecUNet_2D, e.g. NNDetector(...).model) and its with_range_fallback, so that an input
+        the f16x2 mode cannot represent runs in fp32; fade_s, min_gain, above_fmax ("mute" / "keep") and speech_channel are its
+        parameters (include/softspoken.h).  The model's device context must not be in use by another thread meanwhile."""
+        if method not in self.METHODS:
+            raise ValueError(f"method must be one of {self.METHODS}, not {method!r}")
+        if method == "separate" and model is None:
+            raise ValueError('method="separate" needs the model (a SpecUNet_2D) whose spec head gives the gains')
         self.review_df, self.output_dir = review_df, output_dir
         self.ctx = ctx
+        self.method, self.model = method, model
+        self.sep_params = dict(fade_s=fade_s, min_gain=min_gain, above_fmax=above_fmax, speech_channel=speech_channel)
         self.file_started, self.file_complete = file_started, file_complete
         self.overall_progress, self.finished = overall_progress, finished
         self.stop_requested = False
@@ -38,7 +55,7 @@ class SilenceJob:
         if erase.empty:
             self._emit(self.finished)
             return self.outputs
-        ctx = self.ctx or voice_activity.audio_context()
+        ctx = (self.ctx or voice_activity.audio_context()) if self.method == "zero" else None
         groups = erase.groupby(['file_path', 'file_name'])
         total, done = len(groups), 0
         for (fpath, fname), rows in groups:
@@ -52,8 +69,13 @@ class SilenceJob:
                 info = native.wav_parse(buf)
                 pcm = buf[info.data_offset: info.data_offset + info.data_bytes]
                 regions = [(float(s), float(e)) for s, e in zip(rows['start_time'], rows['end_time'])]
-                with voice_activity._audio_lock:
-                    out = ctx.silence_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames, regions)
+                if self.method == "zero":
+                    with voice_activity._audio_lock:
+                        out = ctx.silence_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames, regions)
+                else:
+                    out = self.model.with_range_fallback(
+                        lambda c: c.separate_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames, regions,
+                                                 **self.sep_params), key=("separate", src))
                 with open(out_path, "wb") as fh:
                     fh.write(native.wav_header_pcm16(info.sample_rate, info.channels, info.frames))
                     fh.write(out.tobytes())
@@ -68,6 +90,8 @@ class SilenceJob:
         return self.outputs
 
 
-def silence_files(review_df, output_dir, ctx=None):
+def silence_files(review_df, output_dir, ctx=None, method="zero", model=None, fade_s=0.01, min_gain=0.0, above_fmax="mute",
+                  speech_channel=1):
     """-> list of written paths."""
-    return SilenceJob(review_df, output_dir, ctx=ctx).run()
+    return SilenceJob(review_df, output_dir, ctx=ctx, method=method, model=model, fade_s=fade_s, min_gain=min_gain,
+                      above_fmax=above_fmax, speech_channel=speech_channel).run()
