@@ -399,6 +399,18 @@ int64_t ss_workspace_bytes(ss_ctx* ctx);
  * error; nth < 0 switches it off.  The context must come out of such a failure without a workspace (and allocate one afresh on
  * the next call), never with dangling tensors. */
 int ss_debug_fail_workspace_alloc(ss_ctx* ctx, int nth);
+/* Activation tensors of the context's last network pass, for per-launch tests.  name: a tensor of the activation workspace ("h1" ... "s9"),
+ * "feat" (the pass's features) or "flat_part" (conv_flatten's row-group partial sums, fp32 [n][groups][4][256] read as H = groups,
+ * W = 4, C = 256; exponents: the common power of two they carry).  Copies windows [first_window, first_window + n_windows) of one plane as stored, [n][H][W][C]: fp32,
+ * bf16, or under SS_FLAG_F16X2 the high (plane 0) or low (plane 1) f16 halves.  shape (if not NULL) receives H, W, C and the bytes of
+ * one element; exponents (if not NULL, C entries) the power-of-two channel exponents of the tensor (the stored value of channel c is
+ * 2^e[c] x its value; all zero outside SS_FLAG_F16X2).  out == NULL: shape and exponents only, for any tensor of the model (no pass
+ * needed).  With out given (n_windows may be 0: the checks alone): SS_ERR_STATE without a workspace, while a run is in flight, after a
+ * pass on the second lane, and for a tensor the last pass did not write; then SS_ERR_ARG for an "r*" tensor (stored in MFMA fragment
+ * order: the pass wrote it, i.e. ran that block as A + r / B), an unknown name, a plane the mode does not have, windows outside the
+ * last pass or a short buffer. */
+int ss_debug_activation(ss_ctx* ctx, const char* name, int plane, int64_t first_window, int64_t n_windows, void* out, int64_t out_bytes,
+                        int32_t* shape, int32_t* exponents);
 #endif
 
 #ifdef __cplusplus

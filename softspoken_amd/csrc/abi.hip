@@ -718,6 +718,10 @@ extern "C" int ss_debug_fail_workspace_alloc(ss_ctx* c, int nth) {
     c->fail_alloc_after = nth < 0 ? -1 : nth;
     return SS_OK;
 }
+extern "C" int ss_debug_activation(ss_ctx* c, const char* name, int plane, int64_t first_window, int64_t n_windows, void* out, int64_t out_bytes,
+                                   int32_t* shape, int32_t* exponents) {
+    return debug_activation(c, name, plane, first_window, n_windows, out, out_bytes, shape, exponents);
+}
 #endif
 
 extern "C" int64_t ss_workspace_bytes(ss_ctx* c) { return c ? c->ws_bytes + c->lane1.bytes : -1; }

@@ -9,6 +9,7 @@
 #include "kernels.h"
 
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -161,6 +162,12 @@ struct ss_ctx {
     int* d_range_flag = nullptr; int* h_range_flag = nullptr;    // f16x2: set by the conv kernels when a value does not fit an f16
     int fail_alloc_after = -1;                            // dev build's test hook (ss_debug_fail_workspace_alloc): the n-th workspace allocation from now fails
     bool split_range_ok = true;                           // f16x2: cleared while packing when a folded weight has no f16 representation
+    // f16x2: power-of-two channel exponents of every activation tensor, by tensor name (weights.hip; all zero in the other modes and under
+    // SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c
+    std::map<std::string, std::vector<int>> act_exp;
+    // the last network pass, for the dev build's ss_debug_activation (kept in both builds: the units shared by the two libraries must see
+    // one layout of this struct): its windows, the tensors it wrote, whether it ran on the second lane's workspace
+    int dbg_n = 0; bool dbg_lane1 = false; std::set<std::string> dbg_written;
 
     // arena
     float* d_arena = nullptr; size_t arena_cap = 0, arena_used = 0;
@@ -242,6 +249,10 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
               const float* ext_logits = nullptr, int64_t ext_windows = 0);
 int run_poll(ss_ctx* c, ss_progress_fn progress, void* user, int block, const volatile int* stop_flag);
 int run_end(ss_ctx* c);
+#ifdef SS_DEVBUILD
+int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int64_t n, void* out, int64_t out_bytes, int32_t* shape,
+                     int32_t* exponents);
+#endif
 void ensure_regions(ss_ctx* c);
 int upload_winoff(ss_ctx* c, const std::vector<int64_t>& off);
 // abi.hip

@@ -82,6 +82,7 @@ void free_workspace(ss_ctx* c) {
     void* arena = c->d_act_arena; float* feat = c->d_feat; float* fp = c->d_flat_part;
     c->d_act_arena = nullptr; c->d_feat = nullptr; c->d_flat_part = nullptr; c->lo_delta = 0;
     c->act.clear();
+    c->dbg_n = 0; c->dbg_lane1 = false; c->dbg_written.clear();
     if (arena) hipFree(arena);
     if (feat) hipFree(feat);
     if (fp) hipFree(fp);
@@ -96,18 +97,20 @@ static hipError_t ws_malloc(ss_ctx* c, void** p, size_t bytes) {
 // one workspace for n windows: arena (+ the tensor table), feature and flatten-partial buffers; the zero headers are written on `stream`.
 // On failure everything it allocated is freed again and *what names the step.
 struct WsAlloc { void* arena = nullptr; float* feat = nullptr; float* flat = nullptr; std::map<std::string, void*> act; int64_t lo_delta = 0, bytes = 0; };
+struct WsTensor { const char* n; int H, W, C; };
+static const WsTensor kWsTensors[] = {{"h1", 128, 256, 32}, {"c1", 128, 256, 32}, {"p1", 64, 128, 32}, {"h2", 64, 128, 64}, {"c2", 64, 128, 64},
+                                      {"p2", 32, 64, 64},   {"h3", 32, 64, 96},   {"c3", 32, 64, 96},  {"p3", 16, 32, 96},  {"h4", 16, 32, 128},
+                                      {"c4", 16, 32, 128},  {"p4", 8, 16, 128},   {"hb", 8, 16, 128},  {"bott", 8, 16, 128}, {"he", 8, 16, 128},
+                                      {"enc", 8, 16, 128},  {"h6", 16, 32, 96},   {"c6", 16, 32, 96},  {"h7", 32, 64, 64},  {"c7", 32, 64, 64},
+                                      {"h8", 64, 128, 32},  {"c8", 64, 128, 32},  {"h9", 128, 256, 32}, {"c9", 128, 256, 32},
+                                      {"hs", 128, 256, 32}, {"s9", 128, 256, 32},
+                                      // r = residual projection written by A launches that keep it (conv6, conv8, the spec head; every block in fp32 / f16x2)
+                                      {"r2", 64, 128, 64},  {"r3", 32, 64, 96},   {"r4", 16, 32, 128}, {"rb", 8, 16, 128},  {"re", 8, 16, 128},
+                                      {"r6", 16, 32, 96},   {"r7", 32, 64, 64},   {"r8", 64, 128, 32}, {"r9", 128, 256, 32}, {"rs", 128, 256, 32}};
 static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, WsAlloc& w, std::string& what) {
     const size_t es = c->prec == kFp32 ? 4 : 2;
-    struct T { const char* n; int H, W, C; };
-    const T ts[] = {{"h1", 128, 256, 32}, {"c1", 128, 256, 32}, {"p1", 64, 128, 32}, {"h2", 64, 128, 64}, {"c2", 64, 128, 64},
-                    {"p2", 32, 64, 64},   {"h3", 32, 64, 96},   {"c3", 32, 64, 96},  {"p3", 16, 32, 96},  {"h4", 16, 32, 128},
-                    {"c4", 16, 32, 128},  {"p4", 8, 16, 128},   {"hb", 8, 16, 128},  {"bott", 8, 16, 128}, {"he", 8, 16, 128},
-                    {"enc", 8, 16, 128},  {"h6", 16, 32, 96},   {"c6", 16, 32, 96},  {"h7", 32, 64, 64},  {"c7", 32, 64, 64},
-                    {"h8", 64, 128, 32},  {"c8", 64, 128, 32},  {"h9", 128, 256, 32}, {"c9", 128, 256, 32},
-                    {"hs", 128, 256, 32}, {"s9", 128, 256, 32},
-                    // r = residual projection written by A launches that keep it (conv6, conv8, the spec head; every block in fp32 / f16x2)
-                    {"r2", 64, 128, 64},  {"r3", 32, 64, 96},   {"r4", 16, 32, 128}, {"rb", 8, 16, 128},  {"re", 8, 16, 128},
-                    {"r6", 16, 32, 96},   {"r7", 32, 64, 64},   {"r8", 64, 128, 32}, {"r9", 128, 256, 32}, {"rs", 128, 256, 32}};
+    using T = WsTensor;
+    const auto& ts = kWsTensors;
     // one arena, one size (the spec head's tensors included): the workspace is sized once per context and chunk
     size_t total = 0;
     std::vector<size_t> offs;
@@ -204,11 +207,24 @@ struct StageStamps {
 };
 #endif
 
+// the tensors a pass writes, by name (dev build: ss_debug_activation refuses the others)
+static void mark_written(ss_ctx* c, const void* p) {
+#ifdef SS_DEVBUILD
+    if (!p) return;
+    for (const auto& kv : c->act)
+        if (kv.second == p) { c->dbg_written.insert(kv.first); return; }
+#else
+    (void)c; (void)p;
+#endif
+}
+
 // One launch of a ResBlock half.  A launches (r_out) compute h and the residual projection r from the block input
 // (x0 [+ upsampled x1]); B launches (r_in) compute the block output from h and add r.
 static int run_conv2(ss_ctx* c, const ConvPlan& p, int n, const void* x0, const void* x1, void* out, void* pool, void* r_out,
                      const void* r_in, const float* feat, const ConvExtra& ex = ConvExtra()) {
     const bool isA = r_out != nullptr;
+    if (ex.store_out) mark_written(c, out);
+    mark_written(c, pool); mark_written(c, r_out);
     ConvArgs a{};
     a.first_w = ex.first_w; a.first_b = ex.first_b; a.flat_w = ex.flat_w; a.flat_w4 = ex.flat_w4; a.flat_part = ex.flat_part; a.store_out = ex.store_out;
     a.src0 = x0; a.src1 = x1; a.wpk = p.d_w2; a.bias = p.d_bias2;
@@ -321,6 +337,8 @@ static int run_block_proj(ss_ctx* c, const ConvPlan& pa, const ConvPlan& pb, int
     au.wpk = pa.d_w_ups;
     const bool ups = c->prec == kF16x2 && pa.d_w_ups && x1 && conv_ups_supports(au, c->num_cus);
     if ((!ups && !conv_v4_supports(a, pa.NT, c->num_cus, prec4)) || !conv_v4_supports(b, pb.NT, c->num_cus, prec4)) return 1;
+    mark_written(c, h); mark_written(c, pool);
+    if (ex.store_out) mark_written(c, out);
     const double px = (double)n * pa.H * pa.W, cin = pa.C0 + pa.C1, cinb = pa.C0 + pa.C1 / 4.0;
     if (ups) {
         // FLOPs booked are the layer's algorithmic ones (2 x multiply-adds of the 3x3 as the reference computes it); this
@@ -360,8 +378,24 @@ static int run_block_proj(ss_ctx* c, const ConvPlan& pa, const ConvPlan& pb, int
     return SS_OK;
 }
 
+static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out);
+
 // SpecUNet_2D.forward (pytorch_neural_nets.py:142-197) for n <= ws_chunk windows whose arena offsets are d_winoff[0..n)
 int forward_chunk(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out) {
+#ifdef SS_DEVBUILD
+    // the pass's record for ss_debug_activation: on the second lane the context's tensor table is the lane's (engine.hip run_begin)
+    c->dbg_written.clear(); c->dbg_n = n;
+    c->dbg_lane1 = c->act.empty() || c->act.at("h1") != (char*)c->d_act_arena + kActHeader;
+    if (!d_feat_out) c->dbg_written.insert("feat");
+    const int rc = forward_chunk_(c, d_winoff, n, d_logits, d_spec, d_feat_out);
+    if (rc) { c->dbg_written.clear(); c->dbg_n = 0; }
+    return rc;
+#else
+    return forward_chunk_(c, d_winoff, n, d_logits, d_spec, d_feat_out);
+#endif
+}
+
+static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out) {
     FrontendTables tb{c->d_pretw, c->d_w2048, c->d_mel_start, c->d_mel_count, c->d_mel_off, c->d_mel_w, c->mel_nw, c->d_mel_wp, dev_env("SOFTSPOKEN_FEDBG", 0),
                       c->d_win2, c->d_twt, c->d_wkt, c->d_mel_wq, c->d_mel_p0};
     float* feat = d_feat_out ? d_feat_out : c->d_feat;
@@ -413,6 +447,9 @@ int forward_chunk(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, fl
         }
         i += 2;
     }
+#ifdef SS_DEVBUILD
+    c->dbg_written.insert("flat_part");
+#endif
     if (d_spec) {   // dead head of the reference (worker.py:78-79 drops it), on request
         RC2(run_conv2(c, cv[i], n, A("c9"), nullptr, A("hs"), nullptr, A("rs"), nullptr, nullptr));
         RC2(run_conv2(c, cv[i + 1], n, A("hs"), nullptr, A("s9"), nullptr, nullptr, A("rs"), nullptr));
@@ -425,6 +462,54 @@ int forward_chunk(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, fl
     HIPCHK(c, launch_mask_head_parts(c->d_flat_part, groups, c->d_flat_b, c->head, d_logits, n, c->stream));
     return SS_OK;
 }
+
+#ifdef SS_DEVBUILD
+// ss_debug_activation: one plane of a tensor of the last pass, [n][H][W][C] as stored, and its channel exponents
+int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int64_t n, void* out, int64_t out_bytes, int32_t* shape,
+                     int32_t* exponents) {
+    if (!c || !name) return fail(c, SS_ERR_ARG, "ss_debug_activation: null argument");
+    const std::string k = name;
+    int H = 128, W = 256, C = 1, es = 4;
+    const void* base = nullptr;
+    if (k == "feat") {
+        base = c->d_feat;
+    } else if (k == "flat_part") {                        // conv_flatten's row-group partial sums [n][groups][4][256] (heads.hip)
+        base = c->d_flat_part; H = std::max(c->flat_groups, 1); W = 4; C = 256;
+    } else {
+        const WsTensor* t = nullptr;
+        for (const WsTensor& e : kWsTensors) if (k == e.n) t = &e;
+        if (!t) return fail(c, SS_ERR_ARG, "ss_debug_activation: no tensor named '" + k + "'");
+        H = t->H; W = t->W; C = t->C; es = c->prec == kFp32 ? 4 : 2;
+    }
+    if (shape) { shape[0] = H; shape[1] = W; shape[2] = C; shape[3] = es; }
+    if (exponents) {
+        const auto it = c->act_exp.find(k);
+        for (int i = 0; i < C; ++i) exponents[i] = it != c->act_exp.end() && i < (int)it->second.size() ? it->second[i] : 0;
+    }
+    if (!out) return SS_OK;                               // (shape and exponents are the model's: no pass needed)
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "ss_debug_activation: a run is in flight");
+    if (!c->ws_chunk || c->act.empty()) return fail(c, SS_ERR_STATE, "ss_debug_activation: the context has no workspace");
+    if (c->dbg_lane1) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass ran on the second lane's workspace");
+    if (!c->dbg_written.count(k)) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass did not write " + k);
+    // (after the staleness test: SS_ERR_ARG for an r tensor tells the caller that the pass ran the block as A + r / B)
+    if (k[0] == 'r') return fail(c, SS_ERR_ARG, "ss_debug_activation: " + k + " is stored in MFMA fragment order; check it through its B launch");
+    if (k != "feat" && k != "flat_part") base = c->act.at(k);
+    const bool two = k != "feat" && k != "flat_part" && c->prec == kF16x2;
+    if (plane < 0 || plane > (two ? 1 : 0)) return fail(c, SS_ERR_ARG, "ss_debug_activation: no plane " + std::to_string(plane) + " in " + k);
+    if (first < 0 || n < 0 || first + n > c->dbg_n)
+        return fail(c, SS_ERR_ARG, "ss_debug_activation: windows [" + std::to_string(first) + ", " + std::to_string(first + n) + ") are outside the last pass (" +
+                                   std::to_string(c->dbg_n) + " windows)");
+    const int64_t per = (int64_t)H * W * C * es, need = n * per;
+    if (out_bytes < need) return fail(c, SS_ERR_ARG, "ss_debug_activation: output buffer too small");
+    if (need) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const char* src = (const char*)base + (plane ? c->lo_delta : 0) + first * per;
+        HIPCHK(c, hipMemcpy(out, src, (size_t)need, hipMemcpyDeviceToHost));
+    }
+    return SS_OK;
+}
+#endif
 
 int upload_winoff(ss_ctx* c, const std::vector<int64_t>& off) {
     int rc = ensure(c, &c->d_winoff, &c->winoff_cap, off.size());

@@ -495,8 +495,9 @@ static int pick_nt(int cout, int H) { return H <= 8 ? 1 : (cout == 96 ? 3 : (cou
 
 // One ResBlock (pytorch_neural_nets.py:7-41) -> launch A (conv1+BN+ReLU) and launch B (conv2+BN + residual+BN, add, ReLU).
 // s_in: exponents of the block input's channels (cat[x0, x1]); s_out receives the block output's (all zero unless f16x2)
+// s_hid receives the exponents of the block's hidden tensor h (the A launch's output)
 static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, int cin0, int cin1, int cout, int H, int W,
-                          const std::vector<int>& s_in, std::vector<int>& s_out) {
+                          const std::vector<int>& s_in, std::vector<int>& s_out, std::vector<int>& s_hid) {
     std::string err;
     const int cin = cin0 + cin1;
     Folded f1, f2, fr;
@@ -504,8 +505,9 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
     if (!fold_conv_bn(bl, name + ".conv2.0", name + ".conv2.1", cout, cout, 9, f2, err)) return fail(c, SS_ERR_FORMAT, err);
     if (!fold_conv_bn(bl, name + ".residual.0", name + ".residual.1", cout, cin, 1, fr, err)) return fail(c, SS_ERR_FORMAT, err);
     s_out.assign(cout, 0);
+    s_hid.assign(cout, 0);
     if (c->prec == kF16x2 && dev_env("SOFTSPOKEN_NORM", 1)) {      // power-of-two channel normalisation (above)
-        std::vector<int> s_h(cout, 0);
+        std::vector<int>& s_h = s_hid;
         for (int co = 0; co < cout; ++co) s_h[co] = norm_exponent(row_sumsq(f1, co, s_in), f1.b[co]);
         for (int co = 0; co < cout; ++co) s_out[co] = norm_exponent(row_sumsq(f2, co, s_h) + row_sumsq(fr, co, s_in), (double)f2.b[co] + (double)fr.b[co]);
         scale_folded(f1, s_h, s_in);
@@ -641,21 +643,32 @@ int build_model(ss_ctx* c, const Blob& bl) {
     // launch order == pytorch_neural_nets.py:156-181
     // x0 / x1: the blocks whose outputs are concatenated into this block's input (pytorch_neural_nets.py:171-180: [skip, upsampled]);
     // their channel exponents (f16x2 normalisation) travel with them
-    struct RB { const char* n; int c0, c1, co, H, W; const char *x0, *x1; };
-    const RB rbs[] = {{"conv1_1", 1, 0, 32, 128, 256, nullptr, nullptr},  {"conv2_1", 32, 0, 64, 64, 128, "conv1_1", nullptr},
-                      {"conv3_1", 64, 0, 96, 32, 64, "conv2_1", nullptr}, {"conv4_1", 96, 0, 128, 16, 32, "conv3_1", nullptr},
-                      {"conv_bottleneck", 128, 0, 128, 8, 16, "conv4_1", nullptr}, {"encoder_out", 128, 0, 128, 8, 16, "conv_bottleneck", nullptr},
-                      {"conv6", 128, 128, 96, 16, 32, "conv4_1", "encoder_out"},  {"conv7", 96, 96, 64, 32, 64, "conv3_1", "conv6"},
-                      {"conv8", 64, 64, 32, 64, 128, "conv2_1", "conv7"},         {"conv9_1", 32, 32, 32, 128, 256, "conv1_1", "conv8"},
-                      {"spec_output_conv.0", 32, 0, 32, 128, 256, "conv9_1", nullptr}};
+    // (h, y, pool: the block's tensors in the activation workspace, engine.hip alloc_ws)
+    struct RB { const char* n; int c0, c1, co, H, W; const char *x0, *x1, *h, *y, *pool; };
+    const RB rbs[] = {{"conv1_1", 1, 0, 32, 128, 256, nullptr, nullptr, "h1", "c1", "p1"},
+                      {"conv2_1", 32, 0, 64, 64, 128, "conv1_1", nullptr, "h2", "c2", "p2"},
+                      {"conv3_1", 64, 0, 96, 32, 64, "conv2_1", nullptr, "h3", "c3", "p3"},
+                      {"conv4_1", 96, 0, 128, 16, 32, "conv3_1", nullptr, "h4", "c4", "p4"},
+                      {"conv_bottleneck", 128, 0, 128, 8, 16, "conv4_1", nullptr, "hb", "bott", nullptr},
+                      {"encoder_out", 128, 0, 128, 8, 16, "conv_bottleneck", nullptr, "he", "enc", nullptr},
+                      {"conv6", 128, 128, 96, 16, 32, "conv4_1", "encoder_out", "h6", "c6", nullptr},
+                      {"conv7", 96, 96, 64, 32, 64, "conv3_1", "conv6", "h7", "c7", nullptr},
+                      {"conv8", 64, 64, 32, 64, 128, "conv2_1", "conv7", "h8", "c8", nullptr},
+                      {"conv9_1", 32, 32, 32, 128, 256, "conv1_1", "conv8", "h9", "c9", nullptr},
+                      {"spec_output_conv.0", 32, 0, 32, 128, 256, "conv9_1", nullptr, "hs", "s9", nullptr}};
     std::map<std::string, std::vector<int>> sc;           // block name -> exponents of its output channels
+    c->act_exp.clear();
     for (const RB& r : rbs) {
-        std::vector<int> s_in;
+        std::vector<int> s_in, s_hid;
         if (r.x0) s_in = sc[r.x0]; else s_in.assign(r.c0, 0);          // (conv1_1: the features, as they are)
         if (r.x1) s_in.insert(s_in.end(), sc[r.x1].begin(), sc[r.x1].end());
         if ((int)s_in.size() != r.c0 + r.c1) return fail(c, SS_ERR_STATE, "build_model: channel bookkeeping");
-        if ((rc = build_resblock(c, bl, r.n, r.c0, r.c1, r.co, r.H, r.W, s_in, sc[r.n]))) return rc;
+        if ((rc = build_resblock(c, bl, r.n, r.c0, r.c1, r.co, r.H, r.W, s_in, sc[r.n], s_hid))) return rc;
+        c->act_exp[r.h] = s_hid;
+        c->act_exp[r.y] = sc[r.n];
+        if (r.pool) c->act_exp[r.pool] = sc[r.n];
     }
+    c->act_exp["feat"] = std::vector<int>(1, 0);
     std::string err;
     // conv_flatten (pytorch_neural_nets.py:133): weight (4, 32, 128, 1) -> [h][ci][c]
     const float* wf0 = bl.f32("conv_flatten.weight", 4 * 32 * 128, err);
@@ -671,6 +684,7 @@ int build_model(ss_ctx* c, const Blob& bl) {
     for (int co = 0; co < 4; ++co) for (int ci = 0; ci < 32; ++ci) for (int h = 0; h < 128; ++h)
         wfs[((size_t)co * 32 + ci) * 128 + h] = std::ldexp(wfs[((size_t)co * 32 + ci) * 128 + h], s_common - s9[ci]);
     c->head.fscale = std::ldexp(1.0f, -s_common);
+    c->act_exp["flat_part"] = std::vector<int>(256, s_common);          // (the partial sums carry 2^s_common)
     const float* wf = wfs.data();
     {   // fused flatten (conv2.hip FLAT): per mel row PAIR a 32 -> 8 (padded to 32) 1x1 "conv" in MFMA fragment order -- columns 0..3 are
         // the four flatten channels with the weights of row 2 p, columns 4..7 the same with those of row 2 p + 1: one product per pair of

@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOFTSPOKEN_LIB") or os.path.join(_HERE, "libsoftspoken_hip.so")
 
 SS_OK = 0
+SS_ERR_ARG = 1
+SS_ERR_STATE = 4
 SS_ERR_STOPPED = 5
 SS_ERR_NOMEM = 6
 SS_ERR_CAPACITY = 7
@@ -144,6 +146,7 @@ EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
 _DEV_SIGS = {
     "ss_debug_fail_workspace_alloc": (C.c_int, [_P, C.c_int]),
+    "ss_debug_activation": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 
 _lib = None
@@ -497,6 +500,34 @@ class Context:
     def debug_fail_workspace_alloc(self, nth: int):
         """Development build only (SOFTSPOKEN_LIB=libsoftspoken_hip_dev.so)."""
         self._ck(lib().ss_debug_fail_workspace_alloc(self._h, int(nth)))
+
+    def debug_activation(self, name: str, first: int, n: int) -> dict:
+        """Development build only: tensor `name` ("h1" ... "s9", "feat", "flat_part") of the last network pass, windows [first, first + n)
+        of that pass.  -> dict(planes=[raw stored planes, [n][H][W][C]: fp32 / bf16 as uint16 / f16 high, f16 low],
+        value=float64 [n][H][W][C] in normalised units (the stored planes decoded; f16x2: high + low), exponents=int32 [C]: the
+        value of channel c is 2^-exponents[c] x the normalised one)."""
+        L = lib()
+        shape = np.zeros(4, dtype=np.int32)
+        key = name.encode()
+        self._ck(L.ss_debug_activation(self._h, key, 0, 0, 0, None, 0, _ptr(shape), None))
+        H, W, Ch, es = (int(v) for v in shape)
+        exps = np.zeros(Ch, dtype=np.int32)
+        self._ck(L.ss_debug_activation(self._h, key, 0, 0, 0, None, 0, None, _ptr(exps)))
+        dt = {4: np.float32, 2: np.uint16}[es]
+        two = name not in ("feat", "flat_part") and self.precision == "f16x2"
+        planes = []
+        for plane in range(2 if two else 1):
+            a = np.empty((n, H, W, Ch), dtype=dt)
+            if n:                                         # (n == 0: the model's shape and exponents, no pass needed)
+                self._ck(L.ss_debug_activation(self._h, key, plane, first, n, _ptr(a), a.nbytes, None, None))
+            planes.append(a)
+        if two:
+            value = planes[0].view(np.float16).astype(np.float64) + planes[1].view(np.float16).astype(np.float64)
+        elif es == 2:
+            value = (planes[0].astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+        else:
+            value = planes[0].astype(np.float64)
+        return dict(planes=planes, value=value, exponents=exps)
 
     def workspace_bytes(self) -> int:
         return int(lib().ss_workspace_bytes(self._h))
