@@ -134,6 +134,12 @@ int64_t ss_plan_windows(double duration_s, int64_t* starts, int64_t cap);
  * minus 3.  *n_out receives the number found; SS_ERR_CAPACITY if it exceeds cap. */
 int ss_find_regions(const double* avg, const int64_t* bin_idx, int64_t n, double threshold, double break_s,
                     ss_region* out, int64_t cap, int64_t* n_out);
+/* The merged table of a recording whose channels were run alone ("speech on any channel"): avg holds n_channels series of n bins
+ * each, channel after channel, over the same bin_idx.  A bin is above when any channel's value is > threshold (a NaN is not above and
+ * does not hide the other channels); everything else is ss_find_regions -- the result is ss_find_regions on the element-wise,
+ * NaN-ignoring maximum (fmax) of the channels, and n_channels == 1 is ss_find_regions itself.  SS_ERR_ARG for n_channels < 1. */
+int ss_find_regions_union(const double* avg, const int64_t* bin_idx, int64_t n, int n_channels, double threshold, double break_s,
+                          ss_region* out, int64_t cap, int64_t* n_out);
 /* CSV body lines (no header) for `n` regions of one file, first ID = first_id, DataFrame.to_csv text.
  * Returns bytes needed (excluding NUL); writes at most cap bytes. */
 int64_t ss_format_csv_rows(const char* file_path, const char* file_name, const ss_region* regions, int64_t n,
@@ -161,6 +167,19 @@ int ss_add_pcm_device(ss_ctx* ctx, const void* pcm_dev, int format, int sample_r
  * the whole batch in two launches.  File ids are first_file_id .. first_file_id + n_files - 1. */
 int ss_add_pcm_batch_device(ss_ctx* ctx, const void* pcm_dev, int format, int sample_rate, int channels,
                             const int64_t* frames, int n_files, int* first_file_id);
+/* Per-channel ingest: no mixdown.  A recording of `channels` channels becomes `channels` signals with consecutive file ids
+ * *first_file_id + c, in channel order; signal c is bit for bit what ss_add_pcm stores for the one-channel PCM made of channel c's
+ * samples (same format, rate and frames; same 3 s of padding and header duration).  The interleaved PCM is read once per two channels
+ * by the resampler (once in all for 22 050 Hz input).  Afterwards the signals are ordinary files of the job.  Argument limits of
+ * ss_add_pcm; channels == 1 is ss_add_pcm.  pcm: host memory; pcm_dev: device memory of this GPU, aligned to the size of a sample
+ * (16-bit stereo is read as 32-bit words: 4 bytes, as for ss_add_pcm_device).  On an error the job keeps the files it had. */
+int ss_add_pcm_channels(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, int* first_file_id);
+int ss_add_pcm_channels_device(ss_ctx* ctx, const void* pcm_dev, int format, int sample_rate, int channels, int64_t frames,
+                               int* first_file_id);
+/* `n_files` recordings back to back in one device buffer, as ss_add_pcm_batch_device: recording r, channel c gets file id
+ * *first_file_id + r * channels + c. */
+int ss_add_pcm_channels_batch_device(ss_ctx* ctx, const void* pcm_dev, int format, int sample_rate, int channels,
+                                     const int64_t* frames, int n_files, int* first_file_id);
 /* A signal that already is mono float32 at 22 050 Hz (the parity boundary). Pads 3 s each side. */
 int ss_add_f32_22k(ss_ctx* ctx, const float* samples, int64_t n, int* file_id);
 /* A signal stored as is, no padding added (what worker.py hands to process_batch; also any buffer of
@@ -250,6 +269,16 @@ int ss_get_regions(ss_ctx* ctx, int file_id, ss_region* out, int64_t cap, int64_
 /* The same for files [first_file, first_file + n_files) in one call: counts[i] regions of file first_file + i, back to
  * back in out (either may be NULL; *n_out = total). */
 int ss_get_regions_batch(ss_ctx* ctx, int first_file, int n_files, int64_t* counts, ss_region* out, int64_t cap, int64_t* n_out);
+/* The merged table of files [first_file, first_file + n_channels) of the ended run -- the channels of one recording added with
+ * ss_add_pcm_channels*: ss_find_regions_union of their averages with the run's threshold and break (found from the run's bin masks,
+ * so it is readable as long as ss_get_regions is).  out may be NULL (*n_out = count).  SS_ERR_ARG when the range is not inside the
+ * run or the files differ in their number of bins. */
+int ss_get_regions_union(ss_ctx* ctx, int first_file, int n_channels, ss_region* out, int64_t cap, int64_t* n_out);
+/* Which channel heard a merged region: peaks[r * n_channels + c] = the maximum of channel c's averaged score over the covered bins from
+ * region r's first to its last bin, both included (NaNs passed over; -inf when every one is NaN).  Channel c heard region r when its
+ * peak is > threshold; at least one did.  Computed on the device from the averages: valid as long as ss_get_avg is.  peaks may be
+ * NULL (*n_out = number of merged regions); SS_ERR_CAPACITY when cap_regions is smaller. */
+int ss_get_region_peaks(ss_ctx* ctx, int first_file, int n_channels, double* peaks, int64_t cap_regions, int64_t* n_out);
 
 /* ---- streaming detection: one recording's PCM arriving in pieces, its final regions returned early -----------------------
  * A stream is one recording in one enum ss_pcm_format encoding, rate and channel count (the limits of ss_add_pcm), pushed in pieces

@@ -52,3 +52,7 @@ hip_file_contexts = 2
 # load-time check of the f16x2 mode on the checkpoint actually loaded: a handful of fixed windows through f16x2 and through fp32;
 # beyond 5e-5 the detector logs once and keeps fp32 for those weights (SpecUNet_2D._selfcheck; < 1 s per set of weights)
 hip_selfcheck = True
+# channels of a recording: 'mix' (the reference's behaviour: librosa.to_mono, the mean of the channels, then one detection) or 'each'
+# (every channel detected alone -- a voice that reached one microphone is not halved by the mean --, the file's regions are "speech on
+# any channel"; which channel heard a region goes to <detections stem>_channels.csv).  A mono file gives the same results either way.
+hip_channel_mode = os.environ.get('SOFTSPOKEN_CHANNELS', 'mix')

@@ -47,11 +47,23 @@ def audio_context(device_index: int = 0):
     return _audio_ctx
 
 
-def add_file_to_context(ctx, path):
-    """Upload a WAV file's samples and decode/mixdown/resample/pad them on the device. -> (file_id, WavInfo)"""
+def channel_mode():
+    """settings.hip_channel_mode, checked: 'mix' or 'each'."""
+    mode = getattr(settings, "hip_channel_mode", "mix")
+    if mode not in ('mix', 'each'):
+        raise ValueError(f"settings.hip_channel_mode (SOFTSPOKEN_CHANNELS) must be 'mix' or 'each', not {mode!r}")
+    return mode
+
+
+def add_file_to_context(ctx, path, mode=None):
+    """Upload a WAV file's samples and decode/mixdown/resample/pad them on the device. -> (file_id, WavInfo)
+    mode (default settings.hip_channel_mode) 'each': no mixdown, the file's info.channels channels become the files file_id,
+    file_id + 1, ... of the context."""
     buf = _map_file(path)
     info = _native.wav_parse(buf)
     pcm = buf[info.data_offset: info.data_offset + info.data_bytes]
+    if (mode or channel_mode()) == 'each' and info.channels > 1:
+        return ctx.add_pcm_channels(pcm, info.format, info.sample_rate, info.channels, info.frames), info
     return ctx.add_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames), info
 
 
@@ -67,7 +79,7 @@ def load_audio(directory, start=None):
             ctx = audio_context()
             ctx.reset()
             if start is None:
-                fid, info = add_file_to_context(ctx, directory)
+                fid, info = add_file_to_context(ctx, directory, mode='mix')      # (the reference's mono signal, whatever the detector runs)
             else:
                 buf = _map_file(directory)
                 info = _native.wav_parse(buf)

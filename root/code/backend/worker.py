@@ -16,9 +16,10 @@ is reported through signals.message and skipped (the reference crashes on len(No
 """
 from __future__ import annotations
 
+import csv
 import ctypes
 import logging
-from os.path import basename, dirname
+from os.path import basename, dirname, exists, splitext
 
 import numpy as np
 import pandas as pd
@@ -77,6 +78,7 @@ class ProcessWorker(_Base):
         self.planned_work = planned_work
         self.stop_requested = False
         self._stop_word = ctypes.c_int(0)       # polled by the library between chunks
+        self._channels_file_checked = False     # 'each' mode: the channels file has been cleared of rows beyond the detections CSV
 
     def stop(self):
         self.stop_requested = True
@@ -110,6 +112,39 @@ class ProcessWorker(_Base):
                                   'erase': 0, 'user_comment': '', 'review_datetime': ''}, columns=list(df.columns))
             block.index = range(len(df), len(df) + n)
             self.detection_project.df = pd.concat([df, block.astype(df.dtypes.to_dict())])
+
+    def _append_channel_rows(self, file, first_id, n_regions):
+        """settings.hip_channel_mode == 'each': which channel heard each of the file's regions, appended to <detections stem>_channels.csv
+        beside the detections CSV -- ID (the region's row in the detections CSV), file_name, n_channels, heard (the channels whose peak is
+        above the threshold, like 0;1) and peaks (every channel's highest averaged score inside the region).  Nothing for a detector
+        without channel_detail or a project without a detections file (and run() does not call it in 'mix' mode)."""
+        detail = getattr(self.detector, "channel_detail", None)
+        project = getattr(getattr(self.detection_project, "settings", None), "current_project", None)
+        csv_path = project.get("detections_file") if isinstance(project, dict) else None
+        if not detail or file not in detail or not csv_path:
+            return
+        n_ch, peaks = detail[file]
+        if len(peaks) != n_regions:
+            logging.warning("%s: %d regions but channel detail for %d -- no rows in the channels file", file, n_regions, len(peaks))
+            return
+        side = splitext(csv_path)[0] + "_channels.csv"
+        if not self._channels_file_checked and exists(side):
+            # rows left by a detections CSV that has since been deleted or recreated: their IDs are about to be handed out again
+            with open(side, newline="") as fh:
+                rows = list(csv.reader(fh))
+            kept = [r for r in rows[1:] if r and r[0].isdigit() and int(r[0]) < first_id]
+            if len(kept) != len(rows) - 1:
+                with open(side, "w", newline="") as fh:
+                    csv.writer(fh, lineterminator="\n").writerows(rows[:1] + kept)
+        self._channels_file_checked = True
+        new = not exists(side)
+        with open(side, "a", newline="") as fh:
+            out = csv.writer(fh, lineterminator="\n")
+            if new:
+                out.writerow(["ID", "file_name", "n_channels", "heard", "peaks"])
+            for k, row in enumerate(peaks):
+                heard = ";".join(str(c) for c, v in enumerate(row) if v > settings.threshold)
+                out.writerow([first_id + k, basename(file), n_ch, heard, ";".join("%.6f" % v for v in row)])
 
     def run(self):
         """The reference's signal sequence per file (worker.py:49-139), with the device ahead of the host: files alternate between
@@ -187,8 +222,11 @@ class ProcessWorker(_Base):
                 files_done += 1
                 self.signals.overallProgressChanged.emit((files_done / total_files) * 100.0)
                 continue
+            first_id = self._next_id() if regions and getattr(settings, "hip_channel_mode", "mix") == "each" else None
             self._append_rows(file, regions)
             self.detection_project.save_detections()
+            if first_id is not None:
+                self._append_channel_rows(file, first_id, len(regions))
             self.signals.fileDone.emit(file)
             files_done += 1
             self.signals.overallProgressChanged.emit((files_done / total_files) * 100.0)

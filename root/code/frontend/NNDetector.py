@@ -24,7 +24,7 @@ import torch
 
 from root.code.backend import settings
 from root.code.backend.pytorch_neural_nets import SpecUNet_2D
-from root.code.backend.voice_activity import add_file_to_context, get_audio_data
+from root.code.backend.voice_activity import add_file_to_context, channel_mode, get_audio_data
 from softspoken_amd import native as _native
 
 try:                                   # 64-bit content hash at memory speed when the wheel is there, a 64-bit BLAKE2 from the stdlib otherwise
@@ -65,6 +65,9 @@ class NNDetector():
         self._resident = None     # (key, file_id) of the signal currently in HBM for process_batch
         self._stage = None        # ingest: (context, [device staging buffer, capacity] x 2) for file_prefetch
         self._stage_turn = 0
+        # settings.hip_channel_mode == 'each': file -> (n_channels, [[peak of channel c ...] per region]) for the regions last returned
+        # for that file (each channel's highest averaged score inside the region; a channel heard it when its peak > settings.threshold)
+        self.channel_detail = {}
 
     # -- checkpoint ---------------------------------------------------------------------------------------
     def load_checkpoint(self, model, file_path='checkpoint.pth'):
@@ -203,10 +206,19 @@ class NNDetector():
 
     class _FileToken:
         """A file in flight: its context, file id, and whether the reference's progress values have all been reported."""
-        __slots__ = ("ctx", "fid", "file", "brk", "buf", "which", "reported")
+        __slots__ = ("ctx", "fid", "file", "brk", "buf", "which", "reported", "n_ch")
 
-        def __init__(self, ctx, fid, file, brk, buf, which):
+        def __init__(self, ctx, fid, file, brk, buf, which, n_ch=0):
             self.ctx, self.fid, self.file, self.brk, self.buf, self.which, self.reported = ctx, fid, file, brk, buf, which, False
+            self.n_ch = n_ch              # 'each' mode: the file's channels are the files fid .. fid + n_ch - 1 ('mix': 0)
+
+    def _file_regions(self, ctx, fid, n_ch, file):
+        """The ended run's regions of `file`; 'each' mode (n_ch >= 1): the merged table of its channels, their peaks to channel_detail."""
+        if n_ch < 1:
+            return [(float(s), float(e)) for s, e in ctx.regions(fid)]
+        merged = ctx.regions_union(fid, n_ch) if n_ch > 1 else ctx.regions(fid)
+        self.channel_detail[file] = (n_ch, ctx.region_peaks(fid, n_ch).tolist())
+        return [(float(s), float(e)) for s, e in merged]
 
     def file_begin(self, file, handle=None, break_duration=0.5, which=0, ctx=None):
         """Enqueue everything for `file` -> token for file_poll / file_end.  No other file may be in flight on the same context
@@ -218,9 +230,13 @@ class NNDetector():
         ctx.reset()
         if which == 0:
             self._resident = None
-        fid = ctx.add_pcm_device(dev, info.format, info.sample_rate, info.channels, info.frames)
+        n_ch = info.channels if channel_mode() == 'each' else 0
+        if n_ch > 1:
+            fid = ctx.add_pcm_channels_device(dev, info.format, info.sample_rate, info.channels, info.frames)
+        else:
+            fid = ctx.add_pcm_device(dev, info.format, info.sample_rate, info.channels, info.frames)
         ctx.run_begin(settings.threshold, break_duration, track=True)
-        return self._FileToken(ctx, fid, file, break_duration, _buf, which)     # (_buf: the mapped file stays alive while its samples may still be in flight)
+        return self._FileToken(ctx, fid, file, break_duration, _buf, which, n_ch)     # (_buf: the mapped file stays alive while its samples may still be in flight)
 
     def file_poll(self, token, progress=None, block=True):
         """Report the reference's progress values (worker.py:82-84: done = 32, 64, ..., total windows) that have completed."""
@@ -241,7 +257,7 @@ class NNDetector():
             t2.ctx.run_poll(None if token.reported else progress, True)
             token.reported = True
             t2.ctx.run_end()
-            return [(float(s), float(e)) for s, e in t2.ctx.regions(t2.fid)]
+            return self._file_regions(t2.ctx, t2.fid, t2.n_ch, file)      # (file_begin read the channel mode again: the re-run keeps it)
 
         if not ctx.alive:                     # a switch to fp32 while this file was in flight on the other context closed it
             return again()
@@ -253,7 +269,7 @@ class NNDetector():
             if self.model.range_refused(file, e):
                 return again()
             return again(self.model.fp32_context())
-        return [(float(s), float(e)) for s, e in ctx.regions(fid)]
+        return self._file_regions(ctx, fid, token.n_ch, file)
 
     def file_abort(self, token):
         """Wait for a file in flight and drop its results (stop requested, or its poll / end raised)."""
@@ -270,14 +286,18 @@ class NNDetector():
         def run(ctx):
             ctx.reset()
             self._resident = None
+            each = channel_mode() == 'each'
             ids = []
             for f in files:
-                fid, _ = add_file_to_context(ctx, f)
-                ids.append(fid)
+                fid, info = add_file_to_context(ctx, f)
+                ids.append((fid, info.channels))
             if not ctx.run(settings.threshold, break_duration, progress, stop_flag):
                 return None
             if not ids:
                 return {}
+            if each:                                                   # the channels of a file are consecutive files of the context
+                return {f: self._file_regions(ctx, fid, n_ch, f) for f, (fid, n_ch) in zip(files, ids)}
+            ids = [fid for fid, _ in ids]
             counts, reg = ctx.regions_batch(ids[0], len(ids))          # ids are consecutive after the reset above
             out, at = {}, 0
             for f, n in zip(files, counts.tolist()):

@@ -73,7 +73,7 @@ extern "C" void ss_destroy(ss_ctx* c) {
     for (void* p : c->user_host) hipHostFree(p);
     free_workspace(c);
     for (auto& kv : c->taps) hipFree(kv.second.first);
-    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_batch, c->d_sil_out, c->d_sil_ranges, c->d_sx, c->d_sm};
+    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_batch, c->d_sil_out, c->d_sil_ranges, c->d_sx, c->d_sm, c->d_peaks};
     for (void* p : singles) if (p) hipFree(p);
     for (hipEvent_t ev : c->evpool) hipEventDestroy(ev);
     for (hipEvent_t ev : c->pass_ev) hipEventDestroy(ev);
@@ -375,6 +375,116 @@ extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int forma
     return SS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// per-channel ingest: a recording of `ch` channels -> `ch` signals, consecutive file ids, no mixdown
+// ------------------------------------------------------------------------------------------------------
+extern "C" int ss_add_pcm_channels_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
+                                                int n_files, int* first_file_id) {
+    if (ch == 1) return ss_add_pcm_batch_device(c, pcm_dev, format, sr, ch, frames, n_files, first_file_id);
+    if (!frames || n_files < 1) return fail(c, SS_ERR_ARG, "ss_add_pcm_channels_batch_device: bad argument");
+    int64_t total_frames = 0, max_frames = 0, max_out = 0;
+    for (int i = 0; i < n_files; ++i) {
+        int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames[i]);
+        if (rc) return rc;
+        total_frames += frames[i]; max_frames = std::max(max_frames, frames[i]);
+    }
+    if ((int64_t)n_files * ch >= (int64_t)1 << 24) return fail(c, SS_ERR_ARG, "ss_add_pcm_channels_batch_device: too many signals");
+    hipSetDevice(c->device);
+    if (c->copy_pending) {                                // ingest: the samples may still be crossing PCIe on the copy stream
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
+        c->copy_pending = false;
+    }
+    const size_t bps = pcm_bytes_per_sample(format);
+    int rc;
+    // reserve every arena slot first (the arena may move while it grows); the slots of a recording's channels have one length, so they
+    // lie a constant stride apart
+    const size_t first = c->files.size();
+    const size_t arena_before = (c->arena_used + 3) & ~(size_t)3;
+    struct Rollback {                                     // any error below: the job keeps the files it had, no half-made signals
+        ss_ctx* c; size_t n_files, arena_used; bool done = false;
+        ~Rollback() { if (!done) { c->files.resize(n_files); c->arena_used = arena_used; } }
+    } rollback{c, first, c->arena_used};
+    std::vector<ChanFile> cf(n_files);
+    std::vector<BatchFile> bf;                            // the unfused pair's resampler: one entry per signal
+    int64_t pcm_off = 0, mono_off = 0;
+    double n22sum = 0;
+    for (int i = 0; i < n_files; ++i) {
+        const int64_t n22 = ss_resampled_length(frames[i], sr);
+        ChanFile& d = cf[i];
+        d.pcm_off = pcm_off; d.frames = frames[i]; d.mono_off = mono_off; d.n_out = n22; d.mono_stride = (frames[i] + 3) & ~(int64_t)3;
+        d.out_off = 0; d.out_stride = 0;
+        for (int k = 0; k < ch; ++k) {
+            FileRec fr;
+            fr.duration = (double)frames[i] / (double)sr;
+            if ((rc = arena_slot(c, n22, fr, -1, false))) return rc;
+            c->files.push_back(fr);
+            if (k == 0) d.out_off = fr.off + SS_WINDOW_SAMPLES;
+            else if (k == 1) d.out_stride = fr.off + SS_WINDOW_SAMPLES - d.out_off;
+            else if (fr.off + SS_WINDOW_SAMPLES != d.out_off + k * d.out_stride) return fail(c, SS_ERR_STATE, "ss_add_pcm_channels: arena slots are not evenly spaced");
+            bf.push_back(BatchFile{0, frames[i], d.mono_off + k * d.mono_stride, fr.off + SS_WINDOW_SAMPLES, n22});
+        }
+        pcm_off += frames[i] * ch * (int64_t)bps; mono_off += d.mono_stride * ch;
+        max_out = std::max(max_out, n22); n22sum += (double)n22 * ch;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_arena + arena_before, 0, (c->arena_used - arena_before) * 4, c->stream));
+    const double pcm_bytes = (double)total_frames * ch * bps;
+    int L = 1, M = 1, half = 0; float* d_taps = nullptr;
+    if (sr != SS_SAMPLE_RATE && (rc = get_taps(c, sr, L, M, half, &d_taps))) return rc;
+    const bool fused = sr != SS_SAMPLE_RATE && resample_fused_applies(L, M, half) && dev_env("SOFTSPOKEN_RES3", 1);
+    if (sr == SS_SAMPLE_RATE)
+        for (ChanFile& d : cf) { d.mono_off = d.out_off; d.mono_stride = d.out_stride; }    // decode straight into the arena
+    // descriptors: the recordings' ChanFiles, then (unfused pair) the signals' BatchFiles, in one device buffer counted in BatchFiles
+    static_assert(sizeof(ChanFile) <= 2 * sizeof(BatchFile) && sizeof(BatchFile) % 8 == 0, "descriptor layout");
+    size_t cap = c->batch_cap;
+    if ((rc = ensure(c, &c->d_batch, &cap, (size_t)2 * n_files + bf.size()))) return rc;
+    c->batch_cap = cap;
+    ChanFile* d_cf = (ChanFile*)c->d_batch;
+    BatchFile* d_bf = c->d_batch + (size_t)2 * n_files;
+    HIPCHK(c, hipMemcpyAsync(d_cf, cf.data(), cf.size() * sizeof(ChanFile), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_bf, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // cf / bf are host temporaries
+    if (sr == SS_SAMPLE_RATE) {
+        ScopedLaunch sl(c, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
+        HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_arena, c->stream));
+    } else if (fused) {
+        // decode inside the resampler's LDS staging, the channels taking turns in the tile: one launch, no mono tensor
+        ScopedLaunch sl(c, "resample_fused_channels", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
+        HIPCHK(c, launch_resample_fused_channels(pcm_dev, format, ch, d_cf, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
+    } else {
+        if ((rc = ensure(c, &c->d_mono, &c->mono_cap, (size_t)mono_off + 16))) return rc;
+        {
+            ScopedLaunch sl(c, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
+            HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_mono, c->stream));
+        }
+        ScopedLaunch sl(c, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * ch * total_frames + 4.0 * n22sum);
+        HIPCHK(c, launch_resample_batch(c->d_mono, d_bf, (int)bf.size(), max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
+    }
+    rollback.done = true;
+    if (first_file_id) *first_file_id = (int)first;
+    c->logits_valid = false;
+    return SS_OK;
+}
+
+extern "C" int ss_add_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, int* first_file_id) {
+    int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    const size_t bytes = (size_t)frames * ch * pcm_bytes_per_sample(format);
+    size_t cap_b = c->pcm_cap;
+    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
+    c->pcm_cap = cap_b;
+    if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ss_add_pcm_channels_batch_device(c, c->d_pcm, format, sr, ch, &frames, 1, first_file_id))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // d_pcm / d_mono are reused by the next call
+    return SS_OK;
+}
+
+extern "C" int ss_add_pcm_channels_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, int64_t frames, int* first_file_id) {
+    int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames);
+    if (rc) return rc;
+    return ss_add_pcm_channels_batch_device(c, pcm_dev, format, sr, ch, &frames, 1, first_file_id);
+}
+
 static int add_f32(ss_ctx* c, const float* s, int64_t n, bool padded, int* file_id) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
     if ((!s && n > 0) || n < 0) return fail(c, SS_ERR_ARG, "ss_add_f32: bad argument");
@@ -672,6 +782,48 @@ extern "C" int ss_get_regions(ss_ctx* c, int file_id, ss_region* out, int64_t ca
     if (!out) return SS_OK;
     if (cap < (int64_t)f.regions.size()) return fail(c, SS_ERR_CAPACITY, "ss_get_regions: capacity too small");
     if (!f.regions.empty()) memcpy(out, f.regions.data(), f.regions.size() * sizeof(ss_region));
+    return SS_OK;
+}
+
+// "speech on any channel" of files [first_file, first_file + n_channels): the channels of one recording (ss_add_pcm_channels*)
+extern "C" int ss_get_regions_union(ss_ctx* c, int first_file, int n_channels, ss_region* out, int64_t cap, int64_t* n_out) {
+    if (!c || !n_out) return fail(c, SS_ERR_ARG, "ss_get_regions_union: bad argument");
+    std::vector<ss_region> rg;
+    int rc = union_regions(c, first_file, n_channels, rg, nullptr);
+    if (rc) return rc;
+    *n_out = (int64_t)rg.size();
+    if (!out) return SS_OK;
+    if (cap < (int64_t)rg.size()) return fail(c, SS_ERR_CAPACITY, "ss_get_regions_union: capacity too small");
+    if (!rg.empty()) memcpy(out, rg.data(), rg.size() * sizeof(ss_region));
+    return SS_OK;
+}
+
+extern "C" int ss_get_region_peaks(ss_ctx* c, int first_file, int n_channels, double* peaks, int64_t cap_regions, int64_t* n_out) {
+    if (!c || !n_out) return fail(c, SS_ERR_ARG, "ss_get_region_peaks: bad argument");
+    int rc = device_results_ok(c, "ss_get_region_peaks");
+    if (rc) return rc;
+    std::vector<ss_region> rg;
+    std::vector<int64_t> bins;
+    if ((rc = union_regions(c, first_file, n_channels, rg, &bins))) return rc;
+    const size_t nr = rg.size(), np = nr * (size_t)n_channels;
+    *n_out = (int64_t)nr;
+    if (!peaks) return SS_OK;
+    if (cap_regions < (int64_t)nr) return fail(c, SS_ERR_CAPACITY, "ss_get_region_peaks: capacity < " + std::to_string(nr) + " regions");
+    if (!nr) return SS_OK;
+    hipSetDevice(c->device);
+    for (int k = 0; k < n_channels; ++k) bins.push_back(c->res_files[first_file + k].bin_off);
+    // one buffer of 8-byte words: [np] peaks, [2 nr] first / last bins, [n_channels] offsets of the channels' averages
+    if ((rc = ensure(c, &c->d_peaks, &c->peaks_cap, np + bins.size()))) return rc;
+    int64_t* d_rng = (int64_t*)(c->d_peaks + np);
+    HIPCHK(c, hipMemcpyAsync(d_rng, bins.data(), bins.size() * 8, hipMemcpyHostToDevice, c->stream));
+    {
+        double nbins = 0;
+        for (size_t r = 0; r < nr; ++r) nbins += (double)(bins[2 * r + 1] - bins[2 * r] + 1);
+        ScopedLaunch sl(c, "region_peaks", 0.0, nbins * n_channels * 12 + (double)np * 8);
+        HIPCHK(c, launch_region_peaks(c->d_avg, c->d_count, d_rng + 2 * nr, n_channels, d_rng, (int64_t)nr, c->d_peaks, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(peaks, c->d_peaks, np * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // `bins` is a host temporary
     return SS_OK;
 }
 

@@ -179,6 +179,7 @@ struct ss_ctx {
     short* d_sil_out = nullptr; size_t sil_out_cap = 0;          // silencer output / frame ranges
     int64_t* d_sil_ranges = nullptr; size_t sil_ranges_cap = 0;
     float* d_mono = nullptr; size_t mono_cap = 0;
+    double* d_peaks = nullptr; size_t peaks_cap = 0;             // ss_get_region_peaks: results, then the regions' bin ranges and the channels' offsets
     ss::BatchFile* d_batch = nullptr; size_t batch_cap = 0;
     std::map<std::pair<int, int>, std::pair<float*, int>> taps;   // (sr_in) -> device taps, half
 
@@ -254,6 +255,7 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
                      int32_t* exponents);
 #endif
 void ensure_regions(ss_ctx* c);
+int union_regions(ss_ctx* c, int first, int n_ch, std::vector<ss_region>& regions, std::vector<int64_t>* bins);
 int upload_winoff(ss_ctx* c, const std::vector<int64_t>& off);
 // abi.hip
 int check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames);

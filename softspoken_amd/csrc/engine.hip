@@ -790,4 +790,45 @@ void ensure_regions(ss_ctx* c) {
     if (timing) fprintf(stderr, "[ss_run] regions %.3f ms\n", now_ms() - t0);
 }
 
+// The merged table of files [first, first + n_ch) of the ended run (ss_get_regions_union): a bin is above when it is above on any of the
+// channels -- the OR of their `above` bits at their bit offsets --, and closes a run when it is covered and above on none; then the run
+// lengths, bin times and gap merge of ensure_regions.  bins (optional): first and last bin of every merged region.
+int union_regions(ss_ctx* c, int first, int n_ch, std::vector<ss_region>& regions, std::vector<int64_t>* bins) {
+    regions.clear();
+    if (bins) bins->clear();
+    if (!c->res_valid) return fail(c, SS_ERR_STATE, "ss_get_regions_union: no completed ss_run");
+    if (first < 0 || n_ch < 1 || (size_t)first + (size_t)n_ch > c->res_files.size())
+        return fail(c, SS_ERR_ARG, "ss_get_regions_union: files outside the run");
+    const ss_ctx::ResFile& f0 = c->res_files[first];
+    for (int k = 1; k < n_ch; ++k)
+        if (c->res_files[first + k].n_bins != f0.n_bins) return fail(c, SS_ERR_ARG, "ss_get_regions_union: the files differ in their number of bins");
+    auto bit = [](const unsigned long long* w, int64_t j) { return (w[j >> 6] >> (j & 63)) & 1ull; };
+    const double break_s = c->res_brk;
+    bool open = false, have = false;
+    int64_t run0 = 0, run1 = 0, reg0 = 0, reg1 = 0;
+    ss_region cur{0, 0};
+    auto close_run = [&]() {
+        const double s0 = bin_time(run0), e0 = bin_time(run1);
+        if (have && s0 - cur.end <= break_s) { cur.end = e0; reg1 = run1; }
+        else {
+            if (have) { regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0}); if (bins) { bins->push_back(reg0); bins->push_back(reg1); } }
+            cur.start = s0; cur.end = e0; reg0 = run0; reg1 = run1; have = true;
+        }
+        open = false;
+    };
+    for (int64_t j = 0; j < f0.n_bins; ++j) {
+        bool above = false, covered = false;
+        for (int k = 0; k < n_ch; ++k) {
+            const int64_t at = c->res_files[first + k].bin_off + j;
+            above = above || bit(c->r_above, at);
+            covered = covered || bit(c->r_cov, at);
+        }
+        if (above) { if (!open) { run0 = j; open = true; } run1 = j; }
+        else if (covered && open) close_run();
+    }
+    if (open) close_run();
+    if (have) { regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0}); if (bins) { bins->push_back(reg0); bins->push_back(reg1); } }
+    return SS_OK;
+}
+
 }  // namespace ss

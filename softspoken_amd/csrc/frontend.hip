@@ -958,6 +958,190 @@ hipError_t launch_decode_mono_batch(const void* pcm, int format, int channels, c
 }
 
 // =========================================================================================================
+// Per-channel ingest (ss_add_pcm_channels*): a recording of C channels becomes C signals, no mixdown.  Signal c is bit for bit what the
+// kernels above make of the one-channel PCM of channel c's samples: decode_sample(base, format, i C + c), then the same polyphase
+// arithmetic (float32 multiply, then add, tap order, no contraction).
+// =========================================================================================================
+// 22 050 Hz input (dst = the arena) and the first half of the unfused pair (dst = the mono planes resample_batch_kernel reads): every
+// interleaved frame is read once and written to C planes
+__global__ __launch_bounds__(256) void decode_channels_batch_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
+                                                                    const ChanFile* __restrict__ files, float* __restrict__ dst) {
+    const ChanFile f = files[blockIdx.y];
+    const unsigned char* base = pcm + f.pcm_off;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < f.frames; i += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < channels; ++c) dst[f.mono_off + (int64_t)c * f.mono_stride + i] = decode_sample(base, format, i * channels + c);
+}
+
+// The fused form per channel.  Tables, tile layout, lane-to-phase dealing and the multiply loop are resample_fused_kernel's (see there);
+// the table of a 48 k -> 22.05 k block already takes ~142 of the 160 KB, so there is ONE tile and the channels take turns in it: what a
+// thread fetched for an item stays in registers -- FAST (16-bit stereo): the 32-bit word that holds both channels of a frame; otherwise
+// CP decoded samples per frame -- and per channel the tile is staged again from them, the multiply loop runs, that channel's outputs are
+// stored.  The PCM of a tile is requested once per CP channels; recordings with more channels take ceil(C / CP) passes over their items
+// with the tables staged once.  The next item's request goes out behind the LAST channel's staging, so it is in flight during one multiply
+// loop, as in the mixdown kernel, and needs no second set of registers.
+static constexpr int kRes3CP = 2;                         // channels per pass: 2 x kRes3Stage sample registers beside the 2 x kRes3Stage tile offsets
+template <bool FAST>
+__global__ __launch_bounds__(kRes3Threads) void resample_fused_channels_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
+                                                                               const ChanFile* __restrict__ files, int n_files, int items_per_file,
+                                                                               int L, int M, int half, int groups, int pitch_v, int lpg,
+                                                                               const float* __restrict__ taps, float* __restrict__ arena) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float s_res3[];
+    const int nt = 2 * half, pitch_t = nt | 1;
+    const int R = 4 * groups;
+    float* s_x = s_res3;                                  // [M][pitch_v]
+    float* s_x1 = s_x + (size_t)M * pitch_v;              // [nt][pitch_v]: rows u < nt shifted by one
+    float* s_t = s_x1 + (size_t)nt * pitch_v;             // [lpg][pitch_t]
+    int* s_perm = (int*)(s_t + (size_t)lpg * pitch_t);    // [lpg]: phase of lane s of a group, or -1
+    const int tid = threadIdx.x;
+    int* s_cls = s_perm + lpg;                            // [L]
+    for (int s = tid; s < lpg; s += kRes3Threads) s_perm[s] = lpg == L ? s : -1;
+    if (tid < L) s_cls[tid] = (int)(((int64_t)tid * M) / L) & 15;
+    __syncthreads();
+    if (lpg != L && tid < L) {
+        const int c = s_cls[tid];
+        int k = 0;
+        for (int ph = 0; ph < tid; ++ph) k += s_cls[ph] == c;
+        s_perm[res3_slot(k, c)] = tid;
+    }
+    __syncthreads();
+    for (int s = tid / 64; s < lpg; s += kRes3Threads / 64) {
+        const int ph = s_perm[s];
+        if (ph < 0) continue;
+        const int q = (int)(((int64_t)ph * M) % L);
+        for (int j = tid & 63; j < nt; j += 64) s_t[s * pitch_t + j] = taps[(size_t)q * nt + j];
+    }
+    const int g = tid / lpg, slot = tid - g * lpg;
+    const int p_of = g < groups ? s_perm[slot] : -1;
+    const bool worker = p_of >= 0;
+    const int p = worker ? p_of : 0;
+    const int b = (int)(((int64_t)p * M) / L);
+    const int jx = M - b < nt ? M - b : nt;
+    const float* tp = s_t + (worker ? slot : 0) * pitch_t;
+    const float* xa = s_x + (size_t)b * pitch_v + 4 * g;
+    const float* xb = s_x1 + ((size_t)b * pitch_v + 4 * g) - (size_t)M * pitch_v;
+    const int span = R * M + M + nt;
+    const int n_items = n_files * items_per_file;
+    int off_x[kRes3Stage], off_x1[kRes3Stage];
+#pragma unroll
+    for (int k = 0; k < kRes3Stage; ++k) {
+        const int ip = tid + k * kRes3Threads;
+        const int vv = ip / M, u = ip - vv * M;
+        off_x[k] = (ip < span && vv < pitch_v) ? u * pitch_v + vv : -1;
+        off_x1[k] = (ip < span && u < nt && vv >= 1 && vv - 1 < pitch_v) ? u * pitch_v + vv - 1 : -1;
+    }
+    uint32_t raw[kRes3Stage];
+    float val[kRes3CP][kRes3Stage];
+    auto valid_item = [&](int item, ChanFile& f, int& it) -> bool {
+        if (item >= n_items) return false;
+        const int fi = item / items_per_file;
+        it = item - fi * items_per_file;
+        f = files[fi];
+        return (int64_t)it * L * R < f.n_out;
+    };
+    for (int c0 = 0; c0 < channels; c0 += kRes3CP) {      // FAST: channels == 2, one pass
+        const int ncp = channels - c0 < kRes3CP ? channels - c0 : kRes3CP;
+        auto fetch = [&](const ChanFile& f, int it) {
+            const int64_t i_lo = (int64_t)it * R * M - half + 1;
+            const unsigned char* base = pcm + f.pcm_off;
+#pragma unroll
+            for (int k = 0; k < kRes3Stage; ++k) {
+                const int64_t idx = i_lo + tid + k * kRes3Threads;
+                const bool in = off_x[k] >= 0 && idx >= 0 && idx < f.frames;
+                if constexpr (FAST) {
+                    raw[k] = 0u;
+                    if (in) raw[k] = ((const uint32_t*)base)[idx];
+                } else {
+#pragma unroll
+                    for (int cc = 0; cc < kRes3CP; ++cc)
+                        val[cc][k] = (in && cc < ncp) ? decode_sample(base, format, idx * channels + c0 + cc) : 0.f;
+                }
+            }
+        };
+        int item = blockIdx.x;
+        ChanFile f{}, fn{};
+        int it = 0, itn = 0;
+        while (item < n_items && !valid_item(item, f, it)) item += gridDim.x;
+        if (item >= n_items) return;                      // (the same items in every pass: block-uniform)
+        fetch(f, it);
+        bool more = true;
+        while (more) {
+            int next = item;
+#pragma unroll
+            for (int cc = 0; cc < kRes3CP; ++cc) {
+                if (cc >= ncp) break;                     // block-uniform
+                __syncthreads();                          // the previous multiply loop's reads (and, first time, the table) are done / visible
+#pragma unroll
+                for (int k = 0; k < kRes3Stage; ++k) {
+                    float v;
+                    if constexpr (FAST) v = (float)(short)(cc ? raw[k] >> 16 : raw[k] & 0xffffu) / 32768.0f;   // decode_sample's x / 32768
+                    else v = val[cc][k];
+                    if (off_x[k] >= 0) s_x[off_x[k]] = v;
+                    if (off_x1[k] >= 0) s_x1[off_x1[k]] = v;
+                }
+                __syncthreads();
+                if (cc == ncp - 1) {                      // the registers are free again: the next item's request, in flight during this multiply loop
+                    next = item + gridDim.x;
+                    while (next < n_items && !valid_item(next, fn, itn)) next += gridDim.x;
+                    more = next < n_items;
+                    if (more) fetch(fn, itn);
+                }
+                if (worker) {
+                    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                    auto tap = [&](const float4& x4, float t) {                    // two roundings per term, as the oracle
+                        { const float pr = t * x4.x; a0 = a0 + pr; }
+                        { const float pr = t * x4.y; a1 = a1 + pr; }
+                        { const float pr = t * x4.z; a2 = a2 + pr; }
+                        { const float pr = t * x4.w; a3 = a3 + pr; }
+                    };
+#pragma unroll 4
+                    for (int j = 0; j < nt; ++j) tap(*(const float4*)((j < jx ? xa : xb) + (size_t)j * pitch_v), tp[j]);
+                    float* out = arena + f.out_off + (int64_t)(c0 + cc) * f.out_stride;
+                    const int64_t m = (int64_t)it * L * R + (int64_t)(4 * g) * L + p;
+                    if (m < f.n_out) out[m] = a0;
+                    if (m + L < f.n_out) out[m + L] = a1;
+                    if (m + 2 * (int64_t)L < f.n_out) out[m + 2 * (int64_t)L] = a2;
+                    if (m + 3 * (int64_t)L < f.n_out) out[m + 3 * (int64_t)L] = a3;
+                }
+            }
+            item = next; f = fn; it = itn;
+        }
+        __syncthreads();                                  // the last multiply loop's reads, before the next pass stages its first tile
+    }
+}
+
+hipError_t launch_decode_channels_batch(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_frames,
+                                        float* dst, hipStream_t s) {
+    if (n_files <= 0 || max_frames <= 0) return hipSuccess;
+    const unsigned gx = (unsigned)std::min<int64_t>((max_frames + 255) / 256, 4096);
+    hipLaunchKernelGGL(decode_channels_batch_kernel, dim3(gx, (unsigned)n_files), dim3(256), 0, s, (const unsigned char*)pcm, format, channels,
+                       d_files, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_fused_channels(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_out, int L,
+                                          int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s) {
+    if (n_files <= 0 || max_out <= 0) return hipSuccess;
+    const Res3Geom gm = res3_geometry(L, M, half);
+    if (!gm.groups) return hipErrorInvalidValue;
+    static std::atomic<uint64_t> attr_done{0};              // (per device: kernels.h allow_full_lds)
+    if (hipError_t e = allow_full_lds((const void*)resample_fused_channels_kernel<true>, attr_done)) return e;
+    static std::atomic<uint64_t> attr_done2{0};
+    if (hipError_t e = allow_full_lds((const void*)resample_fused_channels_kernel<false>, attr_done2)) return e;
+    const int64_t per_item = (int64_t)L * 4 * gm.groups;
+    const int64_t ipf = (max_out + per_item - 1) / per_item;
+    if (ipf * n_files >= (int64_t)1 << 30) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::min<int64_t>(ipf * n_files, num_cus > 0 ? num_cus : 256);
+    if (format == 2 && channels == 2)
+        hipLaunchKernelGGL(resample_fused_channels_kernel<true>, dim3(grid), dim3(kRes3Threads), gm.lds, s, (const unsigned char*)pcm, format,
+                           channels, d_files, n_files, (int)ipf, L, M, half, gm.groups, gm.pitch_v, gm.lpg, taps, arena);
+    else
+        hipLaunchKernelGGL(resample_fused_channels_kernel<false>, dim3(grid), dim3(kRes3Threads), gm.lds, s, (const unsigned char*)pcm, format,
+                           channels, d_files, n_files, (int)ipf, L, M, half, gm.groups, gm.pitch_v, gm.lpg, taps, arena);
+    return hipGetLastError();
+}
+
+// =========================================================================================================
 // Silencer (silencer_ui.py:974-998): every sample decoded to float32 as the loader does, frames inside a
 // reviewed interval zeroed, the rest written as 16-bit PCM -- lrintf(x * 32767) without clipping, which is
 // what libsndfile does for a float buffer written to a PCM_16 WAV (soundfile's default subtype).
@@ -1078,6 +1262,35 @@ hipError_t launch_bin_masks(const double* avg, const int32_t* count, int64_t tot
                             unsigned long long* covered, hipStream_t s) {
     if (total_bins <= 0) return hipSuccess;
     hipLaunchKernelGGL(bin_masks_kernel, dim3((unsigned)((total_bins + 255) / 256)), dim3(256), 0, s, avg, count, total_bins, threshold, above, covered);
+    return hipGetLastError();
+}
+
+// Peak of one channel's averaged score inside one merged region (ss_get_region_peaks).  A maximum of doubles is exact and does not depend
+// on the order, so the tree below gives what a host loop gives; fmax passes over NaNs, uncovered bins do not take part.
+__global__ __launch_bounds__(256) void region_peaks_kernel(const double* __restrict__ avg, const int32_t* __restrict__ count,
+                                                           const int64_t* __restrict__ chan_off, int n_channels,
+                                                           const int64_t* __restrict__ rng, double* __restrict__ peaks) {
+    __shared__ double s_m[256];
+    const int64_t r = blockIdx.x;
+    const int c = blockIdx.y;
+    const int64_t lo = rng[2 * r], hi = rng[2 * r + 1], base = chan_off[c];
+    double m = -__builtin_inf();
+    for (int64_t j = lo + threadIdx.x; j <= hi; j += 256)
+        if (count[base + j] >= 1) m = fmax(m, avg[base + j]);
+    s_m[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) peaks[r * n_channels + c] = s_m[0];
+}
+
+hipError_t launch_region_peaks(const double* avg, const int32_t* count, const int64_t* chan_off, int n_channels, const int64_t* rng,
+                               int64_t n_regions, double* peaks, hipStream_t s) {
+    if (n_regions <= 0 || n_channels <= 0) return hipSuccess;
+    hipLaunchKernelGGL(region_peaks_kernel, dim3((unsigned)n_regions, (unsigned)n_channels), dim3(256), 0, s, avg, count, chan_off, n_channels,
+                       rng, peaks);
     return hipGetLastError();
 }
 

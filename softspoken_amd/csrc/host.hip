@@ -171,6 +171,18 @@ extern "C" int ss_find_regions(const double* avg, const int64_t* bin_idx, int64_
     return SS_OK;
 }
 
+// "speech on any channel": the same on the element-wise fmax of the channels' series (a NaN on one channel does not hide the other; a
+// bin that is NaN on all of them stays in the series, is not above and closes a run)
+extern "C" int ss_find_regions_union(const double* avg, const int64_t* bin_idx, int64_t n, int n_channels, double threshold, double break_s,
+                                     ss_region* out, int64_t cap, int64_t* n_out) {
+    if (n_channels < 1 || n < 0 || (n > 0 && (!avg || !bin_idx)) || !n_out) return fail(nullptr, SS_ERR_ARG, "ss_find_regions_union: bad argument");
+    if (n_channels == 1) return ss_find_regions(avg, bin_idx, n, threshold, break_s, out, cap, n_out);
+    std::vector<double> m(avg, avg + n);
+    for (int c = 1; c < n_channels; ++c)
+        for (int64_t i = 0; i < n; ++i) m[i] = std::fmax(m[i], avg[(size_t)c * n + i]);
+    return ss_find_regions(m.data(), bin_idx, n, threshold, break_s, out, cap, n_out);
+}
+
 // Python repr(float): shortest digits that round-trip, positional for 1e-4 <= |x| < 1e16.
 static std::string py_repr(double v) {
     if (v == 0.0) return std::signbit(v) ? "-0.0" : "0.0";

@@ -154,6 +154,14 @@ hipError_t launch_resample_fused(const void* pcm, int format, int channels, cons
                                  int half, const float* taps, float* arena, int num_cus, hipStream_t s);
 hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, int n_files, int64_t max_out, int L, int M, int half,
                                  const float* taps, float* arena, int num_cus, hipStream_t s);
+// per-channel ingest (no mixdown): channel c of a recording is decoded to dst[mono_off + c mono_stride ..) / resampled to
+// arena[out_off + c out_stride ..); one descriptor per recording, the channels' planes a constant stride apart
+struct ChanFile { int64_t pcm_off; int64_t frames; int64_t mono_off; int64_t out_off; int64_t n_out; int64_t mono_stride; int64_t out_stride; };
+hipError_t launch_decode_channels_batch(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_frames,
+                                        float* dst, hipStream_t s);
+// the fused form (resample_fused_applies): the PCM of a tile fetched once for two channels, the channels taking turns in the one LDS tile
+hipError_t launch_resample_fused_channels(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_out, int L,
+                                          int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s);
 
 // ---- overlap averaging (NNDetector.py:153-190), double accumulation ---------------------------------
 struct AvgFile { int64_t logit_off; int64_t bin_off; int32_t W; int32_t n_bins; int64_t start_off; };
@@ -162,6 +170,10 @@ hipError_t launch_average(const float* logits, const AvgFile* files, int n_files
 // covered / above-threshold bit per bin, 64 bins per word (words = ceil(total_bins / 64), both arrays)
 hipError_t launch_bin_masks(const double* avg, const int32_t* count, int64_t total_bins, double threshold, unsigned long long* above,
                             unsigned long long* covered, hipStream_t s);
+// ss_get_region_peaks: peaks[r * n_channels + c] = max of avg[chan_off[c] + j] over the covered, non-NaN bins j of [rng[2 r], rng[2 r + 1]]
+// (-inf when there is none); one block per (region, channel)
+hipError_t launch_region_peaks(const double* avg, const int32_t* count, const int64_t* chan_off, int n_channels, const int64_t* rng,
+                               int64_t n_regions, double* peaks, hipStream_t s);
 
 // ---- streaming detection (stream.hip): one launch per step for all streams, a descriptor per stream ----------------------------
 struct StreamCopy { const float* src; float* dst; int64_t n; };                       // src == nullptr: n zeros

@@ -85,6 +85,7 @@ _SIGS = {
     "ss_resampled_length": (C.c_int64, [C.c_int64, C.c_int]),
     "ss_plan_windows": (C.c_int64, [C.c_double, _P, C.c_int64]),
     "ss_find_regions": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_find_regions_union": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_format_csv_rows": (C.c_int64, [C.c_char_p, C.c_char_p, _P, C.c_int64, C.c_int64, _P, C.c_int64]),
     "ss_create": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "ss_destroy": (None, [_P]),
@@ -94,6 +95,9 @@ _SIGS = {
     "ss_add_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int)]),
     "ss_add_pcm_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int)]),
     "ss_add_pcm_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
+    "ss_add_pcm_channels": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int)]),
+    "ss_add_pcm_channels_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int)]),
+    "ss_add_pcm_channels_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "ss_add_f32_22k": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
     "ss_add_padded_f32_22k": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
     "ss_signal_length": (C.c_int64, [_P, C.c_int, C.c_int]),
@@ -123,6 +127,8 @@ _SIGS = {
     "ss_get_avg": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_get_regions": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_get_regions_batch": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_get_regions_union": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_get_region_peaks": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_sync": (C.c_int, [_P]),
     "ss_reset_kernel_stats": (C.c_int, [_P]),
     "ss_get_kernel_stats": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -213,6 +219,21 @@ def find_regions(avg, bin_idx, threshold=0.1, break_s=0.5):
     out = (Region * cap)()
     n = C.c_int64(0)
     _check(lib().ss_find_regions(_ptr(avg), _ptr(bin_idx), len(avg), threshold, break_s, out, cap, C.byref(n)))
+    return [(out[i].start, out[i].end) for i in range(n.value)]
+
+
+def find_regions_union(avg, bin_idx, threshold=0.1, break_s=0.5):
+    """The merged table of a recording's channels ("speech on any channel"): avg [n_channels, n] over one bin_idx [n]."""
+    avg = np.ascontiguousarray(avg, dtype=np.float64)
+    if avg.ndim != 2:
+        raise ValueError("avg must be [n_channels, n]")
+    bin_idx = np.ascontiguousarray(bin_idx, dtype=np.int64)
+    if bin_idx.shape != (avg.shape[1],):
+        raise ValueError("bin_idx must hold one bin number per column of avg")
+    cap = avg.shape[1] // 2 + 1
+    out = (Region * cap)()
+    n = C.c_int64(0)
+    _check(lib().ss_find_regions_union(_ptr(avg), _ptr(bin_idx), avg.shape[1], avg.shape[0], threshold, break_s, out, cap, C.byref(n)))
     return [(out[i].start, out[i].end) for i in range(n.value)]
 
 
@@ -380,6 +401,29 @@ class Context:
             self._need_bytes(np.asarray(host_copy), fmt, channels, fr)
         fid = C.c_int(-1)
         self._ck(lib().ss_add_pcm_batch_device(self._h, C.c_void_p(dev_ptr), fmt, sr, channels, _ptr(fr), len(fr), C.byref(fid)))
+        return fid.value
+
+    # ---- per-channel ingest: a recording of C channels -> C signals with consecutive file ids, no mixdown ---------------------
+    def add_pcm_channels(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int) -> int:
+        """-> first file id; channel c is file first + c, bit for bit what add_pcm stores for that channel's samples as mono PCM."""
+        pcm = np.ascontiguousarray(pcm)
+        self._need_bytes(pcm, fmt, channels, frames)
+        fid = C.c_int(-1)
+        self._ck(lib().ss_add_pcm_channels(self._h, _ptr(pcm), fmt, sr, channels, frames, C.byref(fid)))
+        return fid.value
+
+    def add_pcm_channels_device(self, dev_ptr: int, fmt: int, sr: int, channels: int, frames: int) -> int:
+        fid = C.c_int(-1)
+        self._ck(lib().ss_add_pcm_channels_device(self._h, C.c_void_p(dev_ptr), fmt, sr, channels, frames, C.byref(fid)))
+        return fid.value
+
+    def add_pcm_channels_batch_device(self, dev_ptr: int, fmt: int, sr: int, channels: int, frames, host_copy: np.ndarray | None = None) -> int:
+        """As add_pcm_batch_device: recording r, channel c -> file id first + r * channels + c."""
+        fr = np.ascontiguousarray(frames, dtype=np.int64)
+        if host_copy is not None:
+            self._need_bytes(np.asarray(host_copy), fmt, channels, fr)
+        fid = C.c_int(-1)
+        self._ck(lib().ss_add_pcm_channels_batch_device(self._h, C.c_void_p(dev_ptr), fmt, sr, channels, _ptr(fr), len(fr), C.byref(fid)))
         return fid.value
 
     def add_wav_bytes(self, buf) -> tuple[int, WavInfo]:
@@ -564,6 +608,23 @@ class Context:
         out = np.zeros((max(n.value, 1), 2), dtype=np.float64)
         self._ck(lib().ss_get_regions_batch(self._h, first, n_files, _ptr(counts), _ptr(out), n.value, C.byref(n)))
         return counts[:n_files], out[:n.value]
+
+    def regions_union(self, first: int, n_channels: int):
+        """The merged table ("speech on any channel") of files first .. first + n_channels - 1 of the ended run."""
+        n = C.c_int64(0)
+        self._ck(lib().ss_get_regions_union(self._h, int(first), int(n_channels), None, 0, C.byref(n)))
+        arr = (Region * max(1, n.value))()
+        self._ck(lib().ss_get_regions_union(self._h, int(first), int(n_channels), arr, n.value, C.byref(n)))
+        return [(arr[i].start, arr[i].end) for i in range(n.value)]
+
+    def region_peaks(self, first: int, n_channels: int) -> np.ndarray:
+        """float64 [merged regions, n_channels]: each channel's highest averaged score inside each region of regions_union()."""
+        n = C.c_int64(0)
+        self._ck(lib().ss_get_region_peaks(self._h, int(first), int(n_channels), None, 0, C.byref(n)))
+        out = np.empty((n.value, int(n_channels)), dtype=np.float64)
+        if n.value:
+            self._ck(lib().ss_get_region_peaks(self._h, int(first), int(n_channels), _ptr(out), n.value, C.byref(n)))
+        return out
 
     def sync(self):
         self._ck(lib().ss_sync(self._h))
