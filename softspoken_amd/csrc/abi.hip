@@ -66,7 +66,7 @@ extern "C" void ss_destroy(ss_ctx* c) {
     hipSetDevice(c->device);
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->lane1.stream) hipStreamSynchronize(c->lane1.stream);
+    if (c->lane_stream) hipStreamSynchronize(c->lane_stream);
     resolve_events(c);
     for (void* p : c->owned) hipFree(p);
     for (void* p : c->user_dev) hipFree(p);
@@ -80,9 +80,9 @@ extern "C" void ss_destroy(ss_ctx* c) {
     if (c->ev_run0) hipEventDestroy(c->ev_run0);
     if (c->ev_run1) hipEventDestroy(c->ev_run1);
     if (c->stream) hipStreamDestroy(c->stream);
-    if (c->lane1.stream) hipStreamDestroy(c->lane1.stream);
-    if (c->lane1.ev_in) hipEventDestroy(c->lane1.ev_in);
-    if (c->lane1.ev_out) hipEventDestroy(c->lane1.ev_out);
+    if (c->lane_stream) hipStreamDestroy(c->lane_stream);
+    if (c->lane_ev_in) hipEventDestroy(c->lane_ev_in);
+    if (c->lane_ev_out) hipEventDestroy(c->lane_ev_out);
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     if (c->ev_copy) hipEventDestroy(c->ev_copy);
     if (c->h_above) hipHostFree(c->h_above);
@@ -226,7 +226,7 @@ extern "C" int ss_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, in
     if (!ranges.empty())
         HIPCHK(c, hipMemcpyAsync(c->d_sil_ranges, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice, c->stream));
     {
-        ScopedLaunch sl(c, "silence_encode_kernel", 0.0, (double)bytes + 2.0 * (double)total);
+        ScopedLaunch sl(c, c->stream, "silence_encode_kernel", 0.0, (double)bytes + 2.0 * (double)total);
         HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, c->d_sil_ranges, (int)(ranges.size() / 2), c->d_sil_out, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
@@ -297,7 +297,7 @@ extern "C" int ss_stft512_magnitude(ss_ctx* c, const float* samples, int64_t n, 
     if ((rc = ensure(c, &c->d_sm, &c->sm_cap, (size_t)nf * 257))) return rc;
     if (n) HIPCHK(c, hipMemcpyAsync(c->d_sx, samples, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     {
-        ScopedLaunch sl(c, "stft512_mag_kernel", 0.0, (double)n * 4 + (double)nf * 257 * 4);
+        ScopedLaunch sl(c, c->stream, "stft512_mag_kernel", 0.0, (double)n * 4 + (double)nf * 257 * 4);
         HIPCHK(c, launch_stft512_mag(c->d_sx, n, nf, c->d_sm, c->num_cus, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(out, c->d_sm, (size_t)nf * 257 * 4, hipMemcpyDeviceToHost, c->stream));
@@ -350,7 +350,7 @@ extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int forma
         for (int i = 0; i < n_files; ++i) bf[i].mono_off = bf[i].out_off;
         HIPCHK(c, hipMemcpyAsync(c->d_batch, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        ScopedLaunch sl(c, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
+        ScopedLaunch sl(c, c->stream, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
         HIPCHK(c, launch_decode_mono_batch(pcm_dev, format, ch, c->d_batch, n_files, max_frames, c->d_arena, c->stream));
     } else {
         int L, M, half; float* d_taps;
@@ -358,15 +358,15 @@ extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int forma
         double n22sum = 0; for (auto& b : bf) n22sum += (double)b.n_out;
         if (resample_fused_applies(L, M, half) && dev_env("SOFTSPOKEN_RES3", 1)) {
             // decode + mixdown inside the resampler's LDS staging: one launch, no mono tensor
-            ScopedLaunch sl(c, "resample_fused", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
+            ScopedLaunch sl(c, c->stream, "resample_fused", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
             HIPCHK(c, launch_resample_fused(pcm_dev, format, ch, c->d_batch, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
         } else {
             if ((rc = ensure(c, &c->d_mono, &c->mono_cap, (size_t)mono_off + 16))) return rc;
             {
-                ScopedLaunch sl(c, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
+                ScopedLaunch sl(c, c->stream, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
                 HIPCHK(c, launch_decode_mono_batch(pcm_dev, format, ch, c->d_batch, n_files, max_frames, c->d_mono, c->stream));
             }
-            ScopedLaunch sl(c, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * total_frames + 4.0 * n22sum);
+            ScopedLaunch sl(c, c->stream, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * total_frames + 4.0 * n22sum);
             HIPCHK(c, launch_resample_batch(c->d_mono, c->d_batch, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
         }
     }
@@ -444,19 +444,19 @@ extern "C" int ss_add_pcm_channels_batch_device(ss_ctx* c, const void* pcm_dev, 
     HIPCHK(c, hipMemcpyAsync(d_bf, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // cf / bf are host temporaries
     if (sr == SS_SAMPLE_RATE) {
-        ScopedLaunch sl(c, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
+        ScopedLaunch sl(c, c->stream, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
         HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_arena, c->stream));
     } else if (fused) {
         // decode inside the resampler's LDS staging, the channels taking turns in the tile: one launch, no mono tensor
-        ScopedLaunch sl(c, "resample_fused_channels", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
+        ScopedLaunch sl(c, c->stream, "resample_fused_channels", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
         HIPCHK(c, launch_resample_fused_channels(pcm_dev, format, ch, d_cf, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
     } else {
         if ((rc = ensure(c, &c->d_mono, &c->mono_cap, (size_t)mono_off + 16))) return rc;
         {
-            ScopedLaunch sl(c, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
+            ScopedLaunch sl(c, c->stream, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
             HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_mono, c->stream));
         }
-        ScopedLaunch sl(c, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * ch * total_frames + 4.0 * n22sum);
+        ScopedLaunch sl(c, c->stream, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * ch * total_frames + 4.0 * n22sum);
         HIPCHK(c, launch_resample_batch(c->d_mono, d_bf, (int)bf.size(), max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
     }
     rollback.done = true;
@@ -631,9 +631,9 @@ extern "C" int ss_features(ss_ctx* c, int file_id, const int64_t* starts, int n,
     if ((rc = ensure_workspace(c, ch))) return rc;
     for (int i0 = 0; i0 < n; i0 += ch) {
         const int m = std::min(ch, n - i0);
-        if ((rc = forward_chunk(c, c->d_winoff + i0, m, nullptr, nullptr, nullptr))) return rc;
+        if ((rc = forward_chunk(c, c->ws[0], c->stream, c->d_arena, c->d_winoff + i0, m, nullptr, nullptr))) return rc;
         if (feat_out) {
-            HIPCHK(c, hipMemcpyAsync(feat_out + (size_t)i0 * 32768, c->d_feat, (size_t)m * 32768 * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(feat_out + (size_t)i0 * 32768, c->ws[0].feat, (size_t)m * 32768 * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -654,19 +654,19 @@ extern "C" int ss_infer_windows(ss_ctx* c, int file_id, const int64_t* starts, i
     if ((rc = ensure(c, &c->d_logits, &c->logits_cap, (size_t)n * 256))) return rc;
     if (spec_out && (rc = ensure(c, &c->d_spec, &c->spec_cap, (size_t)ch * 2 * 32768))) return rc;
     c->logits_valid = false;
-    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    if ((rc = range_clear(c, c->stream))) return rc;
     for (int i0 = 0; i0 < n; i0 += ch) {
         const int m = std::min(ch, n - i0);
-        if ((rc = forward_chunk(c, c->d_winoff + i0, m, c->d_logits + (size_t)i0 * 256, spec_out ? c->d_spec : nullptr, nullptr))) return rc;
+        if ((rc = forward_chunk(c, c->ws[0], c->stream, c->d_arena, c->d_winoff + i0, m, c->d_logits + (size_t)i0 * 256, spec_out ? c->d_spec : nullptr))) return rc;
         if (spec_out) {
             HIPCHK(c, hipMemcpyAsync(spec_out + (size_t)i0 * 2 * 32768, c->d_spec, (size_t)m * 2 * 32768 * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
     }
     HIPCHK(c, hipMemcpyAsync(mask_out, c->d_logits, (size_t)n * 256 * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->d_range_flag) HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = range_fetch(c, c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_range_flag && *c->h_range_flag)
+    if (range_left(c))
         return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; run this checkpoint with the fp32 mode");
     return SS_OK;
 }
@@ -819,7 +819,7 @@ extern "C" int ss_get_region_peaks(ss_ctx* c, int first_file, int n_channels, do
     {
         double nbins = 0;
         for (size_t r = 0; r < nr; ++r) nbins += (double)(bins[2 * r + 1] - bins[2 * r] + 1);
-        ScopedLaunch sl(c, "region_peaks", 0.0, nbins * n_channels * 12 + (double)np * 8);
+        ScopedLaunch sl(c, c->stream, "region_peaks", 0.0, nbins * n_channels * 12 + (double)np * 8);
         HIPCHK(c, launch_region_peaks(c->d_avg, c->d_count, d_rng + 2 * nr, n_channels, d_rng, (int64_t)nr, c->d_peaks, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(peaks, c->d_peaks, np * 8, hipMemcpyDeviceToHost, c->stream));
@@ -876,4 +876,4 @@ extern "C" int ss_debug_activation(ss_ctx* c, const char* name, int plane, int64
 }
 #endif
 
-extern "C" int64_t ss_workspace_bytes(ss_ctx* c) { return c ? c->ws_bytes + c->lane1.bytes : -1; }
+extern "C" int64_t ss_workspace_bytes(ss_ctx* c) { return c ? c->ws[0].bytes + c->ws[1].bytes : -1; }

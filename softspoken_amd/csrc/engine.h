@@ -1,7 +1,8 @@
 // Internal state of a context, shared by the host-side units of the library:
 //   weights.hip   weights blob -> folded BatchNorm -> MFMA fragment packing, front-end tables      (ss_create's work)
-//   engine.hip    activation workspace, per-chunk launch sequence of the U-Net, job halves (plan + enqueue / wait)
-//   host.hip      host-only pieces of the path: WAV header walk, window plan, regions, CSV text
+//   engine.hip    activation workspaces (ss::Workspace), launch sequence of one pass of the U-Net on a workspace and a stream, job halves
+//                 (plan + enqueue / wait), the region scans of an ended run
+//   host.hip      host-only pieces of the path: WAV header walk, window plan, run merger (ss::RunMerger) and regions, CSV text
 //   abi.hip       the C ABI (include/softspoken.h): argument checks, arena, getters, measurement
 // Not part of the C ABI.
 #pragma once
@@ -97,6 +98,26 @@ struct SepPlan {
     std::vector<ss_separation_range> ranges;
 };
 
+// An activation workspace for `chunk` windows (engine.hip alloc_ws): what one pass of the network writes.  A context has two -- the main
+// one, and the second lane's of a run with several passes.
+struct Workspace {
+    int chunk = 0; int64_t bytes = 0;
+    std::map<std::string, void*> act;                     // tensor name -> first byte (high plane in f16x2 mode) inside arena
+    void* arena = nullptr;
+    int64_t lo_delta = 0;                                 // f16x2: byte distance from a tensor's high plane to its low plane
+    float* feat = nullptr; float* flat = nullptr;         // front-end features; conv_flatten's row-group partial sums
+    int flat_groups = 0;                                  // row groups the last FLAT launch wrote per window into `flat`
+};
+
+// Gap merge of runs of bins above the threshold, in bin order (NNDetector.py:131-141, then worker.py:100's shift by the 3 s of padding):
+// a run whose start lies at most brk seconds behind the current region's end extends it, any other run emits the region and opens the
+// next.  bins (optional): first and last bin of every emitted region.  The callers keep their own scans for the runs.
+struct RunMerger {
+    double brk = 0; bool have = false; ss_region cur{0, 0}; int64_t reg0 = 0, reg1 = 0;
+    void add(int64_t first_bin, int64_t last_bin, std::vector<ss_region>& out, std::vector<int64_t>* bins = nullptr);
+    void flush(std::vector<ss_region>& out, std::vector<int64_t>* bins = nullptr);      // emits the current region, if any
+};
+
 struct KStat { std::string name; int64_t launches = 0; double ms = 0, flops = 0, bytes = 0, issued = 0; };
 struct PendingEvt { int sid; hipEvent_t a, b; };
 
@@ -122,7 +143,6 @@ struct ss_ctx {
     float2 *d_win2 = nullptr, *d_twt = nullptr, *d_wkt = nullptr; float* d_mel_wq = nullptr; int* d_mel_p0 = nullptr;   // second front-end kernel
     float *d_first_w = nullptr, *d_first_b = nullptr;
     float* d_flat_b = nullptr; void* d_flat_frag = nullptr; void* d_flat_frag4 = nullptr;
-    int flat_groups = 0;                                  // row groups the last FLAT launch wrote per window
     float *d_spec_w = nullptr, *d_spec_b = nullptr;
     ss::Head1dWeights head{};
     std::vector<ss::ConvPlan> convs;  // in launch order; pairs (A, B) per ResBlock, conv1_1 has only B
@@ -145,20 +165,11 @@ struct ss_ctx {
     double t_in = 0, t_plan = 0, t_sync = 0, t_loop = 0;
     // progress of the run in flight (ss_run_begin_tracked): an event behind every pass and the windows done at it
     std::vector<hipEvent_t> pass_ev; std::vector<int64_t> pass_done_at; size_t pass_reported = 0; int64_t progress_reported = 0, track_total = 0;
-    // activation workspace for `ws_chunk` windows
-    int ws_chunk = 0;
-    std::map<std::string, void*> act;                     // tensor name -> first byte (high plane in f16x2 mode) inside d_act_arena
-    void* d_act_arena = nullptr;
-    int64_t lo_delta = 0;                                 // f16x2: byte distance from a tensor's high plane to its low plane
-    float* d_feat = nullptr; float* d_flat_part = nullptr;
-    int64_t ws_bytes = 0;
-    // second lane of a run with several passes: its own workspace and stream, so that a pass's launches fill the CUs that the other lane's
-    // launch tails leave idle (engine.hip run_begin); allocated when such a run first asks, dropped with the workspace
-    struct Lane {
-        int chunk = 0; int64_t bytes = 0;
-        std::map<std::string, void*> act; void* arena = nullptr; int64_t lo_delta = 0; float* feat = nullptr; float* flat = nullptr;
-        hipStream_t stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    } lane1;
+    // ws[0]: the main workspace (passes on `stream`).  ws[1]: the second lane of a run with several passes, with a stream of its own, so
+    // that a pass's launches fill the CUs that the other lane's launch tails leave idle (engine.hip run_begin); allocated when such a run
+    // first asks, dropped with the main workspace
+    ss::Workspace ws[2];
+    hipStream_t lane_stream = nullptr; hipEvent_t lane_ev_in = nullptr, lane_ev_out = nullptr;
     int* d_range_flag = nullptr; int* h_range_flag = nullptr;    // f16x2: set by the conv kernels when a value does not fit an f16
     int fail_alloc_after = -1;                            // dev build's test hook (ss_debug_fail_workspace_alloc): the n-th workspace allocation from now fails
     bool split_range_ok = true;                           // f16x2: cleared while packing when a folded weight has no f16 representation
@@ -166,8 +177,8 @@ struct ss_ctx {
     // SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c
     std::map<std::string, std::vector<int>> act_exp;
     // the last network pass, for the dev build's ss_debug_activation (kept in both builds: the units shared by the two libraries must see
-    // one layout of this struct): its windows, the tensors it wrote, whether it ran on the second lane's workspace
-    int dbg_n = 0; bool dbg_lane1 = false; std::set<std::string> dbg_written;
+    // one layout of this struct): its windows, the index of the workspace it ran on, the tensors it wrote
+    int dbg_n = 0, dbg_ws = 0; std::set<std::string> dbg_written;
 
     // arena
     float* d_arena = nullptr; size_t arena_cap = 0, arena_used = 0;
@@ -204,10 +215,10 @@ struct ss_ctx {
 
 namespace ss {
 
-struct ScopedLaunch {      // times one launch with HIP events on the context's stream when profiling
-    ss_ctx* c; int sid; hipEvent_t a = nullptr, b = nullptr;
+struct ScopedLaunch {      // times one launch with HIP events on its stream when profiling
+    ss_ctx* c; hipStream_t stream; int sid; hipEvent_t a = nullptr, b = nullptr;
     // issued_macs: multiply-adds of the form that runs, when it differs from the layer's algorithmic count (< 0: flops / 2)
-    ScopedLaunch(ss_ctx* c_, const std::string& name, double flops, double bytes, double issued_macs = -1.0);
+    ScopedLaunch(ss_ctx* c_, hipStream_t stream_, const std::string& name, double flops, double bytes, double issued_macs = -1.0);
     ~ScopedLaunch();
 };
 void resolve_events(ss_ctx* c);
@@ -243,9 +254,15 @@ int ensure(ss_ctx* c, T** p, size_t* cap, size_t need_elems, bool keep = false) 
 int build_tables(ss_ctx* c, const Blob& bl);
 int build_model(ss_ctx* c, const Blob& bl);
 // engine.hip
-int ensure_workspace(ss_ctx* c, int n);
-void free_workspace(ss_ctx* c);
-int forward_chunk(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out);
+int ensure_workspace(ss_ctx* c, int n);                  // the main workspace holds >= n windows, or an error
+void free_workspace(ss_ctx* c);                           // both workspaces
+// one pass: n <= ws.chunk windows at signal + d_winoff[0..n) through the network, on `stream` (d_logits == nullptr: the front end only)
+int forward_chunk(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec);
+// f16x2's range flag (no-ops in the other modes): clear it on a stream; enqueue its copy to the pinned word; test that word after the
+// stream has been synchronised.  The caller reports SS_ERR_RANGE in its own words.
+int range_clear(ss_ctx* c, hipStream_t stream);
+int range_fetch(ss_ctx* c, hipStream_t stream);
+inline bool range_left(const ss_ctx* c) { return c->h_range_flag && *c->h_range_flag; }
 int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const volatile int* stop_flag,
               const float* ext_logits = nullptr, int64_t ext_windows = 0);
 int run_poll(ss_ctx* c, ss_progress_fn progress, void* user, int block, const volatile int* stop_flag);

@@ -35,18 +35,28 @@ static int stat_id(ss_ctx* c, const std::string& name) {
     return (int)c->stats.size() - 1;
 }
 
-ScopedLaunch::ScopedLaunch(ss_ctx* c_, const std::string& name, double flops, double bytes, double issued_macs) : c(c_) {
+ScopedLaunch::ScopedLaunch(ss_ctx* c_, hipStream_t stream_, const std::string& name, double flops, double bytes, double issued_macs)
+    : c(c_), stream(stream_) {
     sid = stat_id(c, name);
     c->stats[sid].launches++; c->stats[sid].flops += flops; c->stats[sid].bytes += bytes;
     c->stats[sid].issued += 2.0 * (c->prec == kF16x2 ? 3.0 : 1.0) * (issued_macs >= 0 ? issued_macs : flops / 2.0);
     if (c->profile) {
         auto get = [&]() { hipEvent_t e; if (!c->evpool.empty()) { e = c->evpool.back(); c->evpool.pop_back(); } else hipEventCreate(&e); return e; };
         a = get(); b = get();
-        hipEventRecord(a, c->stream);
+        hipEventRecord(a, stream);
     }
 }
 ScopedLaunch::~ScopedLaunch() {
-    if (c->profile) { hipEventRecord(b, c->stream); c->pending.push_back({sid, a, b}); }
+    if (c->profile) { hipEventRecord(b, stream); c->pending.push_back({sid, a, b}); }
+}
+
+int range_clear(ss_ctx* c, hipStream_t stream) {
+    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, stream));
+    return SS_OK;
+}
+int range_fetch(ss_ctx* c, hipStream_t stream) {
+    if (c->d_range_flag) HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, stream));
+    return SS_OK;
 }
 
 void resolve_events(ss_ctx* c) {
@@ -61,32 +71,21 @@ void resolve_events(ss_ctx* c) {
 // ------------------------------------------------------------------------------------------------------
 // activation workspace: NHWC tensors for `n` windows.  Every tensor is preceded by a 256-byte zero header (conv4.hip reads it
 // for out-of-image patch pieces).  f16x2 mode keeps two planes per tensor (high and low halves of every value, both f16) in two
-// arenas of identical layout, so that one byte distance (ss_ctx::lo_delta) leads from any high plane to its low plane.
+// arenas of identical layout, so that one byte distance (Workspace::lo_delta) leads from any high plane to its low plane.
 // ------------------------------------------------------------------------------------------------------
 static constexpr size_t kActHeader = 256;
 
-static void free_lane1(ss_ctx* c) {
-    ss_ctx::Lane& L = c->lane1;
-    L.chunk = 0; L.bytes = 0; L.act.clear(); L.lo_delta = 0;
-    void* arena = L.arena; float* feat = L.feat; float* fp = L.flat;
-    L.arena = nullptr; L.feat = nullptr; L.flat = nullptr;
-    if (arena) hipFree(arena);
-    if (feat) hipFree(feat);
-    if (fp) hipFree(fp);
+static void free_ws(Workspace& w) {
+    // pointers are cleared BEFORE anything else can fail: a context whose growth failed holds no workspace at all (chunk = 0)
+    // and the next call allocates afresh -- never a stale chunk over freed tensors
+    void* const ps[] = {w.arena, w.feat, w.flat};
+    w = Workspace();
+    for (void* p : ps) if (p) hipFree(p);
 }
 
 void free_workspace(ss_ctx* c) {
-    // pointers are cleared BEFORE anything else can fail: a context whose growth failed holds no workspace at all (ws_chunk = 0)
-    // and the next call allocates afresh -- never a stale ws_chunk over freed tensors
-    c->ws_chunk = 0; c->ws_bytes = 0;
-    void* arena = c->d_act_arena; float* feat = c->d_feat; float* fp = c->d_flat_part;
-    c->d_act_arena = nullptr; c->d_feat = nullptr; c->d_flat_part = nullptr; c->lo_delta = 0;
-    c->act.clear();
-    c->dbg_n = 0; c->dbg_lane1 = false; c->dbg_written.clear();
-    if (arena) hipFree(arena);
-    if (feat) hipFree(feat);
-    if (fp) hipFree(fp);
-    free_lane1(c);
+    c->dbg_n = 0; c->dbg_ws = 0; c->dbg_written.clear();
+    for (Workspace& w : c->ws) free_ws(w);
 }
 
 static hipError_t ws_malloc(ss_ctx* c, void** p, size_t bytes) {
@@ -94,9 +93,8 @@ static hipError_t ws_malloc(ss_ctx* c, void** p, size_t bytes) {
     return hipMalloc(p, bytes);
 }
 
-// one workspace for n windows: arena (+ the tensor table), feature and flatten-partial buffers; the zero headers are written on `stream`.
-// On failure everything it allocated is freed again and *what names the step.
-struct WsAlloc { void* arena = nullptr; float* feat = nullptr; float* flat = nullptr; std::map<std::string, void*> act; int64_t lo_delta = 0, bytes = 0; };
+// one workspace for n windows, filled in place: arena (+ the tensor table), feature and flatten-partial buffers; the zero headers are
+// written on `stream`.  On failure everything it allocated is freed again (w is empty) and *what names the step.
 struct WsTensor { const char* n; int H, W, C; };
 static const WsTensor kWsTensors[] = {{"h1", 128, 256, 32}, {"c1", 128, 256, 32}, {"p1", 64, 128, 32}, {"h2", 64, 128, 64}, {"c2", 64, 128, 64},
                                       {"p2", 32, 64, 64},   {"h3", 32, 64, 96},   {"c3", 32, 64, 96},  {"p3", 16, 32, 96},  {"h4", 16, 32, 128},
@@ -107,63 +105,59 @@ static const WsTensor kWsTensors[] = {{"h1", 128, 256, 32}, {"c1", 128, 256, 32}
                                       // r = residual projection written by A launches that keep it (conv6, conv8, the spec head; every block in fp32 / f16x2)
                                       {"r2", 64, 128, 64},  {"r3", 32, 64, 96},   {"r4", 16, 32, 128}, {"rb", 8, 16, 128},  {"re", 8, 16, 128},
                                       {"r6", 16, 32, 96},   {"r7", 32, 64, 64},   {"r8", 64, 128, 32}, {"r9", 128, 256, 32}, {"rs", 128, 256, 32}};
-static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, WsAlloc& w, std::string& what) {
+static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, Workspace& w, std::string& what) {
     const size_t es = c->prec == kFp32 ? 4 : 2;
-    using T = WsTensor;
-    const auto& ts = kWsTensors;
     // one arena, one size (the spec head's tensors included): the workspace is sized once per context and chunk
     size_t total = 0;
     std::vector<size_t> offs;
-    for (const T& t : ts) {
+    for (const WsTensor& t : kWsTensors) {
         offs.push_back(total + kActHeader);
         total += kActHeader + (((size_t)n * t.H * t.W * t.C * es + 255) & ~(size_t)255);
     }
     const int planes = c->prec == kF16x2 ? 2 : 1;
-    auto drop = [&]() { if (w.arena) hipFree(w.arena); if (w.feat) hipFree(w.feat); if (w.flat) hipFree(w.flat); w = WsAlloc(); };
+    const size_t feat_b = (size_t)n * 128 * 256 * 4, flat_b = (size_t)n * 64 * 4 * 256 * 4;
     hipError_t e = ws_malloc(c, &w.arena, total * planes);
-    if (e != hipSuccess) { what = "activation workspace (" + std::to_string(total * planes >> 20) + " MiB)"; drop(); return e; }
-    if ((e = ws_malloc(c, (void**)&w.feat, (size_t)n * 128 * 256 * 4)) != hipSuccess ||
-        (e = ws_malloc(c, (void**)&w.flat, (size_t)n * 64 * 4 * 256 * 4)) != hipSuccess) { what = "activation workspace"; drop(); return e; }
+    if (e != hipSuccess) { what = "activation workspace (" + std::to_string(total * planes >> 20) + " MiB)"; free_ws(w); return e; }
+    if ((e = ws_malloc(c, (void**)&w.feat, feat_b)) != hipSuccess || (e = ws_malloc(c, (void**)&w.flat, flat_b)) != hipSuccess) {
+        what = "activation workspace"; free_ws(w); return e;
+    }
     for (int pl = 0; pl < planes; ++pl)
-        for (size_t i = 0; i < offs.size(); ++i) {
-            e = hipMemsetAsync((char*)w.arena + pl * total + offs[i] - kActHeader, 0, kActHeader, stream);
-            if (e != hipSuccess) { what = "hipMemsetAsync"; drop(); return e; }
+        for (size_t off : offs) {
+            e = hipMemsetAsync((char*)w.arena + pl * total + off - kActHeader, 0, kActHeader, stream);
+            if (e != hipSuccess) { what = "hipMemsetAsync"; free_ws(w); return e; }
         }
-    for (size_t i = 0; i < offs.size(); ++i) w.act[ts[i].n] = (char*)w.arena + offs[i];
+    for (size_t i = 0; i < offs.size(); ++i) w.act[kWsTensors[i].n] = (char*)w.arena + offs[i];
     w.lo_delta = planes == 2 ? (int64_t)total : 0;
-    w.bytes = (int64_t)(total * planes + (size_t)n * 128 * 256 * 4 + (size_t)n * 64 * 4 * 256 * 4);
+    w.bytes = (int64_t)(total * planes + feat_b + flat_b);
+    w.chunk = n;
     return hipSuccess;
 }
 
 int ensure_workspace(ss_ctx* c, int n) {
-    if (n <= c->ws_chunk) return SS_OK;
+    if (n <= c->ws[0].chunk) return SS_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->lane1.stream) HIPCHK(c, hipStreamSynchronize(c->lane1.stream));
+    if (c->lane_stream) HIPCHK(c, hipStreamSynchronize(c->lane_stream));
     free_workspace(c);
-    WsAlloc w; std::string what;
-    const hipError_t e = alloc_ws(c, n, c->stream, w, what);
+    std::string what;
+    const hipError_t e = alloc_ws(c, n, c->stream, c->ws[0], what);
     if (e != hipSuccess) return fail(c, what == "hipMemsetAsync" ? SS_ERR_HIP : SS_ERR_NOMEM, what + ": " + hipGetErrorString(e));
-    c->d_act_arena = w.arena; c->d_feat = w.feat; c->d_flat_part = w.flat; c->act = std::move(w.act); c->lo_delta = w.lo_delta;
-    c->ws_bytes = w.bytes;
-    c->ws_chunk = n;
     return SS_OK;
 }
 
 // the second lane for passes of n windows; false (and no lane) when the memory is not there -- the run then uses one lane
-static bool ensure_lane1(ss_ctx* c, int n) {
-    ss_ctx::Lane& L = c->lane1;
-    if (L.chunk >= n) return true;
-    if (!L.stream) {
-        if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess) { L.stream = nullptr; return false; }
-        if (hipEventCreateWithFlags(&L.ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&L.ev_out, hipEventDisableTiming) != hipSuccess) return false;
+static bool ensure_lane(ss_ctx* c, int n) {
+    Workspace& w = c->ws[1];
+    if (w.chunk >= n) return true;
+    if (!c->lane_stream) {
+        if (hipStreamCreateWithFlags(&c->lane_stream, hipStreamNonBlocking) != hipSuccess) { c->lane_stream = nullptr; return false; }
+        if (hipEventCreateWithFlags(&c->lane_ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->lane_ev_out, hipEventDisableTiming) != hipSuccess) return false;
     }
-    hipStreamSynchronize(L.stream);
-    free_lane1(c);
+    hipStreamSynchronize(c->lane_stream);
+    free_ws(w);
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (int64_t)free_b < c->ws_bytes + ((int64_t)4 << 30)) return false;   // (leave room for the caller's buffers)
-    WsAlloc w; std::string what;
-    if (alloc_ws(c, n, L.stream, w, what) != hipSuccess) { (void)hipGetLastError(); return false; }
-    L.arena = w.arena; L.feat = w.feat; L.flat = w.flat; L.act = std::move(w.act); L.lo_delta = w.lo_delta; L.bytes = w.bytes; L.chunk = n;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (int64_t)free_b < c->ws[0].bytes + ((int64_t)4 << 30)) return false;   // (leave room for the caller's buffers)
+    std::string what;
+    if (alloc_ws(c, n, c->lane_stream, w, what) != hipSuccess) { (void)hipGetLastError(); return false; }
     return true;
 }
 
@@ -182,16 +176,16 @@ static int base_dbg() {
 struct StageStamps {
     void* d_st = nullptr;
     static constexpr size_t st_bytes = (size_t)4096 * 8 * 16 * 4;
-    int begin(ss_ctx* c, const std::string& name, ConvArgs& a) {
+    int begin(ss_ctx* c, hipStream_t stream, const std::string& name, ConvArgs& a) {
         const char* want = getenv("SOFTSPOKEN_STAMP_LAYER");
-        if (want && name == want) { HIPCHK(c, hipMalloc(&d_st, st_bytes)); HIPCHK(c, hipMemsetAsync(d_st, 0, st_bytes, c->stream)); a.stamps = d_st; }
+        if (want && name == want) { HIPCHK(c, hipMalloc(&d_st, st_bytes)); HIPCHK(c, hipMemsetAsync(d_st, 0, st_bytes, stream)); a.stamps = d_st; }
         return SS_OK;
     }
-    int end(ss_ctx* c, const std::string& name, int n) {
+    int end(ss_ctx* c, hipStream_t stream, const std::string& name, int n) {
         if (!d_st) return SS_OK;
         std::vector<uint32_t> h(st_bytes / 4);
-        HIPCHK(c, hipMemcpyAsync(h.data(), d_st, st_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(h.data(), d_st, st_bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(c, hipStreamSynchronize(stream));
         double sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stages = 0; int waves = 0;
         for (size_t w = 0; w < h.size() / 16; ++w) if (h[w * 16 + 5]) {
             ++waves; stages += h[w * 16 + 5];
@@ -205,33 +199,52 @@ struct StageStamps {
         return SS_OK;
     }
 };
+#else
+struct StageStamps {
+    int begin(ss_ctx*, hipStream_t, const std::string&, ConvArgs&) { return SS_OK; }
+    int end(ss_ctx*, hipStream_t, const std::string&, int) { return SS_OK; }
+};
 #endif
 
+// One conv launch with its bookkeeping: the stat entry "<instantiation as rocprofv3 prints it>/<layer>", the dev build's stage stamps
+// when this layer's are asked for, the launch on `stream`, its error.  issued: as ScopedLaunch's issued_macs.
+template <typename Launch>
+static int conv_launch(ss_ctx* c, hipStream_t stream, const char* variant, const std::string& layer, ConvArgs& a, double flops, double bytes,
+                       double issued, Launch&& launch) {
+    StageStamps stamps;
+    if (int rc = stamps.begin(c, stream, layer, a)) return rc;
+    {
+        ScopedLaunch sl(c, stream, std::string(variant) + "/" + layer, flops, bytes, issued);
+        HIPCHK(c, launch(a));
+    }
+    return stamps.end(c, stream, layer, a.N);
+}
+
 // the tensors a pass writes, by name (dev build: ss_debug_activation refuses the others)
-static void mark_written(ss_ctx* c, const void* p) {
+static void mark_written(ss_ctx* c, const Workspace& ws, const void* p) {
 #ifdef SS_DEVBUILD
     if (!p) return;
-    for (const auto& kv : c->act)
+    for (const auto& kv : ws.act)
         if (kv.second == p) { c->dbg_written.insert(kv.first); return; }
 #else
-    (void)c; (void)p;
+    (void)c; (void)ws; (void)p;
 #endif
 }
 
 // One launch of a ResBlock half.  A launches (r_out) compute h and the residual projection r from the block input
 // (x0 [+ upsampled x1]); B launches (r_in) compute the block output from h and add r.
-static int run_conv2(ss_ctx* c, const ConvPlan& p, int n, const void* x0, const void* x1, void* out, void* pool, void* r_out,
-                     const void* r_in, const float* feat, const ConvExtra& ex = ConvExtra()) {
+static int run_conv2(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPlan& p, int n, const void* x0, const void* x1, void* out, void* pool,
+                     void* r_out, const void* r_in, const float* feat, const ConvExtra& ex = ConvExtra()) {
     const bool isA = r_out != nullptr;
-    if (ex.store_out) mark_written(c, out);
-    mark_written(c, pool); mark_written(c, r_out);
+    if (ex.store_out) mark_written(c, ws, out);
+    mark_written(c, ws, pool); mark_written(c, ws, r_out);
     ConvArgs a{};
     a.first_w = ex.first_w; a.first_b = ex.first_b; a.flat_w = ex.flat_w; a.flat_w4 = ex.flat_w4; a.flat_part = ex.flat_part; a.store_out = ex.store_out;
     a.src0 = x0; a.src1 = x1; a.wpk = p.d_w2; a.bias = p.d_bias2;
     a.res_out = r_out; a.res_bias = p.d_res_bias; a.res_in = r_in;
     a.rank1_src = feat; a.rank1_w = p.d_rank1; a.out = out; a.pool_out = pool;
     a.N = n; a.H = p.H; a.W = p.W; a.Cout = p.Cout; a.relu = 1;
-    a.lo_delta = c->lo_delta; a.range_flag = c->d_range_flag;
+    a.lo_delta = ws.lo_delta; a.range_flag = c->d_range_flag;
     if (isA) { a.C0 = p.C0; a.C1 = p.C1; } else { a.C0 = p.Cout; a.C1 = 0; }       // B's 3x3 input is h
     a.dbg = base_dbg();
     const double cin = a.C0 + a.C1;
@@ -240,90 +253,57 @@ static int run_conv2(ss_ctx* c, const ConvPlan& p, int n, const void* x0, const 
     const double es = c->prec == kBf16 ? 2 : 4;           // bytes per stored activation value (f16x2: two f16 planes)
     // (the fused conv1_1 launch reads the fp32 features, not an h1 tensor: h1 only exists in LDS)
     const double bytes = (double)n * p.H * p.W * es * ((ex.first_w ? 4.0 / es : a.C0) + a.C1 / 4.0 + (ex.flat_part && !ex.store_out ? 0 : p.Cout) + (isA || r_in ? p.Cout : 0) + (pool ? p.Cout / 4.0 : 0));
-    // stat name = "<instantiation as rocprofv3 prints it>/<layer>"
     const int prec4 = c->prec == kF16x2 ? 2 : 1;
-#ifdef SS_DEVBUILD
-    StageStamps stamps;
-    if (int rcs = stamps.begin(c, p.name, a)) return rcs;
-    auto print_stamps = [&]() -> int { return stamps.end(c, p.name, n); };
-#endif
-    if (isA && c->prec == kF16x2 && p.d_w_upsr) {  // decoder A launches: the upsampled input half at low resolution (conv4_ups.hip, ring form)
+    const int cus = c->num_cus;
+    // (FLOPs booked: the layer's algorithmic ones, as for every launch; issued < 0: the same multiply-adds are issued)
+    auto go = [&](const char* variant, ConvArgs& x, double issued, auto&& launch) { return conv_launch(c, stream, variant, p.name, x, 2.0 * macs, bytes, issued, launch); };
+    // the decoder forms with the upsampled input half at low resolution issue 9 C0 + 4 C1 multiply-adds per output value (+ cin: the 1x1 projection)
+    const double issued_ups = (double)n * p.H * p.W * p.Cout * (9.0 * p.C0 + 4.0 * p.C1 + cin);
+    if (isA && c->prec == kF16x2 && p.d_w_upsr) {  // decoder A launches: conv4_ups.hip, ring form
         ConvArgs au = a;
         au.wpk = p.d_w_upsr;
-        if (conv_upsr_supports(au, c->num_cus)) {
-            // (FLOPs booked: the layer's algorithmic ones, as for every launch; this form issues 9 C0 + 4 C1 multiply-adds per output value)
-            {
-                const double issued = (double)n * p.H * p.W * p.Cout * (9.0 * p.C0 + 4.0 * p.C1 + cin);     // (+ cin: the 1x1 projection)
-                ScopedLaunch sl(c, std::string(conv_upsr_variant()) + "/" + p.name, 2.0 * macs, bytes, issued);
-                HIPCHK(c, launch_conv3x3_upsr(au, c->num_cus, c->stream));
-            }
-#ifdef SS_DEVBUILD
-            return print_stamps();
-#else
-            return SS_OK;
-#endif
-        }
+        if (conv_upsr_supports(au, cus)) return go(conv_upsr_variant(), au, issued_ups, [&](ConvArgs& x) { return launch_conv3x3_upsr(x, cus, stream); });
     }
     if (isA && c->prec == kFp32 && p.d_w_ups32 && x1) {   // fp32 decoder A launches: the same idea on the fp32 matrix instruction (conv2_ups.hip)
         ConvArgs au = a;
         au.wpk = p.d_w_ups32;
-        const int mtw = dev_env("SOFTSPOKEN_UPS32_MTW", 2) == 2 && p.ups32_nt < 3 ? 2 : 1;
-        if (conv_ups32_supports(au, p.ups32_nt, mtw, c->num_cus)) {
-            const double issued = (double)n * p.H * p.W * p.Cout * (9.0 * p.C0 + 4.0 * p.C1 + cin);
-            ScopedLaunch sl(c, std::string(conv_ups32_variant(p.ups32_nt, mtw)) + "/" + p.name, 2.0 * macs, bytes, issued);
-            HIPCHK(c, launch_conv3x3_ups32(au, p.ups32_nt, mtw, c->num_cus, c->stream));
-            return SS_OK;
-        }
+        const int nt = p.ups32_nt, mtw = dev_env("SOFTSPOKEN_UPS32_MTW", 2) == 2 && nt < 3 ? 2 : 1;
+        if (conv_ups32_supports(au, nt, mtw, cus))
+            return go(conv_ups32_variant(nt, mtw), au, issued_ups, [&](ConvArgs& x) { return launch_conv3x3_ups32(x, nt, mtw, cus, stream); });
     }
     if (c->prec == kF16x2 && ex.first_w && p.d_w_s16 && dev_env("SOFTSPOKEN_C1S", 1)) {   // conv1_1: the row-streaming form (conv1s.hip)
         ConvArgs as = a;
-                const int form = dev_env("SOFTSPOKEN_C1S_FORM", 16) == 32 && p.d_w_s1 ? 32 : 16;     // (32: the development build's other form)
+        const int form = dev_env("SOFTSPOKEN_C1S_FORM", 16) == 32 && p.d_w_s1 ? 32 : 16;     // (32: the development build's other form)
         as.wpk = form == 16 ? p.d_w_s16 : p.d_w_s1;
         as.relu = 1 | (dev_env("SOFTSPOKEN_C1S_ABLATE", 0) << 4);    // (dev build, timing only: 1 no stores, 2 no second-conv products, 4 no pooled rows)
         as.plain = p.s1_range_proven && dev_env("SOFTSPOKEN_C1S_TRACK", 0) == 0;
         if (conv1_stream_supports(as)) {
-#ifdef SS_DEVBUILD
-            as.stamps = a.stamps;
-#endif
-            {
-                ScopedLaunch sl(c, std::string(conv1_stream_variant(as, form)) + "/" + p.name, 2.0 * macs, bytes);
-                HIPCHK(c, launch_conv1_stream(as, form, dev_env("SOFTSPOKEN_C1S_ROWS", 32), c->num_cus, c->stream));
-            }
-#ifdef SS_DEVBUILD
-            if (dev_env("SOFTSPOKEN_C1S", 1) != 2) return print_stamps();    // (2: conv4.hip's form runs as well, behind it -- an A/B aid)
-#else
-            return SS_OK;
-#endif
+            const int rows = dev_env("SOFTSPOKEN_C1S_ROWS", 32);
+            if (int rc = go(conv1_stream_variant(as, form), as, -1.0, [&](ConvArgs& x) { return launch_conv1_stream(x, form, rows, cus, stream); })) return rc;
+            if (dev_env("SOFTSPOKEN_C1S", 1) != 2) return SS_OK;     // (dev build, 2: conv4.hip's form runs as well, behind it -- an A/B aid)
         }
     }
-    if (c->prec != kFp32 && dev_env("SOFTSPOKEN_CONV4", 1) && conv_v4_supports(a, p.NT, c->num_cus, prec4)) {   // conv4.hip: bf16 / f16x2 launches
-        {
-            ScopedLaunch sl(c, std::string(conv_v4_variant(a, p.NT, c->num_cus, prec4)) + "/" + p.name, 2.0 * macs, bytes);
-            HIPCHK(c, launch_conv3x3_v4(a, p.NT, c->num_cus, prec4, c->stream));
-        }
-#ifdef SS_DEVBUILD
-        { const int rcs = print_stamps(); if (rcs) return rcs; }
-#endif
-        if (ex.flat_part) c->flat_groups = conv_v4_flat_groups();
+    if (c->prec != kFp32 && dev_env("SOFTSPOKEN_CONV4", 1) && conv_v4_supports(a, p.NT, cus, prec4)) {   // conv4.hip: bf16 / f16x2 launches
+        if (int rc = go(conv_v4_variant(a, p.NT, cus, prec4), a, -1.0, [&](ConvArgs& x) { return launch_conv3x3_v4(x, p.NT, cus, prec4, stream); })) return rc;
+        if (ex.flat_part) ws.flat_groups = conv_v4_flat_groups();
         return SS_OK;
     }
     if (c->prec == kF16x2) return fail(c, SS_ERR_STATE, "f16x2: no kernel form for " + p.name);
-    if (ex.flat_part) c->flat_groups = conv_v2_flat_groups(c->bf16);
-    ScopedLaunch sl(c, std::string(conv_v2_variant(a, c->bf16, p.NT, c->num_cus)) + "/" + p.name, 2.0 * macs, bytes);
-    HIPCHK(c, launch_conv3x3_v2(a, c->bf16, p.NT, c->num_cus, c->stream));
-    return SS_OK;
+    if (ex.flat_part) ws.flat_groups = conv_v2_flat_groups(c->bf16);
+    return go(conv_v2_variant(a, c->bf16, p.NT, cus), a, -1.0, [&](ConvArgs& x) { return launch_conv3x3_v2(x, c->bf16, p.NT, cus, stream); });
 }
 
 // A ResBlock in the "projection in B" form (conv4.hip RP; bf16, and f16x2 for the blocks conv4.hip has the form for): A writes h
 // alone, B reads h and the centre pixels of the block input.  Returns 1 when conv4.hip has no instantiation for this block (the
 // caller then uses A + r / B).
-static int run_block_proj(ss_ctx* c, const ConvPlan& pa, const ConvPlan& pb, int n, const void* x0, const void* x1, void* h, void* out,
-                          void* pool, const ConvExtra& ex = ConvExtra()) {
+static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPlan& pa, const ConvPlan& pb, int n, const void* x0, const void* x1,
+                          void* h, void* out, void* pool, const ConvExtra& ex = ConvExtra()) {
     if ((c->prec != kBf16 && c->prec != kF16x2) || !pa.d_w3 || !pb.d_proj) return 1;
     const int prec4 = c->prec == kF16x2 ? 2 : 1;
+    const int cus = c->num_cus;
     const double es = c->prec == kBf16 ? 2 : 4;
     ConvArgs a{}, b{};
-    a.lo_delta = b.lo_delta = c->lo_delta; a.range_flag = b.range_flag = c->d_range_flag;
+    a.lo_delta = b.lo_delta = ws.lo_delta; a.range_flag = b.range_flag = c->d_range_flag;
     a.src0 = x0; a.src1 = x1; a.wpk = pa.d_w3; a.bias = pa.d_bias2; a.out = h; a.plain = 1;
     a.N = n; a.H = pa.H; a.W = pa.W; a.Cout = pa.Cout; a.C0 = pa.C0; a.C1 = pa.C1; a.relu = 1;
     b.src0 = h; b.wpk = pb.d_w2; b.bias = pb.d_bias3; b.out = out; b.pool_out = pool;
@@ -335,78 +315,59 @@ static int run_block_proj(ss_ctx* c, const ConvPlan& pa, const ConvPlan& pb, int
     // instead of nine on those channels) where that form exists -- conv9_1.A
     ConvArgs au = a;
     au.wpk = pa.d_w_ups;
-    const bool ups = c->prec == kF16x2 && pa.d_w_ups && x1 && conv_ups_supports(au, c->num_cus);
-    if ((!ups && !conv_v4_supports(a, pa.NT, c->num_cus, prec4)) || !conv_v4_supports(b, pb.NT, c->num_cus, prec4)) return 1;
-    mark_written(c, h); mark_written(c, pool);
-    if (ex.store_out) mark_written(c, out);
+    const bool ups = c->prec == kF16x2 && pa.d_w_ups && x1 && conv_ups_supports(au, cus);
+    if ((!ups && !conv_v4_supports(a, pa.NT, cus, prec4)) || !conv_v4_supports(b, pb.NT, cus, prec4)) return 1;
+    mark_written(c, ws, h); mark_written(c, ws, pool);
+    if (ex.store_out) mark_written(c, ws, out);
     const double px = (double)n * pa.H * pa.W, cin = pa.C0 + pa.C1, cinb = pa.C0 + pa.C1 / 4.0;
+    const double flops_a = 2.0 * px * pa.Cout * 9.0 * cin, bytes_a = px * es * (cinb + pa.Cout);
+    auto v4 = [&](const ConvPlan& p, ConvArgs& x, double flops, double bytes) {
+        return conv_launch(c, stream, conv_v4_variant(x, p.NT, cus, prec4), p.name, x, flops, bytes, -1.0,
+                           [&](ConvArgs& y) { return launch_conv3x3_v4(y, p.NT, cus, prec4, stream); });
+    };
+    int rc;
     if (ups) {
         // FLOPs booked are the layer's algorithmic ones (2 x multiply-adds of the 3x3 as the reference computes it); this
-        // form issues 9 C0 + 4 C1 multiply-adds per output value instead of 9 (C0 + C1)
-        ScopedLaunch sl(c, std::string(conv_ups_variant()) + "/" + pa.name, 2.0 * px * pa.Cout * 9.0 * cin, px * es * (cinb + pa.Cout),
-                        px * pa.Cout * (9.0 * pa.C0 + 4.0 * pa.C1));
-        HIPCHK(c, launch_conv3x3_ups(au, c->num_cus, c->stream));
-    } else {
-#ifdef SS_DEVBUILD
-        StageStamps st;
-        if (int rcs = st.begin(c, pa.name, a)) return rcs;
-#endif
-        {
-            ScopedLaunch sl(c, std::string(conv_v4_variant(a, pa.NT, c->num_cus, prec4)) + "/" + pa.name, 2.0 * px * pa.Cout * 9.0 * cin, px * es * (cinb + pa.Cout));
-            HIPCHK(c, launch_conv3x3_v4(a, pa.NT, c->num_cus, prec4, c->stream));
-        }
-#ifdef SS_DEVBUILD
-        if (int rcs = st.end(c, pa.name, n)) return rcs;
-#endif
-    }
-    {
-        const double flops = 2.0 * px * pb.Cout * (9.0 * pb.Cout + cin) + (ex.flat_part ? 2.0 * px * 32 * 4 : 0.0);
-        const double bytes = px * es * (pb.Cout + cinb + (ex.flat_part && !ex.store_out ? 0 : pb.Cout) + (pool ? pb.Cout / 4.0 : 0));
-#ifdef SS_DEVBUILD
-        StageStamps st;
-        if (int rcs = st.begin(c, pb.name, b)) return rcs;
-#endif
-        {
-            ScopedLaunch sl(c, std::string(conv_v4_variant(b, pb.NT, c->num_cus, prec4)) + "/" + pb.name, flops, bytes);
-            HIPCHK(c, launch_conv3x3_v4(b, pb.NT, c->num_cus, prec4, c->stream));
-        }
-#ifdef SS_DEVBUILD
-        if (int rcs = st.end(c, pb.name, n)) return rcs;
-#endif
-        if (ex.flat_part) c->flat_groups = conv_v4_flat_groups();
-    }
+        // form issues 9 C0 + 4 C1 multiply-adds per output value instead of 9 (C0 + C1).  (It takes no stage stamps.)
+        ScopedLaunch sl(c, stream, std::string(conv_ups_variant()) + "/" + pa.name, flops_a, bytes_a, px * pa.Cout * (9.0 * pa.C0 + 4.0 * pa.C1));
+        HIPCHK(c, launch_conv3x3_ups(au, cus, stream));
+    } else if ((rc = v4(pa, a, flops_a, bytes_a))) return rc;
+    const double flops_b = 2.0 * px * pb.Cout * (9.0 * pb.Cout + cin) + (ex.flat_part ? 2.0 * px * 32 * 4 : 0.0);
+    const double bytes_b = px * es * (pb.Cout + cinb + (ex.flat_part && !ex.store_out ? 0 : pb.Cout) + (pool ? pb.Cout / 4.0 : 0));
+    if ((rc = v4(pb, b, flops_b, bytes_b))) return rc;
+    if (ex.flat_part) ws.flat_groups = conv_v4_flat_groups();
     return SS_OK;
 }
 
-static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out);
+static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec);
 
-// SpecUNet_2D.forward (pytorch_neural_nets.py:142-197) for n <= ws_chunk windows whose arena offsets are d_winoff[0..n)
-int forward_chunk(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out) {
+// SpecUNet_2D.forward (pytorch_neural_nets.py:142-197) for n <= ws.chunk windows that start at signal + d_winoff[0..n)
+int forward_chunk(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec) {
 #ifdef SS_DEVBUILD
-    // the pass's record for ss_debug_activation: on the second lane the context's tensor table is the lane's (engine.hip run_begin)
-    c->dbg_written.clear(); c->dbg_n = n;
-    c->dbg_lane1 = c->act.empty() || c->act.at("h1") != (char*)c->d_act_arena + kActHeader;
-    if (!d_feat_out) c->dbg_written.insert("feat");
-    const int rc = forward_chunk_(c, d_winoff, n, d_logits, d_spec, d_feat_out);
+    // the pass's record for ss_debug_activation
+    c->dbg_written.clear(); c->dbg_n = n; c->dbg_ws = (int)(&ws - c->ws);
+    c->dbg_written.insert("feat");
+    if (d_logits) c->dbg_written.insert("flat_part");
+    const int rc = forward_chunk_(c, ws, stream, signal, d_winoff, n, d_logits, d_spec);
     if (rc) { c->dbg_written.clear(); c->dbg_n = 0; }
     return rc;
 #else
-    return forward_chunk_(c, d_winoff, n, d_logits, d_spec, d_feat_out);
+    return forward_chunk_(c, ws, stream, signal, d_winoff, n, d_logits, d_spec);
 #endif
 }
 
-static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_logits, float* d_spec, float* d_feat_out) {
+static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec) {
     FrontendTables tb{c->d_pretw, c->d_w2048, c->d_mel_start, c->d_mel_count, c->d_mel_off, c->d_mel_w, c->mel_nw, c->d_mel_wp, dev_env("SOFTSPOKEN_FEDBG", 0),
                       c->d_win2, c->d_twt, c->d_wkt, c->d_mel_wq, c->d_mel_p0};
-    float* feat = d_feat_out ? d_feat_out : c->d_feat;
+    float* const feat = ws.feat;
     {
-        ScopedLaunch sl(c, "frontend", 0.0, (double)n * (66150.0 * 4 + 128.0 * 256 * 4));
-        HIPCHK(c, launch_frontend(c->d_arena, d_winoff, n, tb, feat, c->num_cus, c->stream));
+        ScopedLaunch sl(c, stream, "frontend", 0.0, (double)n * (66150.0 * 4 + 128.0 * 256 * 4));
+        HIPCHK(c, launch_frontend(signal, d_winoff, n, tb, feat, c->num_cus, stream));
     }
     if (!d_logits) return SS_OK;
     auto A = [&](const char* k) -> void* {
-        auto it = c->act.find(k);
-        return it == c->act.end() ? nullptr : it->second;      // (never null after ensure_workspace; a null would be refused by the launch checks)
+        auto it = ws.act.find(k);
+        return it == ws.act.end() ? nullptr : it->second;      // (never null after ensure_workspace; a null would be refused by the launch checks)
     };
     const double es = c->prec == kBf16 ? 2 : 4;
     const std::vector<ConvPlan>& cv = c->convs;
@@ -415,7 +376,7 @@ static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_lo
     {   // conv1_1: first conv produced in the loader (bf16: MFMA on bf16 features; f16x2: three MFMAs on f16 halves), 1 -> 32 residual
         // from the features (bf16: one more MFMA on hi/lo halves; f16x2: a rank-1 fp32 term in the epilogue; fp32: conv2.hip's own form)
         ConvExtra ex; ex.first_w = c->d_first_w; ex.first_b = c->d_first_b;
-        RC2(run_conv2(c, cv[i++], n, nullptr, nullptr, A("c1"), A("p1"), nullptr, nullptr, feat, ex));
+        RC2(run_conv2(c, ws, stream, cv[i++], n, nullptr, nullptr, A("c1"), A("p1"), nullptr, nullptr, feat, ex));
     }
     struct Blk { const char *x0, *x1, *h, *r, *y, *pool; };
     const Blk blks[] = {{"p1", nullptr, "h2", "r2", "c2", "p2"},   {"p2", nullptr, "h3", "r3", "c3", "p3"},
@@ -428,38 +389,35 @@ static int forward_chunk_(ss_ctx* c, const int64_t* d_winoff, int n, float* d_lo
         // Blocks whose input is narrower than their output (encoder) move fewer bytes when B recomputes the 1x1 projection from
         // the block input than when A writes r and B reads it back; conv4.hip has that form for the blocks where it pays.
         if (proj) {
-            rc = run_block_proj(c, cv[i], cv[i + 1], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), A(b.y), b.pool ? A(b.pool) : nullptr);
+            rc = run_block_proj(c, ws, stream, cv[i], cv[i + 1], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), A(b.y), b.pool ? A(b.pool) : nullptr);
             if (rc == SS_OK) { i += 2; continue; }
             if (rc != 1) return rc;
         }
-        RC2(run_conv2(c, cv[i], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), nullptr, A(b.r), nullptr, nullptr));
-        RC2(run_conv2(c, cv[i + 1], n, A(b.h), nullptr, A(b.y), b.pool ? A(b.pool) : nullptr, nullptr, A(b.r), nullptr));
+        RC2(run_conv2(c, ws, stream, cv[i], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), nullptr, A(b.r), nullptr, nullptr));
+        RC2(run_conv2(c, ws, stream, cv[i + 1], n, A(b.h), nullptr, A(b.y), b.pool ? A(b.pool) : nullptr, nullptr, A(b.r), nullptr));
         i += 2;
     }
     {   // conv9_1 on cat[conv1, up(conv8)]; conv_flatten rides in B's epilogue (c9 itself only when the spec head runs)
-        ConvExtra ex; ex.flat_w = c->d_flat_frag; ex.flat_w4 = c->d_flat_frag4; ex.flat_part = c->d_flat_part; ex.store_out = d_spec ? 1 : 0;
+        ConvExtra ex; ex.flat_w = c->d_flat_frag; ex.flat_w4 = c->d_flat_frag4; ex.flat_part = ws.flat; ex.store_out = d_spec ? 1 : 0;
         rc = 1;
-        if (proj && (rc = run_block_proj(c, cv[i], cv[i + 1], n, A("c1"), A("c8"), A("h9"), A("c9"), nullptr, ex)) != 1) {
+        if (proj && (rc = run_block_proj(c, ws, stream, cv[i], cv[i + 1], n, A("c1"), A("c8"), A("h9"), A("c9"), nullptr, ex)) != 1) {
             if (rc) return rc;
         } else {
-            RC2(run_conv2(c, cv[i], n, A("c1"), A("c8"), A("h9"), nullptr, A("r9"), nullptr, nullptr));
-            RC2(run_conv2(c, cv[i + 1], n, A("h9"), nullptr, A("c9"), nullptr, nullptr, A("r9"), nullptr, ex));
+            RC2(run_conv2(c, ws, stream, cv[i], n, A("c1"), A("c8"), A("h9"), nullptr, A("r9"), nullptr, nullptr));
+            RC2(run_conv2(c, ws, stream, cv[i + 1], n, A("h9"), nullptr, A("c9"), nullptr, nullptr, A("r9"), nullptr, ex));
         }
         i += 2;
     }
-#ifdef SS_DEVBUILD
-    c->dbg_written.insert("flat_part");
-#endif
     if (d_spec) {   // dead head of the reference (worker.py:78-79 drops it), on request
-        RC2(run_conv2(c, cv[i], n, A("c9"), nullptr, A("hs"), nullptr, A("rs"), nullptr, nullptr));
-        RC2(run_conv2(c, cv[i + 1], n, A("hs"), nullptr, A("s9"), nullptr, nullptr, A("rs"), nullptr));
-        ScopedLaunch sl(c, "spec_tail", 2.0 * n * 32768 * 64, (double)n * 32768 * (32 * es + 8));
-        HIPCHK(c, launch_spec_tail(A("s9"), c->lo_delta, c->d_spec_w, c->d_spec_b, d_spec, n, (int)c->prec, c->stream));
+        RC2(run_conv2(c, ws, stream, cv[i], n, A("c9"), nullptr, A("hs"), nullptr, A("rs"), nullptr, nullptr));
+        RC2(run_conv2(c, ws, stream, cv[i + 1], n, A("hs"), nullptr, A("s9"), nullptr, nullptr, A("rs"), nullptr));
+        ScopedLaunch sl(c, stream, "spec_tail", 2.0 * n * 32768 * 64, (double)n * 32768 * (32 * es + 8));
+        HIPCHK(c, launch_spec_tail(A("s9"), ws.lo_delta, c->d_spec_w, c->d_spec_b, d_spec, n, (int)c->prec, stream));
     }
 #undef RC2
-    const int groups = c->flat_groups;
-    ScopedLaunch sl(c, "mask_head_parts", 0.0, (double)n * (groups * 4 * 256 * 4 + 1024));
-    HIPCHK(c, launch_mask_head_parts(c->d_flat_part, groups, c->d_flat_b, c->head, d_logits, n, c->stream));
+    const int groups = ws.flat_groups;
+    ScopedLaunch sl(c, stream, "mask_head_parts", 0.0, (double)n * (groups * 4 * 256 * 4 + 1024));
+    HIPCHK(c, launch_mask_head_parts(ws.flat, groups, c->d_flat_b, c->head, d_logits, n, stream));
     return SS_OK;
 }
 
@@ -469,12 +427,13 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
                      int32_t* exponents) {
     if (!c || !name) return fail(c, SS_ERR_ARG, "ss_debug_activation: null argument");
     const std::string k = name;
+    const Workspace& w = c->ws[0];
     int H = 128, W = 256, C = 1, es = 4;
     const void* base = nullptr;
     if (k == "feat") {
-        base = c->d_feat;
+        base = w.feat;
     } else if (k == "flat_part") {                        // conv_flatten's row-group partial sums [n][groups][4][256] (heads.hip)
-        base = c->d_flat_part; H = std::max(c->flat_groups, 1); W = 4; C = 256;
+        base = w.flat; H = std::max(w.flat_groups, 1); W = 4; C = 256;
     } else {
         const WsTensor* t = nullptr;
         for (const WsTensor& e : kWsTensors) if (k == e.n) t = &e;
@@ -488,12 +447,12 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
     }
     if (!out) return SS_OK;                               // (shape and exponents are the model's: no pass needed)
     if (c->run_pending) return fail(c, SS_ERR_STATE, "ss_debug_activation: a run is in flight");
-    if (!c->ws_chunk || c->act.empty()) return fail(c, SS_ERR_STATE, "ss_debug_activation: the context has no workspace");
-    if (c->dbg_lane1) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass ran on the second lane's workspace");
+    if (!w.chunk || w.act.empty()) return fail(c, SS_ERR_STATE, "ss_debug_activation: the context has no workspace");
+    if (c->dbg_ws != 0) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass ran on the second lane's workspace");
     if (!c->dbg_written.count(k)) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass did not write " + k);
     // (after the staleness test: SS_ERR_ARG for an r tensor tells the caller that the pass ran the block as A + r / B)
     if (k[0] == 'r') return fail(c, SS_ERR_ARG, "ss_debug_activation: " + k + " is stored in MFMA fragment order; check it through its B launch");
-    if (k != "feat" && k != "flat_part") base = c->act.at(k);
+    if (k != "feat" && k != "flat_part") base = w.act.at(k);
     const bool two = k != "feat" && k != "flat_part" && c->prec == kF16x2;
     if (plane < 0 || plane > (two ? 1 : 0)) return fail(c, SS_ERR_ARG, "ss_debug_activation: no plane " + std::to_string(plane) + " in " + k);
     if (first < 0 || n < 0 || first + n > c->dbg_n)
@@ -504,7 +463,7 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
     if (need) {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        const char* src = (const char*)base + (plane ? c->lo_delta : 0) + first * per;
+        const char* src = (const char*)base + (plane ? w.lo_delta : 0) + first * per;
         HIPCHK(c, hipMemcpy(out, src, (size_t)need, hipMemcpyDeviceToHost));
     }
     return SS_OK;
@@ -524,7 +483,7 @@ int upload_winoff(ss_ctx* c, const std::vector<int64_t>& off) {
 // enqueued by run_begin; run_end waits for it; the regions are found on the host when first asked for.
 // ------------------------------------------------------------------------------------------------------
 // device side of the post-processing (NNDetector.py:153-190 averaging, the comparison of :118): logits of `af` files -> two bit masks
-static int enqueue_post(ss_ctx* c, const std::vector<AvgFile>& af, int64_t total, int64_t total_bins, int max_bins, double threshold) {
+static int enqueue_post(ss_ctx* c, const std::vector<AvgFile>& af, int64_t total_bins) {
     int rc;
     if ((rc = ensure(c, &c->d_avgfiles, &c->avgfiles_cap, af.size()))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_avgfiles, af.data(), af.size() * sizeof(AvgFile), hipMemcpyHostToDevice, c->stream));   // af lives in the context
@@ -547,22 +506,21 @@ static int enqueue_post(ss_ctx* c, const std::vector<AvgFile>& af, int64_t total
         HIPCHK(c, hipHostMalloc((void**)&c->h_cov, cap * 8, hipHostMallocDefault));
         c->hmask_cap = cap;
     }
-    (void)total; (void)max_bins; (void)threshold;
     return SS_OK;
 }
 
 static int launch_post(ss_ctx* c, size_t n_files, int64_t total, int64_t total_bins, int max_bins, double threshold) {
     const size_t words = (size_t)((total_bins + 255) / 256) * 4 + 1;
     {
-        ScopedLaunch sl(c, "average", 0.0, (double)total * 1024 * 5 + (double)total_bins * 12);
+        ScopedLaunch sl(c, c->stream, "average", 0.0, (double)total * 1024 * 5 + (double)total_bins * 12);
         HIPCHK(c, launch_average(c->d_logits, c->d_avgfiles, (int)n_files, c->d_starts, c->d_avg, c->d_count, max_bins, c->stream));
     }
     if (total_bins) {
-        ScopedLaunch sl(c, "bin_masks", 0.0, (double)total_bins * 12 + (double)words * 16);
+        ScopedLaunch sl(c, c->stream, "bin_masks", 0.0, (double)total_bins * 12 + (double)words * 16);
         HIPCHK(c, launch_bin_masks(c->d_avg, c->d_count, total_bins, threshold, c->d_above, c->d_cov, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_run1, c->stream));
-    if (c->d_range_flag) HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = range_fetch(c, c->stream)) return rc;
     if (total_bins) {
         HIPCHK(c, hipMemcpyAsync(c->h_above, c->d_above, words * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_cov, c->d_cov, words * 8, hipMemcpyDeviceToHost, c->stream));
@@ -643,12 +601,12 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
         if (ext_logits) HIPCHK(c, hipMemcpyAsync(c->d_logits, ext_logits, (size_t)total * 1024, hipMemcpyHostToDevice, c->stream));
         if ((rc = upload_winoff(c, off))) return rc;      // (synchronises: off, starts and the caller's logits are free again)
     }
-    if ((rc = enqueue_post(c, af, total, total_bins, max_bins, threshold))) return rc;
+    if ((rc = enqueue_post(c, af, total_bins))) return rc;
     c->total_bins = total_bins; c->avg_on_host = false; ++c->begin_gen;
     c->t_plan = now_ms();
     c->t_sync = c->t_plan;
     HIPCHK(c, hipEventRecord(c->ev_run0, c->stream));
-    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    if ((rc = range_clear(c, c->stream))) return rc;
     c->pass_done_at.clear(); c->pass_reported = 0; c->progress_reported = 0; c->track_total = total;
     if (!ext_logits) {
         // passes of equal size (2560 windows: 3 x 854, not 1024 + 1024 + 512: a short last pass has the launch overheads and tail
@@ -660,30 +618,26 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
         // its last workgroups leave CUs idle until the slowest is done; with another pass's launches queued beside it those CUs take the
         // other lane's workgroups (two processes sharing the card showed it: 30.6 k audio-s/s against 29.6 k).  Same kernels, same
         // results; not with per-launch profiling (the launch times would overlap) and not when the memory for the lane is not there.
-        ss_ctx::Lane& L = c->lane1;
         // Off in the product build (SOFTSPOKEN_LANES=2 in the dev build): under rocprofv3 the overlapped launches' durations no longer are
         // the per-launch times the bench line's roofline is computed from (its profiled passes run one lane), and + 0.5-1 % is not worth two
         // sets of numbers that disagree.
-        const bool two = n_pass >= 2 && !c->profile && dev_env("SOFTSPOKEN_LANES", 1) >= 2 && ensure_lane1(c, ch);
-        struct LaneSwap {                                 // the context's workspace fields <-> the lane's
-            ss_ctx* c; ss_ctx::Lane& L; bool on = false;
-            void flip() { std::swap(c->act, L.act); std::swap(c->d_feat, L.feat); std::swap(c->d_flat_part, L.flat); std::swap(c->lo_delta, L.lo_delta); std::swap(c->stream, L.stream); on = !on; }
-            ~LaneSwap() { if (on) flip(); }
-        } lane{c, L};
-        if (two) { HIPCHK(c, hipEventRecord(L.ev_in, c->stream)); HIPCHK(c, hipStreamWaitEvent(L.stream, L.ev_in, 0)); }
+        const bool two = n_pass >= 2 && !c->profile && dev_env("SOFTSPOKEN_LANES", 1) >= 2 && ensure_lane(c, ch);
+        // (the lane starts behind what the main stream holds so far: the uploads, the cleared range flag)
+        if (two) { HIPCHK(c, hipEventRecord(c->lane_ev_in, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->lane_stream, c->lane_ev_in, 0)); }
         // ---- windows in chunks, across file boundaries (worker.py:71-84 batches per file of 32) ----
-        // track: an event behind every pass, from which run_poll reports the progress (below).  The passes keep their full size and
-        // are all enqueued here; nothing waits for the device.
+        // track: an event behind every pass, on that pass's stream, from which run_poll reports the progress (below).  The passes keep
+        // their full size and are all enqueued here; nothing waits for the device.
         int64_t pass_no = 0;
         for (int64_t i0 = 0; i0 < total; i0 += ch, ++pass_no) {
             if (stop_flag && *stop_flag) {
                 hipStreamSynchronize(c->stream);
-                if (two) hipStreamSynchronize(L.stream);   // (one of the two is the lane's, whichever way the fields are flipped)
+                if (two) hipStreamSynchronize(c->lane_stream);
                 return fail(c, SS_ERR_STOPPED, "stopped on request");
             }
             const int m = (int)std::min<int64_t>(ch, total - i0);
-            if (two && ((pass_no & 1) != 0) != lane.on) lane.flip();
-            if ((rc = forward_chunk(c, c->d_winoff + i0, m, c->d_logits + (size_t)i0 * 256, nullptr, nullptr))) return rc;
+            const int lane = two ? (int)(pass_no & 1) : 0;
+            const hipStream_t st = lane ? c->lane_stream : c->stream;
+            if ((rc = forward_chunk(c, c->ws[lane], st, c->d_arena, c->d_winoff + i0, m, c->d_logits + (size_t)i0 * 256, nullptr))) return rc;
             if (track) {
                 const size_t k = c->pass_done_at.size();
                 if (k >= c->pass_ev.size()) {
@@ -691,12 +645,12 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
                     HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
                     c->pass_ev.push_back(e);
                 }
-                HIPCHK(c, hipEventRecord(c->pass_ev[k], c->stream));
+                HIPCHK(c, hipEventRecord(c->pass_ev[k], st));
                 c->pass_done_at.push_back(i0 + m);
             }
         }
-        if (lane.on) lane.flip();
-        if (two) { HIPCHK(c, hipEventRecord(L.ev_out, L.stream)); HIPCHK(c, hipStreamWaitEvent(c->stream, L.ev_out, 0)); }
+        // (the main stream's averaging below reads both lanes' logits)
+        if (two) { HIPCHK(c, hipEventRecord(c->lane_ev_out, c->lane_stream)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->lane_ev_out, 0)); }
     }
     // ---- overlap averaging on the device (NNDetector.py:153-190), then two bits per bin ----
     if ((rc = launch_post(c, af.size(), total, total_bins, max_bins, threshold))) return rc;
@@ -715,7 +669,7 @@ int run_end(ss_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_run0, c->ev_run1) == hipSuccess) c->last_run_ms = ms; }
     resolve_events(c);
-    if (c->h_range_flag && *c->h_range_flag)
+    if (range_left(c))
         return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; run this checkpoint with the fp32 mode");
     const double t_d2h = now_ms();
     // the run's results leave the working set: file bookkeeping is copied, the mask buffers change places with the previous result's
@@ -744,7 +698,6 @@ void ensure_regions(ss_ctx* c) {
     if (c->res_regions) return;
     const bool timing = dev_env("SOFTSPOKEN_TIMING", 0) != 0;
     const double t0 = now_ms();
-    const double break_s = c->res_brk;
     const unsigned long long* AB = c->r_above;
     const unsigned long long* CV = c->r_cov;
     // first set bit of (word(k) for k >= pos) in [pos, hi), or hi
@@ -771,20 +724,17 @@ void ensure_regions(ss_ctx* c) {
     for (ss_ctx::ResFile& f : c->res_files) {
         f.regions.clear();
         const int64_t lo = f.bin_off, hi = f.bin_off + f.n_bins;
-        bool have = false;
-        ss_region cur{0, 0};
+        RunMerger mg; mg.brk = c->res_brk;
         int64_t pos = lo;
         while (pos < hi) {
             const int64_t first = next_bit(above_w, pos, hi);
             if (first == hi) break;
             const int64_t q = next_bit(closer_w, first + 1, hi);              // the covered bin that ends the run, or the file's end
             const int64_t last = prev_above(first, q);                         // (>= first: `first` itself is above)
-            const double s0 = bin_time(first - lo), e0 = bin_time(last - lo);
-            if (have && s0 - cur.end <= break_s) cur.end = e0;
-            else { if (have) f.regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0}); cur.start = s0; cur.end = e0; have = true; }
+            mg.add(first - lo, last - lo, f.regions);
             pos = q + 1;
         }
-        if (have) f.regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0});
+        mg.flush(f.regions);
     }
     c->res_regions = true;
     if (timing) fprintf(stderr, "[ss_run] regions %.3f ms\n", now_ms() - t0);
@@ -792,7 +742,7 @@ void ensure_regions(ss_ctx* c) {
 
 // The merged table of files [first, first + n_ch) of the ended run (ss_get_regions_union): a bin is above when it is above on any of the
 // channels -- the OR of their `above` bits at their bit offsets --, and closes a run when it is covered and above on none; then the run
-// lengths, bin times and gap merge of ensure_regions.  bins (optional): first and last bin of every merged region.
+// lengths; bin times and gap merge by the same RunMerger.  bins (optional): first and last bin of every merged region.
 int union_regions(ss_ctx* c, int first, int n_ch, std::vector<ss_region>& regions, std::vector<int64_t>* bins) {
     regions.clear();
     if (bins) bins->clear();
@@ -803,19 +753,9 @@ int union_regions(ss_ctx* c, int first, int n_ch, std::vector<ss_region>& region
     for (int k = 1; k < n_ch; ++k)
         if (c->res_files[first + k].n_bins != f0.n_bins) return fail(c, SS_ERR_ARG, "ss_get_regions_union: the files differ in their number of bins");
     auto bit = [](const unsigned long long* w, int64_t j) { return (w[j >> 6] >> (j & 63)) & 1ull; };
-    const double break_s = c->res_brk;
-    bool open = false, have = false;
-    int64_t run0 = 0, run1 = 0, reg0 = 0, reg1 = 0;
-    ss_region cur{0, 0};
-    auto close_run = [&]() {
-        const double s0 = bin_time(run0), e0 = bin_time(run1);
-        if (have && s0 - cur.end <= break_s) { cur.end = e0; reg1 = run1; }
-        else {
-            if (have) { regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0}); if (bins) { bins->push_back(reg0); bins->push_back(reg1); } }
-            cur.start = s0; cur.end = e0; reg0 = run0; reg1 = run1; have = true;
-        }
-        open = false;
-    };
+    RunMerger mg; mg.brk = c->res_brk;
+    bool open = false;
+    int64_t run0 = 0, run1 = 0;
     for (int64_t j = 0; j < f0.n_bins; ++j) {
         bool above = false, covered = false;
         for (int k = 0; k < n_ch; ++k) {
@@ -824,10 +764,10 @@ int union_regions(ss_ctx* c, int first, int n_ch, std::vector<ss_region>& region
             covered = covered || bit(c->r_cov, at);
         }
         if (above) { if (!open) { run0 = j; open = true; } run1 = j; }
-        else if (covered && open) close_run();
+        else if (covered && open) { mg.add(run0, run1, regions, bins); open = false; }
     }
-    if (open) close_run();
-    if (have) { regions.push_back(ss_region{cur.start - 3.0, cur.end - 3.0}); if (bins) { bins->push_back(reg0); bins->push_back(reg1); } }
+    if (open) mg.add(run0, run1, regions, bins);
+    mg.flush(regions, bins);
     return SS_OK;
 }
 

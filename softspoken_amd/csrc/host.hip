@@ -142,32 +142,39 @@ double ss::bin_time(int64_t idx) {    // float(f"{idx / (256 / 3):.4f}")  (NNDet
     return strtod(buf, nullptr);
 }
 
+// NNDetector.py:131-141 (gap merge), then worker.py:100 (the 3 s of padding in front leave the times)
+void ss::RunMerger::add(int64_t first_bin, int64_t last_bin, std::vector<ss_region>& out, std::vector<int64_t>* bins) {
+    const double s0 = bin_time(first_bin), e0 = bin_time(last_bin);
+    if (have && s0 - cur.end <= brk) { cur.end = e0; reg1 = last_bin; return; }
+    flush(out, bins);
+    cur = ss_region{s0, e0}; reg0 = first_bin; reg1 = last_bin; have = true;
+}
+void ss::RunMerger::flush(std::vector<ss_region>& out, std::vector<int64_t>* bins) {
+    if (!have) return;
+    out.push_back(ss_region{cur.start - 3.0, cur.end - 3.0});
+    if (bins) { bins->push_back(reg0); bins->push_back(reg1); }
+    have = false;
+}
+
 // NNDetector.py:112-141 then worker.py:100
 extern "C" int ss_find_regions(const double* avg, const int64_t* bin_idx, int64_t n, double threshold, double break_s,
                                ss_region* out, int64_t cap, int64_t* n_out) {
     if ((n > 0 && (!avg || !bin_idx)) || !n_out) return fail(nullptr, SS_ERR_ARG, "ss_find_regions: null argument");
     // a run's start/end are the time strings of its first/last bin: format only at run boundaries
-    std::vector<std::pair<double, double>> runs;
+    std::vector<ss_region> merged;
+    RunMerger mg; mg.brk = break_s;
     bool open = false; int64_t first = 0, last = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (avg[i] > threshold) {
             if (!open) { first = bin_idx[i]; open = true; }
             last = bin_idx[i];
-        } else if (open) { runs.emplace_back(bin_time(first), bin_time(last)); open = false; }
+        } else if (open) { mg.add(first, last, merged); open = false; }
     }
-    if (open) runs.emplace_back(bin_time(first), bin_time(last));
-    std::vector<std::pair<double, double>> merged;
-    if (!runs.empty()) {
-        auto cur = runs[0];
-        for (size_t i = 1; i < runs.size(); ++i) {
-            if (runs[i].first - cur.second <= break_s) cur.second = runs[i].second;
-            else { merged.push_back(cur); cur = runs[i]; }
-        }
-        merged.push_back(cur);
-    }
+    if (open) mg.add(first, last, merged);
+    mg.flush(merged);
     *n_out = (int64_t)merged.size();
     if ((int64_t)merged.size() > cap) return fail(nullptr, SS_ERR_CAPACITY, "ss_find_regions: output capacity too small");
-    for (size_t i = 0; i < merged.size(); ++i) { out[i].start = merged[i].first - 3.0; out[i].end = merged[i].second - 3.0; }
+    if (!merged.empty()) memcpy(out, merged.data(), merged.size() * sizeof(ss_region));
     return SS_OK;
 }
 

@@ -420,11 +420,11 @@ static int sep_run_maps(ss_ctx* c, int fid, int64_t W, const std::vector<std::pa
     if ((rc = ensure(c, &c->d_logits, &c->logits_cap, (size_t)ch * 256))) return rc;
     if ((rc = ensure(c, &c->d_spec, &c->spec_cap, (size_t)ch * 2 * 32768))) return rc;
     c->logits_valid = false;
-    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    if ((rc = range_clear(c, c->stream))) return rc;
     for (int p0 = 0; p0 < nw; p0 += ch) {
         const int m = std::min(ch, nw - p0);
-        if ((rc = forward_chunk(c, c->d_winoff + p0, m, c->d_logits, c->d_spec, nullptr))) return rc;
-        ScopedLaunch sl(c, "sep_accumulate_kernel", 256.0 * ncb * 6, (double)ncb * 256 * 16);
+        if ((rc = forward_chunk(c, c->ws[0], c->stream, c->d_arena, c->d_winoff + p0, m, c->d_logits, c->d_spec))) return rc;
+        ScopedLaunch sl(c, c->stream, "sep_accumulate_kernel", 256.0 * ncb * 6, (double)ncb * 256 * 16);
         hipLaunchKernelGGL(sep_accumulate_kernel, dim3((unsigned)((ncb + 255) / 256), 256), dim3(256), 0, c->stream, c->d_spec, p0, m, st.d_slot,
                            (int)W, st.d_cbin, ncb, st.d_sum, st.d_count);
         HIPCHK(c, hipGetLastError());
@@ -432,15 +432,15 @@ static int sep_run_maps(ss_ctx* c, int fid, int64_t W, const std::vector<std::pa
     {
         const int sp = params ? params->speech_channel : 1;
         const double mg = params ? params->min_gain : 0.0;
-        ScopedLaunch sl(c, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)));
+        ScopedLaunch sl(c, c->stream, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)));
         hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256)), dim3(256), 0, c->stream, st.d_sum, st.d_count, ncb,
                            st.d_map, params ? st.d_gain : nullptr, sp, mg);
         HIPCHK(c, hipGetLastError());
     }
     if (c->d_range_flag) {
-        HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = range_fetch(c, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (*c->h_range_flag)
+        if (range_left(c))
             return fail(c, SS_ERR_RANGE, "f16x2: an activation of the spec head left the f16 range (|x| > 65504) or was not finite; run this file with the fp32 mode");
     }
     return SS_OK;
@@ -503,7 +503,7 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
     const size_t total = (size_t)frames * ch;
     if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
     {   // the transcode of the whole file: what ss_silence_pcm writes outside its ranges
-        ScopedLaunch sl(c, "sep_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
+        ScopedLaunch sl(c, c->stream, "sep_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
         HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, nullptr, 0, c->d_sil_out, c->stream));
     }
     if (!pl.ranges.empty()) {
@@ -566,13 +566,13 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
         for (const Chunk& ck : chunks) {
             {
                 const double lg = std::log2((double)N);
-                ScopedLaunch sl(c, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
+                ScopedLaunch sl(c, c->stream, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
                                 (double)ck.nrec * npairs * N * (2.0 * pcm_bytes_per_sample(format) + 8.0));
                 HIPCHK(c, launch_sep_stft_n(N, c->d_pcm, format, ch, frames, st.d_frames + ck.rec0, (int)ck.nrec, hop, st.d_gain, *tb, gain_hi,
                                             st.d_fout, c->stream));
             }
             const int64_t all = ck.total * ch;
-            ScopedLaunch sl(c, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
+            ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
             const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
             hipLaunchKernelGGL(sep_blend_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch, st.d_segs + ck.seg0,
                                (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_sil_out);

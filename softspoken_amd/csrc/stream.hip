@@ -23,7 +23,7 @@ int64_t win_start_bin(int64_t i) { return (512 * i + 5) / 10; }     // round(51.
 
 struct StreamRec {
     int format = 0, sr = 0, ch = 0;
-    double thr = 0, brk = 0;
+    double thr = 0;                                   // (break_s: mg.brk)
     int L = 1, M = 1, half = 0;                       // 22 050 Hz: decoded straight into the signal (no resampler)
     float* d_taps = nullptr;
     int64_t frames_in = 0;                            // frames decoded so far
@@ -36,8 +36,8 @@ struct StreamRec {
     bool on_host = false; std::vector<float> h_mono, h_sig, h_lg;
     int64_t m_next = 0;                               // next resampled output (index into the unpadded signal)
     int64_t win_run = 0, bins_done = 0;
-    // region walk (engine.hip ensure_regions, carried across steps)
-    bool have = false, run_open = false; ss_region cur{0, 0}; int64_t run_first = 0, run_last = 0;
+    // region walk, carried across steps: the open run of bins above the threshold, and the merge of the closed ones
+    bool run_open = false; int64_t run_first = 0, run_last = 0; RunMerger mg;
     // the last step's results
     std::vector<ss_region> r_out; std::vector<double> a_out; std::vector<int64_t> b_out;
 };
@@ -175,7 +175,7 @@ extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double thre
     if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
     hipSetDevice(c->device);
     StreamRec s;
-    s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.brk = break_s;
+    s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.mg.brk = break_s;
     if ((rc = init_rates(c, s))) return rc;
     StreamSet& S = streams_of(c);
     *id = S.next_id++;
@@ -247,9 +247,9 @@ extern "C" int ss_stream_avg(ss_ctx* c, int id, double* avg, int64_t* bin_idx, i
 // ------------------------------------------------------------------------------------------------------
 // the step
 // ------------------------------------------------------------------------------------------------------
-// the region walk of engine.hip ensure_regions over bins in order, one bin at a time: a run opens at a bin above the threshold and
-// closes at the next covered bin that is not; runs merge while s0 - cur.end <= break_s.  A merged region is final once a covered
-// bin lies more than break_s after its end (bin times never decrease, so no later run can merge into it).
+// the region walk over bins in order, one bin at a time: a run opens at a bin above the threshold and closes at the next covered bin
+// that is not; closed runs go through the stream's RunMerger.  A merged region is final once a covered bin lies more than brk after
+// its end (bin times never decrease, so no later run can merge into it).
 static void walk_bin(StreamRec& s, int64_t j, unsigned char f) {
     if (!(f & 1)) return;                                 // not covered: absent from the reference's series
     if (f & 2) {
@@ -257,24 +257,13 @@ static void walk_bin(StreamRec& s, int64_t j, unsigned char f) {
         s.run_last = j;
         return;
     }
-    if (s.run_open) {
-        const double s0 = bin_time(s.run_first), e0 = bin_time(s.run_last);
-        if (s.have && s0 - s.cur.end <= s.brk) s.cur.end = e0;
-        else { if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.cur.start = s0; s.cur.end = e0; s.have = true; }
-        s.run_open = false;
-    }
-    if (s.have && bin_time(j) - s.cur.end > s.brk) { s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.have = false; }
+    if (s.run_open) { s.mg.add(s.run_first, s.run_last, s.r_out); s.run_open = false; }
+    if (s.mg.have && bin_time(j) - s.mg.cur.end > s.mg.brk) s.mg.flush(s.r_out);
 }
 
 static void finish_regions(StreamRec& s) {
-    if (s.run_open) {
-        const double s0 = bin_time(s.run_first), e0 = bin_time(s.run_last);
-        if (s.have && s0 - s.cur.end <= s.brk) s.cur.end = e0;
-        else { if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0}); s.cur.start = s0; s.cur.end = e0; s.have = true; }
-        s.run_open = false;
-    }
-    if (s.have) s.r_out.push_back(ss_region{s.cur.start - 3.0, s.cur.end - 3.0});
-    s.have = false;
+    if (s.run_open) { s.mg.add(s.run_first, s.run_last, s.r_out); s.run_open = false; }
+    s.mg.flush(s.r_out);
 }
 
 static int ensure_pinned(ss_ctx* c, unsigned char** p, size_t* cap, size_t need) {
@@ -285,14 +274,6 @@ static int ensure_pinned(ss_ctx* c, unsigned char** p, size_t* cap, size_t need)
     *cap = nc;
     return SS_OK;
 }
-
-namespace {
-struct ArenaSwap {                                        // forward_chunk reads windows from c->d_arena: the stream arena for the passes
-    ss_ctx* c; float* saved;
-    ArenaSwap(ss_ctx* c_, float* a) : c(c_), saved(c_->d_arena) { c->d_arena = a; }
-    ~ArenaSwap() { c->d_arena = saved; }
-};
-}  // namespace
 
 extern "C" int ss_stream_step(ss_ctx* c) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
@@ -405,37 +386,36 @@ extern "C" int ss_stream_step(ss_ctx* c) {
     // ---- device work ----
     HIPCHK(c, hipMemcpyAsync(S.d_up, S.h_up, at, hipMemcpyHostToDevice, c->stream));
     {
-        ScopedLaunch sl(c, "stream_copy", 0.0, 8.0 * max_copy * pre.size());
+        ScopedLaunch sl(c, c->stream, "stream_copy", 0.0, 8.0 * max_copy * pre.size());
         HIPCHK(c, launch_stream_copy((const StreamCopy*)(S.d_up + o_pre), (int)pre.size(), max_copy, c->stream));
     }
     {
-        ScopedLaunch sl(c, "stream_decode", 0.0, 0.0);
+        ScopedLaunch sl(c, c->stream, "stream_decode", 0.0, 0.0);
         HIPCHK(c, launch_stream_decode(S.d_up, (const StreamDecode*)(S.d_up + o_dec), (int)dec.size(), max_dec, c->stream));
     }
     {
-        ScopedLaunch sl(c, "stream_resample", 0.0, 0.0);
+        ScopedLaunch sl(c, c->stream, "stream_resample", 0.0, 0.0);
         HIPCHK(c, launch_stream_resample((const StreamResample*)(S.d_up + o_res), (int)res.size(), max_res, c->stream));
     }
-    if (c->d_range_flag) HIPCHK(c, hipMemsetAsync(c->d_range_flag, 0, 4, c->stream));
+    if ((rc = range_clear(c, c->stream))) return rc;
     if (total_w > 0) {
         // passes of equal size, as run_begin
         const int64_t n_pass = std::max<int64_t>(1, (total_w + c->chunk - 1) / c->chunk);
         const int ch = (int)std::max<int64_t>(1, (total_w + n_pass - 1) / n_pass);
         if ((rc = ensure_workspace(c, ch))) return rc;
-        ArenaSwap sw(c, A);
         const int64_t* d_win = (const int64_t*)(S.d_up + o_win);
         for (int64_t i0 = 0; i0 < total_w; i0 += ch) {
             const int m = (int)std::min<int64_t>(ch, total_w - i0);
-            if ((rc = forward_chunk(c, d_win + i0, m, S.d_newlg + (size_t)i0 * 256, nullptr, nullptr))) return rc;
+            if ((rc = forward_chunk(c, c->ws[0], c->stream, A, d_win + i0, m, S.d_newlg + (size_t)i0 * 256, nullptr))) return rc;
         }
     }
     {
         int64_t mx = 0; for (const StreamCopy& p : post) mx = std::max(mx, p.n);
-        ScopedLaunch sl(c, "stream_copy", 0.0, 8.0 * mx * post.size());
+        ScopedLaunch sl(c, c->stream, "stream_copy", 0.0, 8.0 * mx * post.size());
         HIPCHK(c, launch_stream_copy((const StreamCopy*)(S.d_up + o_post), (int)post.size(), mx, c->stream));
     }
     {
-        ScopedLaunch sl(c, "stream_average", 0.0, (double)total_b * 1024 * 5 / 51.2 + (double)total_b * 9);
+        ScopedLaunch sl(c, c->stream, "stream_average", 0.0, (double)total_b * 1024 * 5 / 51.2 + (double)total_b * 9);
         HIPCHK(c, launch_stream_average((const StreamAvg*)(S.d_up + o_avg), (int)avg.size(), max_bins, S.d_avg, S.d_flags, c->stream));
     }
     S.h_avg.resize((size_t)total_b); S.h_flags.resize((size_t)total_b);
@@ -443,10 +423,10 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         HIPCHK(c, hipMemcpyAsync(S.h_avg.data(), S.d_avg, (size_t)total_b * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(S.h_flags.data(), S.d_flags, (size_t)total_b, hipMemcpyDeviceToHost, c->stream));
     }
-    if (c->d_range_flag) HIPCHK(c, hipMemcpyAsync(c->h_range_flag, c->d_range_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = range_fetch(c, c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
-    if (c->h_range_flag && *c->h_range_flag)
+    if (range_left(c))
         return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; nothing of the step is committed: "
                                      "move the streams that had windows in it to an fp32 context (ss_stream_export / ss_stream_import)");
     // ---- commit ----
@@ -508,8 +488,8 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     if (cap < need) return fail(c, SS_ERR_CAPACITY, "ss_stream_export: capacity < " + std::to_string(need));
     ImageHdr h{};
     memcpy(h.magic, kMagic, 8);
-    h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->have; h.run_open = s->run_open;
-    h.thr = s->thr; h.brk = s->brk; h.cur_start = s->cur.start; h.cur_end = s->cur.end;
+    h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->mg.have; h.run_open = s->run_open;
+    h.thr = s->thr; h.brk = s->mg.brk; h.cur_start = s->mg.cur.start; h.cur_end = s->mg.cur.end;
     h.frames_in = s->frames_in; h.staged_frames = s->staged_frames; h.staged_bytes = (int64_t)s->staged.size();
     h.mono_base = s->mono_base; h.mono_n = s->mono_n; h.sig_base = s->sig_base; h.sig_n = s->sig_n; h.lg_w0 = s->lg_w0; h.lg_n = s->lg_n;
     h.m_next = s->m_next; h.win_run = s->win_run; h.bins_done = s->bins_done; h.run_first = s->run_first; h.run_last = s->run_last;
@@ -545,8 +525,8 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
         return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
     hipSetDevice(c->device);
     StreamRec s;
-    s.format = h.format; s.sr = h.sr; s.ch = h.ch; s.closed = h.closed; s.finished = h.finished; s.have = h.have; s.run_open = h.run_open;
-    s.thr = h.thr; s.brk = h.brk; s.cur = ss_region{h.cur_start, h.cur_end};
+    s.format = h.format; s.sr = h.sr; s.ch = h.ch; s.closed = h.closed; s.finished = h.finished; s.mg.have = h.have; s.run_open = h.run_open;
+    s.thr = h.thr; s.mg.brk = h.brk; s.mg.cur = ss_region{h.cur_start, h.cur_end};
     s.frames_in = h.frames_in; s.staged_frames = h.staged_frames;
     s.mono_base = h.mono_base; s.mono_n = h.mono_n; s.sig_base = h.sig_base; s.sig_n = h.sig_n; s.lg_w0 = h.lg_w0; s.lg_n = h.lg_n;
     s.m_next = h.m_next; s.win_run = h.win_run; s.bins_done = h.bins_done; s.run_first = h.run_first; s.run_last = h.run_last;
