@@ -77,15 +77,19 @@ def hann_window_512():
     return torch.hann_window(512).numpy().copy()
 
 
-def mel_filterbank():
-    """HTK mel filterbank (1025, 128) float32, torchaudio melscale_fbanks recipe in float32.
+def mel_edges_hz():
+    """The 130 band edges of the filterbank in Hz, float32: torchaudio's HTK mel points, 700 (10^(m / 2595) - 1) on a float32 linspace.
 
-    Restated from SURVEY.md section 8(a) row A3: f_min 0, f_max 8000, sr 22050, norm None, 'htk'.
-    float32 arithmetic throughout, as torchaudio does it on float32 tensors.
+    float32 arithmetic by numpy, whose float32 `power` is accurate to one ulp and not correctly rounded: at 19 of the 130 edges it is
+    one ulp away from the correctly rounded value, which is what a C library's powf (and torch 2.10's float32 pow on x86) gives.  One
+    ulp of an edge moves 416 of the 1 469 weights by up to 5e-4 relative.  Every synthetic checkpoint and every fixture of this
+    project (tests/golden/mel_tables.npz included) is built on THESE values, so they are the project's statement of the recipe, and
+    weights.hip carries them as a table (kMelEdgesHz) for checkpoints without the `fb` buffer; tests/test_frontend_ref.py holds the
+    table to this function.  Which of the two roundings a given torchaudio build writes into a real checkpoint is not pinned
+    (DESIGN.md section 2, row A3); a real checkpoint carries the buffer, and the buffer is what is used.
     """
     f32 = np.float32
-    n_freqs, n_mels = 1025, 128
-    all_freqs = np.linspace(0.0, float(SR // 2), n_freqs, dtype=np.float64).astype(f32)
+    n_mels = 128
     m_min = 2595.0 * math.log10(1.0 + 0.0 / 700.0)
     m_max = 2595.0 * math.log10(1.0 + 8000.0 / 700.0)
     # torch.linspace(float32): start + step*i for the first half, end - step*(n-1-i) for the second
@@ -95,7 +99,19 @@ def mel_filterbank():
     half = steps // 2
     m_pts = np.where(idx < half, f32(m_min) + step * idx.astype(f32),
                      f32(m_max) - step * (steps - 1 - idx).astype(f32)).astype(f32)
-    f_pts = (f32(700.0) * (np.power(f32(10.0), m_pts / f32(2595.0), dtype=f32) - f32(1.0))).astype(f32)
+    return (f32(700.0) * (np.power(f32(10.0), m_pts / f32(2595.0), dtype=f32) - f32(1.0))).astype(f32)
+
+
+def mel_filterbank():
+    """HTK mel filterbank (1025, 128) float32, torchaudio melscale_fbanks recipe in float32.
+
+    Restated from SURVEY.md section 8(a) row A3: f_min 0, f_max 8000, sr 22050, norm None, 'htk'.
+    float32 arithmetic throughout, as torchaudio does it on float32 tensors.
+    """
+    f32 = np.float32
+    n_freqs = 1025
+    all_freqs = np.linspace(0.0, float(SR // 2), n_freqs, dtype=np.float64).astype(f32)
+    f_pts = mel_edges_hz()
     f_diff = (f_pts[1:] - f_pts[:-1]).astype(f32)
     slopes = (f_pts[None, :] - all_freqs[:, None]).astype(f32)
     down = ((f32(-1.0) * slopes[:, :-2]) / f_diff[:-1]).astype(f32)

@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("SOFTSPOKEN_LIB") or os.path.join(_HERE, "libsoftspoke
 
 SS_OK = 0
 SS_ERR_ARG = 1
+SS_ERR_HIP = 2
+SS_ERR_FORMAT = 3
 SS_ERR_STATE = 4
 SS_ERR_STOPPED = 5
 SS_ERR_NOMEM = 6

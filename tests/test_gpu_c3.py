@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import frontend_ref as FR
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -166,6 +167,10 @@ def test_c5_48k_stereo_recording_front_end(native, blob, sd_torch):
     want = O.mel_features(xw, sd_torch["mel_spectrogram.spectrogram.window"], sd_torch["mel_spectrogram.mel_scale.fb"]).numpy()
     d = np.abs(feats - want)
     assert (d > 1e-5).sum() <= 8 and d.max() < 3e-4
+    # and every value inside the interval bound around the float64 reference (tests/frontend_ref.py)
+    rep = FR.check(feats, xw.numpy(), sd_torch["mel_spectrogram.spectrogram.window"].numpy(), sd_torch["mel_spectrogram.mel_scale.fb"].numpy())
+    print(FR.line("c5", rep))
+    assert rep["over"] == 0 and rep["ratio"] <= 1.0, FR.line("c5", rep)
     # all windows of the file through the front-end alone (the C5 bench leg): same values as the picked ones, no fault at full size
     allf = c.features(fid, starts)
     assert np.array_equal(allf[pick], feats) and np.isfinite(allf).all()

@@ -1,5 +1,6 @@
-"""Every launch of a network pass against a float64 reference computed from the tensors the device stored (tests/layer_ref.py), and the
-spec head end to end against the float64 oracle.
+"""Every launch of a network pass against a float64 reference computed from the tensors the device stored (tests/layer_ref.py; the
+front-end launch: tests/frontend_ref.py, from the padded signal the device holds), and the spec head end to end against the float64
+oracle.
 
 The per-launch checks run in child processes on the development build (SOFTSPOKEN_LIB: ss_debug_activation reads the workspace back).
 A child prints one line per launch,
@@ -25,6 +26,7 @@ torch.set_grad_enabled(False)
 from softspoken_amd import synth, native, checkpoint
 from oracle import oracle_np as O
 import layer_ref as R
+import frontend_ref as FR
 tag, mode, hostile, n_sel, out_npy = {tag!r}, {mode!r}, {hostile!r}, {n_sel!r}, {out_npy!r}
 sd = synth.make_state_dict(0, hostile=hostile)
 sig = np.load({sig_npy!r})
@@ -69,10 +71,9 @@ def check_pass(pname, n, with_spec, spec, logits):
     win = S[-n:]
     feat, _, _ = get("feat", n)
     pad = ctx.read_signal(fid, padded=True)
-    ref_f = O.mel_features(torch.stack([torch.from_numpy(pad[s:s + 66150]) for s in win]),
-                           torch.as_tensor(sd["mel_spectrogram.spectrogram.window"]), torch.as_tensor(sd["mel_spectrogram.mel_scale.fb"]))
-    # front-end: quiet bins may sit one float32 step of log10(x + 1) apart (3e-4, test_gpu_parity.test_frontend_features)
-    report(pname, "frontend", R.ratio_report(feat, ref_f.double().unsqueeze(1), torch.full_like(feat, 3e-4)))
+    # front-end: the float64 reference and interval bound of tests/frontend_ref.py, from the padded signal as the device holds it
+    fe = FR.check(feat[:, 0].numpy(), FR.windows_of(pad, win), sd["mel_spectrogram.spectrogram.window"], sd["mel_spectrogram.mel_scale.fb"])
+    report(pname, "frontend", dict(ratio=fe["ratio"], at=(fe["at"][0], fe["at"][1], fe["at"][2], 0), over=fe["over"]))
     c1, e_c1, d_c1 = get("c1", n)
     p1, e_p1, d_p1 = get("p1", n)
     form = "conv2" if any(k["name"].startswith("conv3x3_v2") and k["name"].endswith("/conv1_1.B") for k in ctx.kernel_stats()) else "conv4"

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import frontend_ref as FR
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +51,10 @@ def test_frontend_features(ctx, c1, gold, sd_torch):
     # quiet bins sit on the float32 grid of log10(x + 1) (steps of ~2.3e-4 near 0):
     # a one-ulp difference in the mel sum may move a bin by one such step; everything else is ~1e-6
     assert (d > TOL_FEAT).sum() <= 4 and d.max() < 3e-4
+    # and every value inside the interval bound around the float64 reference (tests/frontend_ref.py)
+    rep = FR.check(allf, x.numpy(), sd_torch["mel_spectrogram.spectrogram.window"].numpy(), sd_torch["mel_spectrogram.mel_scale.fb"].numpy())
+    print(FR.line("c1", rep))
+    assert rep["over"] == 0 and rep["ratio"] <= 1.0, FR.line("c1", rep)
     assert np.array_equal(allf[0], np.zeros_like(allf[0]))           # leading 3 s pad: exactly zero features
     stats = gf["feat_stats"]
     assert np.abs(allf.mean(axis=(1, 2)) - stats[:, 0]).max() < 1e-6
