@@ -207,12 +207,16 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
 
     const int xcd = blockIdx.x & 7, local = (int)(blockIdx.x >> 3) * NH + half, gper = (int)(gridDim.x >> 3) * NH;
     const int per = (total_tiles + 7) >> 3;
+    // RING: the order of the workgroup's items (kernels.h); the sequential one exists in the development build only (SOFTSPOKEN_ORDER=0)
+#ifdef SS_DEVBUILD
+    const bool order_seq = !(a.dbg & 512);
+#else
+    constexpr bool order_seq = !kOrderSideBySide;
+#endif
     auto tile_of = [&](int loc, int it) -> int {          // tile `it` of the (half-)block with index `loc` on this XCD
-        if constexpr (RING) {                             // every tile of the workgroup walks a position's channel groups in the same order
-            const int total_pos = total_tiles / ngroups, per_pos = (total_pos + 7) >> 3;
-            const int idx = loc + (it / ngroups) * gper;
-            const int pos = xcd * per_pos + idx;
-            return (idx < per_pos && pos < total_pos) ? pos * ngroups + it % ngroups : -1;
+        if constexpr (RING) {                             // kernels.h: the ring kernels' work order (all four tiles carry the same group in an item)
+            const RingItem r = ring_item(xcd, loc / NH, (int)(gridDim.x >> 3), it, loc % NH, total_tiles / ngroups, ngroups, order_seq);
+            return r.pos >= 0 ? r.pos * ngroups + r.g : -1;
         }
         const int idx = loc + it * gper;
         const int t = xcd * per + idx;
@@ -319,16 +323,21 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         }
     };
     // RING: the loader duty of tiles 0 (high banks) and 1 (low banks) in the off-phase of their stage slot s: even s requests the
-    // bank of chunk s / 2 + 1, odd s writes it into its slot.  Chunk k of the walk is (group, chunk) number k mod (groups x chunks),
-    // which is also its place in memory.  n_chunks = chunks of the longest walk (tile 0's).
+    // bank of chunk s / 2 + 1, odd s writes it into its slot.  Chunk k of the walk is chunk k mod chunks of the workgroup's item
+    // k / chunks, whose group follows the work order (kernels.h): the cursor (ring_g, ring_c) steps with the requests, which come in
+    // order of s.  A bank lies at (group x chunks + chunk) in memory.  n_chunks = chunks of the longest walk (tile 0's).
     constexpr int NPH = NPB / 2;                          // 16-byte pieces of one bank
+    const int ring_g0 = RING ? ring_group0((int)(blockIdx.x >> 3), ngroups, order_seq) : 0;
+    const int ring_gstep = RING ? ring_group_step((int)(gridDim.x >> 3), ngroups, order_seq) : 0;
+    int ring_g = ring_g0, ring_c = 0;
     auto ring_duty = [&](int s, int n_chunks) {
         if constexpr (RING) {
             if (half > 1) return;
             const int k = (s >> 1) + 1;
             if (k >= n_chunks) return;
             if (!(s & 1)) {
-                const char* wsrc = (const char*)a.wpk + ((size_t)(k % (ngroups * nch_r)) * 2 + half) * (TAPS * kTapBytes);
+                if (++ring_c == nch_r) { ring_c = 0; ring_g += ring_gstep; if (ring_g >= ngroups) ring_g -= ngroups; }
+                const char* wsrc = (const char*)a.wpk + ((size_t)(ring_g * nch_r + ring_c) * 2 + half) * (TAPS * kTapBytes);
 #pragma unroll
                 for (int it = 0; it < BIT; ++it) {
                     const int p = tid + NTHR * it;
@@ -406,8 +415,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     // (DUO: a half without tiles runs the prologue on tile 0 -- valid addresses, results unused -- and then only keeps the beat)
     Stage cs{0, decode((DUO && my_stages == 0) ? 0 : tile_at(0))}, n1 = cs, n2 = cs;
 
-    if constexpr (BRES || RING) {                         // resident banks / RING: chunk 0 of the walk into slot 0
-        const char* wsrc = (const char*)a.wpk;
+    if constexpr (BRES || RING) {                         // resident banks / RING: chunk 0 of the walk (the first item's group) into slot 0
+        const char* wsrc = (const char*)a.wpk + (RING ? (size_t)ring_g0 * nch_r * 2 * (TAPS * kTapBytes) : 0);
         for (int p = tid; p < lds_b_bytes / 16; p += NTHR) *(u32x4*)(sB + p * 16) = *(const u32x4*)(wsrc + (size_t)p * 16);
     }
     for (int i = tid; i < Cout * (RES ? 2 : 1); i += NTHR)

@@ -437,12 +437,16 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     };
     auto entry_size = [&](const Sp& p) -> int { return p.sec ? kEntU : (p.part == 2 ? kEntR : kEntRH); };
 
-    // positions: tile j of the (quarter-)workgroup with index loc on this XCD is position xcd per_pos + loc + j gper; every tile of the
-    // workgroup walks a position's channel groups in the same order
-    const int xcd = blockIdx.x & 7, local = (int)(blockIdx.x >> 3) * NH + half, gper = (int)(gridDim.x >> 3) * NH;
-    const int total_pos = total_tiles / ngroups, per_pos = (total_pos + 7) >> 3;
-    const int lim = min(per_pos, total_pos - xcd * per_pos);
-    auto count_pos = [&](int loc) -> int { return lim > loc ? (lim - loc + gper - 1) / gper : 0; };
+    // the walk: the workgroup's items in the ring kernels' work order (kernels.h); every tile of the workgroup carries the same channel
+    // group in an item.  The sequential order exists in the development build only (SOFTSPOKEN_ORDER=0)
+#ifdef SS_DEVBUILD
+    const bool order_seq = !(a.dbg & 512);
+#else
+    constexpr bool order_seq = !kOrderSideBySide;
+#endif
+    const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3), nwg = (int)(gridDim.x >> 3);
+    const int total_pos = total_tiles / ngroups;
+    const int g0 = ring_group0(wg, ngroups, order_seq), gstep = ring_group_step(nwg, ngroups, order_seq);
     struct Tile { int n, y0, x0, g; };
     auto decode_pos = [&](int pos, int g) -> Tile {
         Tile d;
@@ -452,9 +456,9 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
         d.n = pos / a.tiles_y;
         return d;
     };
-    const int my_pos = count_pos(local);
-    const int my_stages = my_pos * ngroups * nst;
-    const int max_stages = count_pos((int)(blockIdx.x >> 3) * NH) * ngroups * nst;     // (the tile with the lowest index has the most positions)
+    const int my_items = ring_items(xcd, wg, nwg, half, total_pos, ngroups, order_seq);
+    const int my_stages = my_items * nst;
+    const int max_stages = ring_items(xcd, wg, nwg, 0, total_pos, ngroups, order_seq) * nst;     // (the tile with the lowest index has the most items)
     if (max_stages == 0) return;                          // whole workgroup idle
 
     // ---- this thread's patch pieces (as in the resident form) ----
@@ -514,17 +518,15 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
         }
     };
 
-    // ---- the walk: the current (position, group), the one behind it (decoded once per position, in a light off-phase), and the stage
+    // ---- the walk: the current (position, group), the one behind it (decoded once per item -- kernels.h ring_item: two integer divisions --, in a light off-phase), and the stage
     // whose patch is in flight in `ra` (it lies in the current position or in the next) ----
-    const int pos0 = xcd * per_pos + local;
-    Tile cur = decode_pos(my_pos ? pos0 : 0, 0), nxt = cur;
-    int cur_g = 0, cur_j = 0, nxt_g = 0, nxt_j = 0;
+    Tile cur = decode_pos(my_items ? ring_item(xcd, wg, nwg, 0, half, total_pos, ngroups, order_seq).pos : 0, g0), nxt = cur;
+    int cur_i = 0, nxt_i = 0;
     bool nxt_ok = false;
     auto compute_next = [&]() {
-        nxt_g = cur_g + 1; nxt_j = cur_j;
-        if (nxt_g == ngroups) { nxt_g = 0; ++nxt_j; }
-        nxt_ok = nxt_j < my_pos;
-        if (nxt_ok) nxt = decode_pos(pos0 + nxt_j * gper, nxt_g);
+        nxt_i = cur_i + 1;
+        nxt_ok = nxt_i < my_items;
+        if (nxt_ok) { const RingItem r = ring_item(xcd, wg, nwg, nxt_i, half, total_pos, ngroups, order_seq); nxt = decode_pos(r.pos, r.g); }
     };
     struct Cur { Sp sp; Tile d; bool ok; };
     auto advance = [&](Cur& c) {
@@ -532,11 +534,11 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     };
     Cur ip{Sp{0, 0, 0}, cur, true};
 
-    // ---- the bank ring: prologue = the walk's first three entries (group 0's), by every thread ----
+    // ---- the bank ring: prologue = the walk's first three entries (the first item's group's: a group has four or more), by every thread ----
     {
         Sp p{0, 0, 0};
         for (int e = 0; e < 3; ++e) {
-            const char* src = (const char*)a.wpk + entry_off(p);
+            const char* src = (const char*)a.wpk + (size_t)g0 * group_bytes + entry_off(p);
             const int np = entry_size(p) / 16;
             for (int q = (int)threadIdx.x; q < np; q += NTHR * NH) *(u32x4*)(sR + e * kSlot + q * 16) = *(const u32x4*)(src + (size_t)q * 16);
             do sp_next(p); while (!starts_entry(p));
@@ -547,11 +549,11 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     // write pass); the issuing waves retire it with the vmcnt(0) in front of the barrier that ends beat 2 s_e - 1, the readers pass
     // that barrier before their first read.  The cursor runs d stages ahead of the tile's own stage count.
     Sp rq{0, 0, 0};
-    int rq_g = 0, rq_t = 0, rq_e = 0, rq_slot = 0;        // target stage: group, absolute number; entries started before it: count, slot of the next
+    int rq_g = g0, rq_t = 0, rq_e = 0, rq_slot = 0;       // target stage: group, absolute number; entries started before it: count, slot of the next
     auto rq_advance = [&]() {
         if (starts_entry(rq)) { ++rq_e; rq_slot = rq_slot == 2 ? 0 : rq_slot + 1; }
         ++rq_t;
-        if (sp_next(rq)) { if (++rq_g == ngroups) rq_g = 0; }
+        if (sp_next(rq)) { rq_g += gstep; if (rq_g >= ngroups) rq_g -= ngroups; }      // the next item's group
     };
     if (half & 1) for (int i = 0; i < (half == 1 ? 2 : 3); ++i) rq_advance();
     auto ring_issue = [&]() {
@@ -783,7 +785,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
         if (last) { acc_done = acc; done_off = (((uint32_t)cur.n * H + cur.y0) * W + cur.x0) * Cout + cur.g * 32; have_done = true; }
         if (KIND == 1 && c == 0 && have_done && !SS_ABL(20)) { store_h(); have_done = false; }
         if (KIND == 1 && c == 0) compute_next();          // (before the patch requests reach into the next position: the second chunk's R0 at the earliest)
-        if (last && more) { cur = nxt; cur_g = nxt_g; cur_j = nxt_j; }
+        if (last && more) { cur = nxt; cur_i = nxt_i; }
         substamp(6);
         if (np) {
             do advance(ip); while (ip.ok && !needs_patch(ip.sp));
@@ -801,7 +803,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>; using K2 = std::integral_constant<int, 2>;
     using K3 = std::integral_constant<int, 3>; using K4 = std::integral_constant<int, 4>;
     // beats: tile q starts q barriers late and ends NH - 1 - q barriers late; a tile that runs out of positions keeps the beat and its loader duty
-    const int my_pg = my_pos * ngroups, max_pg = max_stages / nst;
+    const int my_pg = my_items, max_pg = max_stages / nst;
     for (int i = 0; i < half; ++i) lds_barrier();
     for (int pg = 0; pg < max_pg; ++pg) {
         if (pg < my_pg) {

@@ -167,8 +167,9 @@ static bool ensure_lane(ss_ctx* c, int n) {
 struct ConvExtra { const float* first_w = nullptr; const float* first_b = nullptr; const void* flat_w = nullptr; const void* flat_w4 = nullptr; float* flat_part = nullptr; int store_out = 1; };
 
 static int base_dbg() {
-    // product build: 32 (raised wave priority inside conv4.hip's MFMA loop: the measured default); dev build: + SOFTSPOKEN_DBG bits
-    return (dev_env("SOFTSPOKEN_PRIO", 1) ? 32 : 0) | dev_env("SOFTSPOKEN_DBG", 0);
+    // product build: 32 (raised wave priority inside conv4.hip's MFMA loop: the measured default); dev build: + SOFTSPOKEN_DBG bits, and bit 9 =
+    // the ring kernels' side-by-side work order (kernels.h; SOFTSPOKEN_ORDER=0: the sequential one; the product's order is compiled in)
+    return (dev_env("SOFTSPOKEN_PRIO", 1) ? 32 : 0) | (dev_env("SOFTSPOKEN_ORDER", kOrderSideBySide ? 1 : 0) ? 512 : 0) | dev_env("SOFTSPOKEN_DBG", 0);
 }
 
 #ifdef SS_DEVBUILD

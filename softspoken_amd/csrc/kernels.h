@@ -56,6 +56,44 @@ struct ConvArgs {
     int* range_flag;                              // f16x2: set to 1 when a value that is being split does not fit an f16 (overflow, NaN)
     void* stamps;                                 // dev build: [grid][waves][8] uint32 segment times of a stage (null otherwise)
 };
+// ---- work order of the four-tile ring kernels (conv4.hip RING, conv4_ups.hip conv3x3_upsr_kernel) ----------------
+// A launch has total_pos positions (8 x 16-pixel tiles) x ngroups groups of 32 output channels.  XCD x owns the positions
+// [x per_pos, x per_pos + lim), per_pos = ceil(total_pos / 8); a QUAD is four consecutive positions of that range, one per tile of a
+// workgroup.  The XCD's G = gridDim.x / 8 workgroups walk items; all four tiles of a workgroup carry the same group in an item (they
+// share one bank ring), and a tile whose position lies past the range has no work in that item and only keeps the beat.
+//   side by side (the product): the XCD's items are (quad, group), group fastest, and workgroup w takes items w, w + G, w + 2 G, ...:
+//     a quad's groups run at the same time on neighbouring workgroups of one XCD, so the quad's input patches are fetched from the
+//     fabric once and found in that XCD's L2 (or merged with the miss in flight) by the other groups' readers;
+//   sequential (development build, SOFTSPOKEN_ORDER=0; the order up to round 4): workgroup w takes quads w, w + G, ... and walks each
+//     quad's groups one after the other -- between two readings of a patch the XCD's other tiles pull several L2s' worth through.
+// Both orders give every (position, group) to exactly one tile, and with one group they are the same map.
+static constexpr bool kOrderSideBySide = true;      // the product's order
+struct RingItem { int pos, g; };                    // pos < 0: no work for this tile (g is the workgroup's group all the same)
+__host__ __device__ inline int ring_lim(int xcd, int total_pos) {   // positions of the XCD
+    const int per_pos = (total_pos + 7) >> 3, left = total_pos - xcd * per_pos;
+    return left < 0 ? 0 : left < per_pos ? left : per_pos;
+}
+// group of a workgroup's item i: g0 + i * step (mod ngroups)
+__host__ __device__ inline int ring_group0(int wg, int ngroups, bool seq) { return seq ? 0 : wg % ngroups; }
+__host__ __device__ inline int ring_group_step(int G, int ngroups, bool seq) { return seq ? 1 % ngroups : G % ngroups; }
+// item `item` of tile `tile` (0..3) of workgroup `wg` (0..G-1) on XCD `xcd`
+__host__ __device__ inline RingItem ring_item(int xcd, int wg, int G, int item, int tile, int total_pos, int ngroups, bool seq) {
+    const int lim = ring_lim(xcd, total_pos);
+    int quad, g;
+    if (seq) { quad = wg + (item / ngroups) * G; g = item % ngroups; }
+    else { const int j = wg + item * G; quad = j / ngroups; g = j - quad * ngroups; }
+    const int idx = 4 * quad + tile;
+    return RingItem{idx < lim ? xcd * ((total_pos + 7) >> 3) + idx : -1, g};
+}
+// items in which that tile has work: its first ring_items items (a tile never has work again behind an item without)
+__host__ __device__ inline int ring_items(int xcd, int wg, int G, int tile, int total_pos, int ngroups, bool seq) {
+    const int lim = ring_lim(xcd, total_pos);
+    const int quads = lim > tile ? (lim - tile + 3) >> 2 : 0;             // quads in which the tile's position exists
+    if (seq) return quads > wg ? (quads - wg + G - 1) / G * ngroups : 0;
+    const int n = quads * ngroups;
+    return n > wg ? (n - wg + G - 1) / G : 0;
+}
+
 // NT = number of 32-wide output-channel tiles per block (1..3); Cout % (32*NT) == 0.
 // second structure (conv2.hip): persistent blocks, register prefetch, resident weights, staged stores
 hipError_t launch_conv3x3_v2(const ConvArgs& a, bool bf16, int NT, int num_cus, hipStream_t s);
