@@ -143,14 +143,19 @@ __device__ __forceinline__ void from_runs(const u32x4& lo, const u32x4& hi, Pack
 // (and, when the weights are streamed, a bank buffer) and walks its own tiles; resident weights are shared by the two halves.
 // Every thread of the workgroup executes the same number of barriers: a half that runs out of stages keeps the beat.
 template <int NT, int NW, bool BRES, bool RES, bool RADD, bool POOL, int RP, bool FIRST, bool FLAT, bool PF2, bool SPLIT = false, bool RANK1 = false,
-          int NH = 1>
+          int NH = 1, bool GRES = false>
 // (registers: two blocks per CU want 128; the f16x2 A form of the 8 x 16 level -- 4 waves, streamed banks, two accumulator sets -- is held to
 // two blocks per CU by its 57 KB of LDS anyway, i.e. two waves per SIMD: at 128 registers it spilled 35 of them)
 __global__ __launch_bounds__(64 * NW * NH) __attribute__((amdgpu_waves_per_eu((NT <= 2 && !(SPLIT && RES && !BRES && NW == 4 && NH == 1)) ? 4 : 2)))
 void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     constexpr int KC = 32;
     constexpr bool DUO = NH > 1;                          // NH tiles per workgroup (2 x 8 waves or 4 x 4 waves), one beat apart
-    static_assert(!DUO || (NT == 1 && NW * NH == 16 && RP == 0 && !FIRST && !FLAT && !PF2), "DUO: the plain A / B launches");
+    static_assert(!DUO || (NT == 1 && NW * NH == 16 && (RP == 0 || (GRES && RP == 1 && POOL)) && !FIRST && !FLAT && !PF2),
+                  "DUO: the plain A / B launches; GRES also conv2_1.B's projection in B");
+    // GRES (DUO, several channel groups): the workgroup carries ONE group for its whole life (kernels.h: gres_item) and holds that
+    // group's banks -- all chunks, both halves -- in LDS from the prologue on, where the other forms stream them per (tile, group)
+    // or per quad.  Slot 0 of the bank area is the workgroup's group.
+    static_assert(!GRES || (DUO && BRES && SPLIT && !RES), "GRES: f16x2 B launches with resident banks");
     // RING (DUO with streamed banks, four tiles): the workgroup's tiles walk the same (group, chunk) sequence a beat apart, so a
     // chunk's two banks are staged ONCE per workgroup into a two-slot ring: chunk k is read during beats 4k .. 4k+5 (tile q's two
     // stages of it multiply at beats 4k+q and 4k+2+q), its slot is free again from beat 4k+6, chunk k+2's high bank lands there at
@@ -214,6 +219,10 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     constexpr bool order_seq = !kOrderSideBySide;
 #endif
     auto tile_of = [&](int loc, int it) -> int {          // tile `it` of the (half-)block with index `loc` on this XCD
+        if constexpr (GRES) {                             // kernels.h: one group per workgroup
+            const RingItem r = gres_item(xcd, loc / NH, (int)(gridDim.x >> 3), it, loc % NH, total_tiles / ngroups, ngroups, NH);
+            return r.pos >= 0 ? r.pos * ngroups + r.g : -1;
+        }
         if constexpr (RING) {                             // kernels.h: the ring kernels' work order (all four tiles carry the same group in an item)
             const RingItem r = ring_item(xcd, loc / NH, (int)(gridDim.x >> 3), it, loc % NH, total_tiles / ngroups, ngroups, order_seq);
             return r.pos >= 0 ? r.pos * ngroups + r.g : -1;
@@ -404,8 +413,13 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     if constexpr (DUO) {
         const int l0 = (int)(blockIdx.x >> 3) * NH;      // (the group with the lowest index has the most tiles)
         int n0 = 0, nmine = 0;
-        while (tile_of(l0, n0) >= 0) ++n0;
-        while (tile_of(l0 + half, nmine) >= 0) ++nmine;
+        if constexpr (GRES) {
+            n0 = gres_items(xcd, (int)(blockIdx.x >> 3), (int)(gridDim.x >> 3), 0, total_tiles / ngroups, ngroups, NH);
+            nmine = gres_items(xcd, (int)(blockIdx.x >> 3), (int)(gridDim.x >> 3), half, total_tiles / ngroups, ngroups, NH);
+        } else {
+            while (tile_of(l0, n0) >= 0) ++n0;
+            while (tile_of(l0 + half, nmine) >= 0) ++nmine;
+        }
         my_stages = nmine * nch;
         max_stages = n0 * nch;
         if (max_stages == 0) return;                      // whole workgroup idle
@@ -415,7 +429,10 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     // (DUO: a half without tiles runs the prologue on tile 0 -- valid addresses, results unused -- and then only keeps the beat)
     Stage cs{0, decode((DUO && my_stages == 0) ? 0 : tile_at(0))}, n1 = cs, n2 = cs;
 
-    if constexpr (BRES || RING) {                         // resident banks / RING: chunk 0 of the walk (the first item's group) into slot 0
+    if constexpr (GRES) {                                 // the workgroup's own group, every chunk: loaded once, by all its threads
+        const char* wsrc = (const char*)a.wpk + (size_t)gres_group((int)(blockIdx.x >> 3), ngroups) * nch_r * 2 * (TAPS * kTapBytes);
+        for (int p = (int)threadIdx.x; p < lds_b_bytes / 16; p += NTHR * NH) *(u32x4*)(sB + p * 16) = *(const u32x4*)(wsrc + (size_t)p * 16);
+    } else if constexpr (BRES || RING) {                         // resident banks / RING: chunk 0 of the walk (the first item's group) into slot 0
         const char* wsrc = (const char*)a.wpk + (RING ? (size_t)ring_g0 * nch_r * 2 * (TAPS * kTapBytes) : 0);
         for (int p = tid; p < lds_b_bytes / 16; p += NTHR) *(u32x4*)(sB + p * 16) = *(const u32x4*)(wsrc + (size_t)p * 16);
     }
@@ -723,7 +740,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         if constexpr (FLAT && SPLIT && RP > 0) load_flat_w();
         {
             // (resident banks of several channel groups -- DUO only -- lie as in memory: [group][chunk][bank])
-            const char* bbase = sB + boff0 + (BRES ? ((DUO ? cur.g * nch : 0) + (SPLIT ? (ci >> 1) * 2 : ci)) * TAPS * kTapBytes
+            const char* bbase = sB + boff0 + (BRES ? ((DUO && !GRES ? cur.g * nch : 0) + (SPLIT ? (ci >> 1) * 2 : ci)) * TAPS * kTapBytes
                                                    : RING ? ((stage_no >> 1) & 1) * lds_b_bytes : 0);
             constexpr int PD = (NT == 1) ? 4 : 2;        // fragment prefetch depth (NT = 2 at depth 4 spills under its 128-register cap)
             u32x4 af[PD], bfr[PD][NT];
@@ -1074,6 +1091,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             }
             ring_duty(stage_no, max_stages >> 1);
             ++stage_no;
+            if constexpr (SPLIT && RP > 0 && PART == 0) issue_proj(cur, ci >> 1, KZ_{}, KH_{});
             jitter(4);
             epilogue();
             jitter(6);
@@ -1166,18 +1184,27 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
 }
 
 template <int NT, int NW, bool BRES, bool RES, bool RADD, bool POOL, int RP, bool FIRST, bool FLAT, bool PF2, bool SPLIT = false, bool RANK1 = false,
-          int NH = 1>
+          int NH = 1, bool GRES = false>
 static hipError_t launch_v4_k(const ConvArgs& a, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};              // (per device: kernels.h allow_full_lds)
-    if (hipError_t e = allow_full_lds((const void*)conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH>, attr_done)) return e;
-    hipLaunchKernelGGL((conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH>), dim3(grid), dim3(64 * NW * NH),
+    if (hipError_t e = allow_full_lds((const void*)conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH, GRES>, attr_done)) return e;
+    hipLaunchKernelGGL((conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH, GRES>), dim3(grid), dim3(64 * NW * NH),
                        lds, s, a, total, lds_b);
     return hipGetLastError();
 }
 
 // DUO forms (f16x2, resident banks shared by the two halves): the plain A (RES) and B (RADD, + POOL) launches with 8-wave tiles
-template <int NW, int NH, bool BRES>
+// GRES (one channel group per workgroup, its banks resident): the B launches of the two-group 64 -> 64 blocks -- conv7.B (RADD), conv2_1.B
+// ("projection in B" + POOL; RADD + POOL when the development build switches the projection off)
+template <int NW, int NH, bool BRES, bool GRES = false>
 static hipError_t launch_v4_duo(const ConvArgs& a, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
+    if constexpr (GRES) {
+        static_assert(NH == 4 && NW == 4, "GRES: four 4-wave tiles");
+        if (a.proj_w) return a.pool_out ? launch_v4_k<1, NW, true, false, false, true, 1, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s)
+                                        : hipErrorInvalidValue;
+        if (a.pool_out) return launch_v4_k<1, NW, true, false, true, true, 0, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s);
+        return launch_v4_k<1, NW, true, false, true, false, 0, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s);
+    }
     if constexpr (BRES && NH == 4) {
         if (a.plain) return launch_v4_k<1, NW, true, false, false, false, 0, false, false, false, true, false, NH>(a, total, lds_b, lds, grid, s);
     }
@@ -1258,7 +1285,10 @@ static hipError_t launch_v4_kind(const ConvArgs& a, bool bres, int total, int ld
 #ifndef SS_DUO_DEFAULT
 #define SS_DUO_DEFAULT 4
 #endif
-struct V4Choice { bool ok; int nw, total, lds_b, grid; bool bres; size_t lds; int duo; };
+#ifndef SS_GRES_DEFAULT
+#define SS_GRES_DEFAULT 1
+#endif
+struct V4Choice { bool ok; int nw, total, lds_b, grid; bool bres; size_t lds; int duo; bool gres; };
 
 static V4Choice choose_v4(ConvArgs& a, int NT, int num_cus, int prec) {
     V4Choice c{};
@@ -1328,6 +1358,30 @@ static V4Choice choose_v4(ConvArgs& a, int NT, int num_cus, int prec) {
     // (the four-tile form's tiles are 8 rows: it also takes the 8 x 16 level -- conv_bottleneck.A / encoder_out.A over the bank ring, one
     // whole picture per tile -- where the independent 4-wave blocks ran at 190 TFLOP/s)
     static const int duo8_env = dev_env("SOFTSPOKEN_DUO_H8", 1);
+    // GRES: one channel group per workgroup, that group's banks resident (kernels.h: gres_item).  A B launch with several groups whose
+    // ONE group's banks fit beside the patches: the 64 -> 64 blocks' (72 KB per group) -- conv7.B over four 8-row tiles, conv2_1.B
+    // ("projection in B") likewise.  The other forms stage those 72 KB per (tile, group) or per quad.  conv2_1.B as two 16-row tiles with
+    // the banks resident measured the same as the four 8-row tiles (tools/experiments/r06_conv2_1B_resident_two_tiles.patch).
+    // (SOFTSPOKEN_GRES=0 in the dev build: the forms below, as before)
+    static const int gres_env = dev_env("SOFTSPOKEN_GRES", SS_GRES_DEFAULT);
+    if (gres_env && duo_env == 4 && split && NT == 1 && ngroups > 1 && !first && !flat && !rank1 && !a.plain && !a.res_out &&
+        (proj ? (a.pool_out && rp == 1 && c.nw == 8) : a.res_in != nullptr) && (c.nw == 8 || duo8_env)) {
+        const int nh = 4, thd = 32 / nh;
+        const size_t group_b = (size_t)all_taps * tap_bytes * banks;
+        const size_t proj_b = proj ? (size_t)((a.C0x + a.C1x) / 16) * (a.Cout / 32) * 1024 * banks : 0;
+        const size_t lds = nh * (size_t)(thd + 2) * kRowPitch + group_b + proj_b + (size_t)a.Cout * 4;
+        const long total_pos = (long)a.N * (a.H / thd) * a.tiles_x;
+        const int grid = total_pos <= 0x7fffffff / ngroups ? gres_grid(num_cus, (int)total_pos, ngroups, nh) : 0;
+        if (lds <= 160 * 1024 && gres_grid_ok(grid, ngroups)) {
+            c.duo = nh; c.gres = true; c.bres = true; c.lds_b = (int)group_b; c.lds = lds;
+            c.nw = 16 / nh;
+            a.tiles_y = a.H / thd;
+            c.total = (int)(total_pos * ngroups);
+            c.grid = grid;
+            c.ok = true;
+            return c;
+        }
+    }
     if ((duo_env == 2 || duo_env == 4) && split && NT == 1 && (c.nw == 8 || (duo_env == 4 && duo8_env)) && !first && !flat && !proj && !rank1) {
         const int nh = duo_env, thd = 32 / nh;           // tile rows: 16 (8 waves) or 8 (4 waves)
         const size_t fixed = nh * (size_t)(thd + 2) * kRowPitch + (size_t)a.Cout * 4 * (a.res_out ? 2 : 1);
@@ -1378,9 +1432,9 @@ bool conv_v4_supports(const ConvArgs& a_in, int NT, int num_cus, int prec) {
     return choose_v4(a, NT, num_cus, prec).ok;
 }
 
-// conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH> as rocprofv3 prints it
+// conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH, GRES> as rocprofv3 prints it
 const char* conv_v4_variant(const ConvArgs& a_in, int NT, int num_cus, int prec) {
-    static thread_local char buf[112];
+    static thread_local char buf[128];
     ConvArgs a = a_in;
     const V4Choice c = choose_v4(a, NT, num_cus, prec);
     if (!c.ok) return "conv3x3_v4_kernel<invalid>";
@@ -1391,10 +1445,10 @@ const char* conv_v4_variant(const ConvArgs& a_in, int NT, int num_cus, int prec)
     const bool radd = !res && !first && !a.plain && rp == 0 && !rank1;
     const bool pf2 = !split && rp == 0 && c.nw == 8 && !(res && NT == 2) && v4_pf2(c.bres, c.lds, NT, first, flat);
     if (split)
-        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, false, true, %s, %d>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
-                 tf(!res && a.pool_out), rp, tf(first), tf(flat), tf(rank1), c.duo ? c.duo : 1);
+        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, false, true, %s, %d, %s>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
+                 tf(!res && a.pool_out), rp, tf(first), tf(flat), tf(rank1), c.duo ? c.duo : 1, tf(c.gres));
     else
-        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, %s, false, false, 1>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
+        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, %s, false, false, 1, false>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
                  tf(!res && a.pool_out), rp, tf(first), tf(flat), tf(pf2));
     return buf;
 }
@@ -1404,6 +1458,7 @@ hipError_t launch_conv3x3_v4(const ConvArgs& a_in, int NT, int num_cus, int prec
     const V4Choice c = choose_v4(a, NT, num_cus, prec);
     if (!c.ok) return hipErrorInvalidValue;
     if (prec == 2) {
+        if (c.gres) return launch_v4_duo<4, 4, true, true>(a, c.total, c.lds_b, c.lds, c.grid, s);
         if (c.duo == 2) return launch_v4_duo<8, 2, true>(a, c.total, c.lds_b, c.lds, c.grid, s);
         if (c.duo == 4) return c.bres ? launch_v4_duo<4, 4, true>(a, c.total, c.lds_b, c.lds, c.grid, s)
                                       : launch_v4_duo<4, 4, false>(a, c.total, c.lds_b, c.lds, c.grid, s);

@@ -94,6 +94,36 @@ __host__ __device__ inline int ring_items(int xcd, int wg, int G, int tile, int 
     return n > wg ? (n - wg + G - 1) / G : 0;
 }
 
+// ---- work order "one group per workgroup" (conv4.hip GRES: a group's banks resident in the workgroup's LDS) ----------------------
+// The XCDs own the positions as above (ring_lim).  Of an XCD's G workgroups, workgroup w carries group w mod ngroups for its whole life
+// and belongs to slot w / ngroups; the S = G / ngroups slots deal the XCD's positions among themselves, nh consecutive ones per item
+// (one per tile of the workgroup): item i of slot s is the positions (s + i S) nh + tile.  The ngroups workgroups of a slot are
+// neighbours on one XCD and walk the SAME position sequence at the same time, so a position's patches come from the fabric once and
+// the siblings find them in that XCD's L2 -- and a workgroup loads its group's banks once per launch.
+// The form needs G to be a multiple of ngroups: gres_grid_ok is the chooser's predicate, gres_grid the grid it asks for.
+__host__ __device__ inline bool gres_grid_ok(int grid, int ngroups) { return grid > 0 && ngroups > 0 && grid % (8 * ngroups) == 0; }
+// workgroups of a launch on num_cus CUs: one per CU, fewer when the busiest XCD has fewer items than slots; 0 = the form does not apply
+__host__ __device__ inline int gres_grid(int num_cus, int total_pos, int ngroups, int nh) {
+    int G = (num_cus + 7) / 8;
+    if (ngroups <= 0 || G % ngroups) return 0;
+    const int units = (((total_pos + 7) >> 3) + nh - 1) / nh;        // items of the busiest XCD (XCD 0)
+    if (units < G / ngroups) G = (units > 0 ? units : 1) * ngroups;
+    return 8 * G;
+}
+__host__ __device__ inline int gres_group(int wg, int ngroups) { return wg % ngroups; }
+// item `item` of tile `tile` (0..nh-1) of workgroup `wg` (0..G-1) on XCD `xcd`; pos < 0: no work for this tile
+__host__ __device__ inline RingItem gres_item(int xcd, int wg, int G, int item, int tile, int total_pos, int ngroups, int nh) {
+    const int lim = ring_lim(xcd, total_pos), S = G / ngroups;
+    const int idx = (wg / ngroups + item * S) * nh + tile;
+    return RingItem{idx < lim ? xcd * ((total_pos + 7) >> 3) + idx : -1, wg % ngroups};
+}
+// items in which that tile has work: its first gres_items items
+__host__ __device__ inline int gres_items(int xcd, int wg, int G, int tile, int total_pos, int ngroups, int nh) {
+    const int lim = ring_lim(xcd, total_pos), S = G / ngroups, s = wg / ngroups;
+    const int units = lim > tile ? (lim - tile + nh - 1) / nh : 0;    // items of the XCD in which the tile's position exists
+    return units > s ? (units - s + S - 1) / S : 0;
+}
+
 // NT = number of 32-wide output-channel tiles per block (1..3); Cout % (32*NT) == 0.
 // second structure (conv2.hip): persistent blocks, register prefetch, resident weights, staged stores
 hipError_t launch_conv3x3_v2(const ConvArgs& a, bool bf16, int NT, int num_cus, hipStream_t s);

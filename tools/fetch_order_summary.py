@@ -7,17 +7,18 @@ usage: python tools/fetch_order_summary.py <windows> <label=fetch_dir:hit_dir> .
 import collections, csv, glob, os, sys
 
 # launches of a pass in dispatch order per instantiation: (layer, H, W, C0, C1 (upsampled, at H/2 x W/2), Cout, B launch)
-RING_A = "conv3x3_v4_kernel<1, 4, false, true, false, false, 0, false, false, false, true, false, 4>"
-RING_BP = "conv3x3_v4_kernel<1, 4, false, false, true, true, 0, false, false, false, true, false, 4>"
-RING_B = "conv3x3_v4_kernel<1, 4, false, false, true, false, 0, false, false, false, true, false, 4>"
-RES_B = "conv3x3_v4_kernel<1, 4, true, false, true, false, 0, false, false, false, true, false, 4>"
+RING_A = "conv3x3_v4_kernel<1, 4, false, true, false, false, 0, false, false, false, true, false, 4, false>"
+RING_BP = "conv3x3_v4_kernel<1, 4, false, false, true, true, 0, false, false, false, true, false, 4, false>"
+RING_B = "conv3x3_v4_kernel<1, 4, false, false, true, false, 0, false, false, false, true, false, 4, false>"
+RES_B = "conv3x3_v4_kernel<1, 4, true, false, true, false, 0, false, false, false, true, false, 4, false>"
+GRES_B = "conv3x3_v4_kernel<1, 4, true, false, true, false, 0, false, false, false, true, false, 4, true>"     # one group per workgroup, banks resident
 LAUNCHES = {
     "conv3x3_upsr_kernel": [("conv6.A", 16, 32, 128, 128, 96, False), ("conv7.A", 32, 64, 96, 96, 64, False), ("conv8.A", 64, 128, 64, 64, 32, False)],
     RING_A: [("conv3_1.A", 32, 64, 64, 0, 96, False), ("conv4_1.A", 16, 32, 96, 0, 128, False), ("conv_bottleneck.A", 8, 16, 128, 0, 128, False),
              ("encoder_out.A", 8, 16, 128, 0, 128, False)],
     RING_BP: [("conv3_1.B", 32, 64, 96, 0, 96, True), ("conv4_1.B", 16, 32, 128, 0, 128, True)],
-    RING_B: [("conv_bottleneck.B", 8, 16, 128, 0, 128, True), ("encoder_out.B", 8, 16, 128, 0, 128, True), ("conv6.B", 16, 32, 96, 0, 96, True),
-             ("conv7.B", 32, 64, 64, 0, 64, True)],
+    RING_B: [("conv_bottleneck.B", 8, 16, 128, 0, 128, True), ("encoder_out.B", 8, 16, 128, 0, 128, True), ("conv6.B", 16, 32, 96, 0, 96, True)],
+    GRES_B: [("conv7.B", 32, 64, 64, 0, 64, True)],
     RES_B: [("conv8.B", 64, 128, 32, 0, 32, True)],
 }
 
