@@ -29,17 +29,11 @@
 // 512-thread block per CU (8 waves, 2 per SIMD, amdgpu_waves_per_eu(2, 2)), a wave takes units blockIdx * 8 + wave, + 8 * grid, ...;
 // TRACK = per-value f16 range test (false when weights.hip proved the range: ConvPlan::s1_range_proven); dynamic LDS 109 / 95 KB.
 #include "kernels.h"
+#include "mfma_util.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace ss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int kH = 128, kW = 256, kC = 32;
 static constexpr int kStrips = 9, kStripCols = 30;       // valid columns per strip: lanes 1 .. 30 of the 32-column tile
@@ -49,28 +43,6 @@ static constexpr int kFPitch = 36;                       // floats per row of a 
 static constexpr int kMaxRows = 32;                      // most rows of a work unit (the patch holds rows y0 - 2 .. y0 + rows + 1)
 static constexpr int kFPatch = (kMaxRows + 5) * kFPitch; // floats per wave (+ one row that the last, unused look-ahead of a unit reads)
 
-__device__ __forceinline__ uint32_t s1_pack(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-// lo = f16(x - hi) for a pair whose high halves are packed in `hi` (conv4.hip split_lo: exact subtraction in fp32, one rounding)
-__device__ __forceinline__ uint32_t s1_split_lo(uint32_t hi, float x0, float x1) {
-    uint32_t l;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi), "v"(x0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(hi), "v"(x1));
-    return l;
-}
-__device__ __forceinline__ uint32_t s1_pk_max_u16(uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x16 s1_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void s1_half_swap(uint32_t& x, uint32_t& y) {     // lanes 32..63 of x <-> lanes 0..31 of y
-    const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-    x = r[0]; y = r[1];
-}
 // lane i <- lane i - 1 / lane i + 1 over the whole wavefront (lane 0 / 63: zero).  Lanes 0 and 32 (31 and 63) of the result belong to
 // tile columns without a neighbour in this strip; they are never stored.
 __device__ __forceinline__ float s1_from_left(float v) {
@@ -78,10 +50,6 @@ __device__ __forceinline__ float s1_from_left(float v) {
 }
 __device__ __forceinline__ float s1_from_right(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float s1_relu(float x) {      // integer max: negative floats (and -0) are negative integers (conv4.hip's form)
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
 
 // h1 of one strip row as the second conv's B operands: [K step][plane: 0 = high halves, 1 = low halves]
@@ -113,8 +81,8 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
     {
         const float* w9 = a.first_w;                      // [9][32], tap-major
         auto wv = [&](int t) { return w9[t * 32 + m]; };
-        auto hi2 = [&](float x, float y) { return s1_pack(x, y); };
-        auto lo2 = [&](float x, float y) { return s1_split_lo(s1_pack(x, y), x, y); };
+        auto hi2 = [&](float x, float y) { return pack_f16(x, y); };
+        auto lo2 = [&](float x, float y) { return split_lo(pack_f16(x, y), x, y); };
         auto lo1 = [&](float x) { return x - (float)(_Float16)x; };
         const float b1 = a.first_b[m], b2 = a.bias[m], r1 = a.rank1_w[m];
         if (hh == 0) {
@@ -221,27 +189,27 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
                 const f32x4 oa = fa;
                 const f32x4 ob = hh ? f32x4{0.f, 0.f, 0.f, 0.f} : fb;
                 uint32_t bh[4], bl[4];
-                bh[0] = s1_pack(oa[0], oa[1]); bl[0] = s1_split_lo(bh[0], oa[0], oa[1]);
-                bh[1] = s1_pack(oa[2], 0.f);   bl[1] = s1_split_lo(bh[1], oa[2], 0.f);
-                bh[2] = s1_pack(ob[0], ob[1]); bl[2] = s1_split_lo(bh[2], ob[0], ob[1]);
-                bh[3] = s1_pack(ob[2], 0.f);   bl[3] = s1_split_lo(bh[3], ob[2], 0.f);
+                bh[0] = pack_f16(oa[0], oa[1]); bl[0] = split_lo(bh[0], oa[0], oa[1]);
+                bh[1] = pack_f16(oa[2], 0.f);   bl[1] = split_lo(bh[1], oa[2], 0.f);
+                bh[2] = pack_f16(ob[0], ob[1]); bl[2] = split_lo(bh[2], ob[0], ob[1]);
+                bh[3] = pack_f16(ob[2], 0.f);   bl[3] = split_lo(bh[3], ob[2], 0.f);
                 if (!hh) { bh[1] |= kOneHi; bh[3] |= kOneHi; }      // (bl: the low half of 1.0 is 0)
                 const u32x4 boph = {bh[0], bh[1], bh[2], bh[3]}, bopl = {bl[0], bl[1], bl[2], bl[3]};
                 f32x16 h;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) h[i] = 0.f;
-                h = s1_mfma(wf_hi, bopl, h);
-                h = s1_mfma(kwl, boph, h);
-                h = s1_mfma(wf_hi, boph, h);
+                h = mfma16<true>(wf_hi, bopl, h);
+                h = mfma16<true>(kwl, boph, h);
+                h = mfma16<true>(wf_hi, boph, h);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
                     for (int hq = 0; hq < 2; ++hq) {
-                        const float v0 = s1_relu(h[4 * g + 2 * hq]), v1 = s1_relu(h[4 * g + 2 * hq + 1]);
-                        const uint32_t ph = s1_pack(v0, v1);
-                        if constexpr (TRACK) ovf = s1_pk_max_u16(ovf, ph);     // (h1 beyond the f16 range: its high half is infinity)
+                        const float v0 = relu_i(h[4 * g + 2 * hq]), v1 = relu_i(h[4 * g + 2 * hq + 1]);
+                        const uint32_t ph = pack_f16(v0, v1);
+                        if constexpr (TRACK) ovf = pk_max_u16(ovf, ph);     // (h1 beyond the f16 range: its high half is infinity)
                         Hn.f[g >> 1][0][2 * (g & 1) + hq] = ph;
-                        Hn.f[g >> 1][1][2 * (g & 1) + hq] = s1_split_lo(ph, v0, v1);
+                        Hn.f[g >> 1][1][2 * (g & 1) + hq] = split_lo(ph, v0, v1);
                     }
                 if (edge_strip) {                         // (wave-uniform)
 #pragma unroll
@@ -285,11 +253,11 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { pm[i] = 0.f; p0[i] = 0.f; pp[i] = 0.f; }
             {   // rank-1 residual + bias: (f_hi, f_lo, f_hi, 1, 1) against (wr_hi, wr_hi, wr_lo, b_hi, b_lo), half-wave 0's K slots
-                const uint32_t fh = s1_pack(fc, fc);      // (f_hi, f_hi)
-                const uint32_t fl = s1_split_lo(fh, fc, fc);
+                const uint32_t fh = pack_f16(fc, fc);      // (f_hi, f_hi)
+                const uint32_t fl = split_lo(fh, fc, fc);
                 u32x4 bop = {(fh & 0xffffu) | (fl << 16), (fh & 0xffffu) | kOneHi, 0x3c00u, 0u};
                 if (hh) bop = u32x4{0u, 0u, 0u, 0u};
-                p0 = s1_mfma(wrq, bop, p0);
+                p0 = mfma16<true>(wrq, bop, p0);
             }
             // 18 groups g = (dy, K step, dx) of three products; a group's two weight fragments are requested three groups ahead (the LDS
             // round trip is ~130 cycles loaded, a group's products 96).  The fences keep that order: left to itself the scheduler sinks
@@ -308,9 +276,9 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
                     if (g + PD < 18) rd(g + PD);
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16& acc = dx == 0 ? pm : (dx == 1 ? p0 : pp);
-                    acc = s1_mfma(wh[g % RS], xl, acc);
-                    acc = s1_mfma(wl[g % RS], xh, acc);
-                    acc = s1_mfma(wh[g % RS], xh, acc);
+                    acc = mfma16<true>(wh[g % RS], xl, acc);
+                    acc = mfma16<true>(wl[g % RS], xh, acc);
+                    acc = mfma16<true>(wh[g % RS], xh, acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -322,22 +290,22 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             for (int i = 0; i < 16; ++i) {
                 float t = p0[i] + s1_from_left(pm[i]);
                 t = t + s1_from_right(pp[i]);
-                v[i] = s1_relu(t);
+                v[i] = relu_i(t);
             }
             auto store_rows = [&](const float (&val)[16], char* dst, bool on, auto track_c) {
                 constexpr bool track = TRACK && decltype(track_c)::value;
                 uint32_t kh[8], kl[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    kh[i] = s1_pack(val[2 * i], val[2 * i + 1]);
+                    kh[i] = pack_f16(val[2 * i], val[2 * i + 1]);
                     // (every lane's value enters the range test, the unstored edge lanes' too: they are sums of the same size)
-                    if (track) ovf = s1_pk_max_u16(ovf, kh[i]);
-                    kl[i] = s1_split_lo(kh[i], val[2 * i], val[2 * i + 1]);
+                    if (track) ovf = pk_max_u16(ovf, kh[i]);
+                    kl[i] = split_lo(kh[i], val[2 * i], val[2 * i + 1]);
                 }
                 // (g, hh) pairs -> 16-byte runs (conv4.hip to_runs): pair index 2 g + hq; after the swaps a lane holds channels
                 // [8 hh, 8 hh + 8) in its first run and [16 + 8 hh, 16 + 8 hh + 8) in its second
-                s1_half_swap(kh[0], kh[2]); s1_half_swap(kh[1], kh[3]); s1_half_swap(kh[4], kh[6]); s1_half_swap(kh[5], kh[7]);
-                s1_half_swap(kl[0], kl[2]); s1_half_swap(kl[1], kl[3]); s1_half_swap(kl[4], kl[6]); s1_half_swap(kl[5], kl[7]);
+                half_swap(kh[0], kh[2]); half_swap(kh[1], kh[3]); half_swap(kh[4], kh[6]); half_swap(kh[5], kh[7]);
+                half_swap(kl[0], kl[2]); half_swap(kl[1], kl[3]); half_swap(kl[4], kl[6]); half_swap(kl[5], kl[7]);
 #ifdef SS_DEVBUILD
                 if (a.relu & 16) on = false;              // timing-only: no stores
 #endif
@@ -456,8 +424,8 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
     u32x4 wf1[2];                                         // w_hi (+ bias): stays in registers; w_lo and the rank-1 operand wait in LDS
     {
         const float* w9 = a.first_w;                      // [9][32], tap-major
-        auto hi2 = [&](float x, float y) { return s1_pack(x, y); };
-        auto lo2 = [&](float x, float y) { return s1_split_lo(s1_pack(x, y), x, y); };
+        auto hi2 = [&](float x, float y) { return pack_f16(x, y); };
+        auto lo2 = [&](float x, float y) { return split_lo(pack_f16(x, y), x, y); };
         auto lo1 = [&](float x) { return x - (float)(_Float16)x; };
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -564,10 +532,10 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     uint32_t bh[4], bl[4];
-                    bh[0] = s1_pack(fa[t][0], fa[t][1]); bl[0] = s1_split_lo(bh[0], fa[t][0], fa[t][1]);
-                    bh[1] = s1_pack(fa[t][2], 0.f);      bl[1] = s1_split_lo(bh[1], fa[t][2], 0.f);
-                    bh[2] = s1_pack(fb[t][0], fb[t][1]); bl[2] = s1_split_lo(bh[2], fb[t][0], fb[t][1]);
-                    bh[3] = s1_pack(fb[t][2], 0.f);      bl[3] = s1_split_lo(bh[3], fb[t][2], 0.f);
+                    bh[0] = pack_f16(fa[t][0], fa[t][1]); bl[0] = split_lo(bh[0], fa[t][0], fa[t][1]);
+                    bh[1] = pack_f16(fa[t][2], 0.f);      bl[1] = split_lo(bh[1], fa[t][2], 0.f);
+                    bh[2] = pack_f16(fb[t][0], fb[t][1]); bl[2] = split_lo(bh[2], fb[t][0], fb[t][1]);
+                    bh[3] = pack_f16(fb[t][2], 0.f);      bl[3] = split_lo(bh[3], fb[t][2], 0.f);
                     bh[1] |= one1; bh[2] |= one2;
                     const u32x4 bop = lo_group ? u32x4{bl[0], bl[1], bl[2], bl[3]} : u32x4{bh[0], bh[1], bh[2], bh[3]};
                     uint32_t ph[2][2], pl[2][2];
@@ -578,10 +546,10 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
                         h = s16_mfma(wf1[u], bop, h);
 #pragma unroll
                         for (int hq = 0; hq < 2; ++hq) {
-                            const float v0 = s1_relu(h[2 * hq]), v1 = s1_relu(h[2 * hq + 1]);
-                            ph[u][hq] = s1_pack(v0, v1);
-                            if constexpr (TRACK) ovf = s1_pk_max_u16(ovf, ph[u][hq]);
-                            pl[u][hq] = s1_split_lo(ph[u][hq], v0, v1);
+                            const float v0 = relu_i(h[2 * hq]), v1 = relu_i(h[2 * hq + 1]);
+                            ph[u][hq] = pack_f16(v0, v1);
+                            if constexpr (TRACK) ovf = pk_max_u16(ovf, ph[u][hq]);
+                            pl[u][hq] = split_lo(ph[u][hq], v0, v1);
                         }
                     }
                     Hn.f[t][0] = u32x4{ph[0][0], ph[0][1], ph[1][0], ph[1][1]};
@@ -619,8 +587,8 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             f32x4 P[3][2][2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {                 // rank-1 residual + bias start P[dx = 0]; the others start at 0
-                const uint32_t fh = s1_pack(fc[t], fc[t]);
-                const uint32_t fl = s1_split_lo(fh, fc[t], fc[t]);
+                const uint32_t fh = pack_f16(fc[t], fc[t]);
+                const uint32_t fl = split_lo(fh, fc[t], fc[t]);
                 u32x4 bop = {(fh & 0xffffu) | (fl << 16), (fh & 0xffffu) | 0x3c000000u, 0x3c00u, 0u};
                 if (g != 0) bop = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
@@ -655,8 +623,8 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    v[0][u][r] = s1_relu(P[1][0][u][r] + s16_shr1f(P[0][1][u][r]) + P[2][1][u][r]);
-                    v[1][u][r] = s1_relu(P[1][1][u][r] + P[0][0][u][r] + s16_shl1f(P[2][0][u][r]));
+                    v[0][u][r] = relu_i(P[1][0][u][r] + s16_shr1f(P[0][1][u][r]) + P[2][1][u][r]);
+                    v[1][u][r] = relu_i(P[1][1][u][r] + P[0][0][u][r] + s16_shl1f(P[2][0][u][r]));
                 }
             // a lane's eight values of a pixel tile are channels 8 g .. 8 g + 7 of its pixel: one 16-byte run per plane
             auto store_px = [&](const float (&val)[2][4], char* dst, bool on, auto track_c) {
@@ -665,9 +633,9 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float e0 = val[i >> 1][2 * (i & 1)], e1 = val[i >> 1][2 * (i & 1) + 1];
-                    kh[i] = s1_pack(e0, e1);
-                    if (track) ovf = s1_pk_max_u16(ovf, kh[i]);
-                    kl[i] = s1_split_lo(kh[i], e0, e1);
+                    kh[i] = pack_f16(e0, e1);
+                    if (track) ovf = pk_max_u16(ovf, kh[i]);
+                    kl[i] = split_lo(kh[i], e0, e1);
                 }
                 if (on) {
                     *(u32x4*)(dst) = u32x4{kh[0], kh[1], kh[2], kh[3]};

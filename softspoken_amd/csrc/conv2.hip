@@ -26,29 +26,18 @@
 //        of an M-tile in different output columns of one product) and writes per-row-group partial sums, added in fixed order by
 //        the mask head: no c9 tensor.
 #include "kernels.h"
+#include "mfma_util.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace ss {
 
-// development switches exist in the dev build only (engine.h has the same helper for the host units)
 // timing-only ablation bits of ConvArgs::dbg (results are wrong with them set): they exist in the dev build only
 #ifdef SS_DEVBUILD
 #define SS_ABL(x) (x)
 #else
 #define SS_ABL(x) 0
 #endif
-#ifdef SS_DEVBUILD
-static int dev_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#else
-static constexpr int dev_env(const char*, int dflt) { return dflt; }
-#endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 static constexpr int kPixPitch = 80;     // as conv.hip: 64 B of channels + 16 B pad per patch pixel
 static constexpr int kRowPitch = 1664;   // 104 x 16 B per patch row, == 8 (mod 16) slots: conflict-free ds_read_b128
 static constexpr int kPatch = 18;
@@ -65,13 +54,6 @@ __device__ __forceinline__ void mma2(f32x16& acc, const u32x4& a, const u32x4& b
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
     }
 }
-
-// LDS ops of one wave execute in issue order, so a wave's own write -> read needs no hardware wait; the asm
-// statement only pins the compiler's order (and drains lgkmcnt, which is cheap).  It must NOT wait on vmcnt:
-// the next stage's prefetch loads and this tile's output stores are meant to stay in flight.
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// workgroup barrier that orders LDS only (a __syncthreads() would also emit vmcnt(0))
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool BF16, int NT, int MTW, int NW, bool BRES, bool RES, bool FIRST, bool FLAT>
 __global__ __launch_bounds__(64 * NW) void conv3x3_v2_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
@@ -289,11 +271,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_v2_kernel(ConvArgs a, int tot
     int jit_n = 0;
     auto jitter = [&](int site) {
 #ifdef SS_DEVBUILD
-        if (a.dbg & 1024) {
-            const int pat = (a.dbg >> 11) & 3;
-            const bool z = pat == 0 ? ((wave + site + jit_n) & 3) == 0 : pat == 1 ? wave == 0 : pat == 2 ? wave != 0 : (wave & 1) != 0;
-            if (z) __builtin_amdgcn_s_sleep(32);
-        }
+        SS_JITTER_SLEEP(a.dbg, wave, site, jit_n)
 #else
         (void)site;
 #endif

@@ -27,12 +27,9 @@
 //            against conv2.hip's nine-tap form; 106 TFLOP/s issued on the fp32 matrix instruction (157 at 2.4 GHz).
 //   development build only: 8 waves x 1 M-tile (one block per CU: 9.50 -> 10.2 ms on conv9_1.A), NT = 2 / 3 (spill: 4-229 registers).
 #include "kernels.h"
+#include "mfma_util.h"
 
 namespace ss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -48,7 +45,6 @@ __device__ __forceinline__ void mma8(f32x16& acc, const u32x4& a, const u32x4& b
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
 }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 }  // namespace
 
@@ -188,11 +184,7 @@ __global__ __launch_bounds__(512 / MTW) __attribute__((amdgpu_waves_per_eu(2, 2)
     int jit_n = 0;
     auto jitter = [&](int site) {
 #ifdef SS_DEVBUILD
-        if (a.dbg & 1024) {
-            const int pat = (a.dbg >> 11) & 3;
-            const bool z = pat == 0 ? ((wave + site + jit_n) & 3) == 0 : pat == 1 ? wave == 0 : pat == 2 ? wave != 0 : (wave & 1) != 0;
-            if (z) __builtin_amdgcn_s_sleep(32);
-        }
+        SS_JITTER_SLEEP(a.dbg, wave, site, jit_n)
 #else
         (void)site;
 #endif

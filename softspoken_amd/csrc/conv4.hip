@@ -19,7 +19,7 @@
 //     out-of-image pieces read offset 0, a 256-byte zero header the engine keeps in front of every activation tensor.
 // LDS image, fragment packing, XCD tile map, register prefetch of the next stage and LDS-only barriers are conv2.hip's.
 // fp32 stays on conv2.hip.
-#include "kernels.h"
+#include "conv4_forms.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -27,94 +27,15 @@
 
 namespace ss {
 
-// development switches exist in the dev build only (engine.h has the same helper for the host units)
-#ifdef SS_DEVBUILD
-static int dev_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#else
-static constexpr int dev_env(const char*, int dflt) { return dflt; }
-#endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-static constexpr int kPixPitch = 80;     // as conv2.hip
-static constexpr int kRowPitch = 1664;
-static constexpr int kPatch = 18;
 // Waves may raise their priority for the MFMA loop (ConvArgs::dbg bit 5, SOFTSPOKEN_PRIO).  A same-box A/B of the bit shows no
 // difference (30.6 vs 30.7 k audio-s/s, twice); builds with and without the instruction differed by +-5 % per launch in both
 // directions, i.e. what moves is the compiler's schedule around it, not the hardware arbitration.
 static constexpr int kMfmaPrio = 2;
-static constexpr int kHdr = 256;         // zero bytes in front of every activation tensor (engine.hip ensure_workspace)
-
-__device__ __forceinline__ void lds_barrier4() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
 __device__ __forceinline__ uint32_t relu_pk(uint32_t v) {            // bf16 pair: negative <=> int16 negative
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), s16x2{0, 0}));
 }
 __device__ __forceinline__ uint32_t max_pk(uint32_t a, uint32_t b) { // valid for non-negative bf16 (after ReLU)
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-// f16x2 mode: a value is the sum of two f16 halves.  hi = f16(v) (round to nearest), lo = f16(v - hi): v - hi is exact in fp32, so
-// the pair carries ~22 significant bits; small low halves are f16 subnormals, which the matrix instruction keeps.
-__device__ __forceinline__ uint32_t pack_f16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-__device__ __forceinline__ f32x2 unpack_f16(uint32_t v) { return __builtin_convertvector(__builtin_bit_cast(f16x2, v), f32x2); }
-// the largest high half seen so far, per 16-bit lane (the values are >= 0 behind the ReLU: as unsigned integers they order like the
-// values, infinity and NaN on top): one instruction per pair; the test for "all exponent bits set" happens once, on the maximum
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// lo = f16(x - hi) of a pair whose high halves are packed in `hi`: the mixed-precision FMA reads the f16 half and the fp32 value, subtracts in
-// fp32 (exactly: hi is x rounded) and rounds to f16 into one half of the destination -- two instructions for the pair instead of two
-// conversions back, two subtractions and a pack; bit for bit the same (tools/probes/fma_mix_split.hip)
-__device__ __forceinline__ uint32_t split_lo(uint32_t hi, float x0, float x1) {
-    uint32_t l;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi), "v"(x0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(hi), "v"(x1));
-    return l;
-}
-// one 32x32x16 product on 16-bit operands: bf16 (throughput mode) or f16 (f16x2 mode)
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// lanes 32..63 of x <-> lanes 0..31 of y
-__device__ __forceinline__ void half_swap(uint32_t& x, uint32_t& y) {
-    const u32x2 r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-    x = r[0]; y = r[1];
-}
-
-// accumulator tile of one (M-tile, 32 output channels): rows = channels, cols = pixels.  Register r of lane (m, hh) holds
-// channel (r&3) + 8*(r>>2) + 4*hh of pixel m.  P[g][h] = channels 8g + 4hh + 2h + {0,1} as a bf16 pair.
-struct Packed { uint32_t p[4][2]; };
-
-// (g, hh) pairs -> 16-byte runs: after the swaps a lane holds channels [8*hh, 8*hh+8) in lo and [16 + 8*hh, 16 + 8*hh + 8) in hi
-__device__ __forceinline__ void to_runs(Packed& k, u32x4& lo, u32x4& hi) {
-    half_swap(k.p[0][0], k.p[1][0]); half_swap(k.p[0][1], k.p[1][1]);
-    half_swap(k.p[2][0], k.p[3][0]); half_swap(k.p[2][1], k.p[3][1]);
-    lo = u32x4{k.p[0][0], k.p[0][1], k.p[1][0], k.p[1][1]};
-    hi = u32x4{k.p[2][0], k.p[2][1], k.p[3][0], k.p[3][1]};
-}
-__device__ __forceinline__ void from_runs(const u32x4& lo, const u32x4& hi, Packed& k) {   // the swap is its own inverse
-    k.p[0][0] = lo[0]; k.p[0][1] = lo[1]; k.p[1][0] = lo[2]; k.p[1][1] = lo[3];
-    k.p[2][0] = hi[0]; k.p[2][1] = hi[1]; k.p[3][0] = hi[2]; k.p[3][1] = hi[3];
-    half_swap(k.p[0][0], k.p[1][0]); half_swap(k.p[0][1], k.p[1][1]);
-    half_swap(k.p[2][0], k.p[3][0]); half_swap(k.p[2][1], k.p[3][1]);
 }
 
 // FIRST (conv1_1): the 3x3 input h1 = relu(conv3x3(features) + b) is produced on the fly into the LDS patch, by MFMA: the
@@ -603,11 +524,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             if (seg >= 0 && (site != 0 || jit_n > 1)) st_sum[seg] += t - st_prev;
             if (seg >= 0) st_prev = t;
         }
-        if (a.dbg & 1024) {
-            const int pat = (a.dbg >> 11) & 3;
-            const bool z = pat == 0 ? ((wave + site + jit_n) & 3) == 0 : pat == 1 ? wave == 0 : pat == 2 ? wave != 0 : (wave & 1) != 0;
-            if (z) __builtin_amdgcn_s_sleep(32);
-        }
+        SS_JITTER_SLEEP(a.dbg, wave, site, jit_n)
 #else
         (void)site;
 #endif
@@ -898,11 +815,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                             }
                         }
     #pragma unroll
-                        for (int r = 0; r < 16; ++r) {                // ReLU as an integer max: negative floats (and -0) are negative integers;
-                            const float av = acc[nt][r];              // (a copy: __builtin_bit_cast on an ext_vector element reads element 0)
-                            const int b = __builtin_bit_cast(int, av);   // one instruction (fmaxf: a NaN-quieting v_max first)
-                            v[r] = __builtin_bit_cast(float, b > 0 ? b : 0);
-                        }
+                        for (int r = 0; r < 16; ++r) v[r] = relu_i(acc[nt][r]);
                         const auto kk = split_store(v, op);
                         Packed kh = kk.first, kl = kk.second;
                         if constexpr (FLAT) {
@@ -1077,7 +990,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         constexpr bool EPI_EARLY = PF2;
         jitter(1);
         if constexpr (EPI_EARLY) epilogue();
-        lds_barrier4();                                   // every wave is done reading this stage's LDS image
+        lds_barrier();                                   // every wave is done reading this stage's LDS image
         jitter(2);
 #ifdef SS_DEVBUILD
         uint32_t tw_i = 0;
@@ -1095,7 +1008,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             jitter(4);
             epilogue();
             jitter(6);
-            lds_barrier4();
+            lds_barrier();
             jitter(5);
             cs = n1; n1 = n2;
             const bool more = ok1;
@@ -1107,7 +1020,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             if constexpr (FIRST) {
                 if constexpr (!SPLIT || NEXT == 0) {      // a new tile's features (f16x2: its first stage)
                     if (tid < (PR + 2) * FW) sF[tid] = rf;
-                    lds_barrier4();
+                    lds_barrier();
                 }
                 jitter(3);
                 produce(n1.d, NEXT);
@@ -1138,15 +1051,15 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             if (ok2) issue_weights(n2.d, n2.ci);
             if constexpr (SPLIT && RP > 0 && PART == 0) issue_proj(cur, ci >> 1, KZ_{}, KH_{});
             jitter(4);
-            lds_barrier4();
+            lds_barrier();
         } else if constexpr (FLAT) {
-            lds_barrier4();                               // the block's last stage: the previous tile's sums are read (flat_reduce
+            lds_barrier();                               // the block's last stage: the previous tile's sums are read (flat_reduce
         }                                                 // above) before this tile's epilogue overwrites them
         jitter(5);
         if constexpr (!EPI_EARLY) epilogue();
         if constexpr (FLAT) { flat_pending = last; flat_tile = cur; }
         if (!ok1) {
-            if constexpr (FLAT) { lds_barrier4(); if (flat_pending) flat_reduce(flat_tile); }
+            if constexpr (FLAT) { lds_barrier(); if (flat_pending) flat_reduce(flat_tile); }
             return false;
         }
         cs = n1; n1 = n2; ok1 = ok2;
@@ -1156,17 +1069,17 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
     if constexpr (DUO) {
         // beats: X = M B (C I E) B M ..., Y = B M B (C I E) B ...: Y starts one barrier late, X ends one barrier late
-        for (int i = 0; i < half; ++i) lds_barrier4();
+        for (int i = 0; i < half; ++i) lds_barrier();
         for (int s = 0; s < max_stages; s += SPLIT ? 2 : 1) {
             if (s < my_stages) {
                 stage(P0{}, ra0);
                 if constexpr (SPLIT) stage(P1{}, ra0);
             } else {                                      // out of stages: keep the beat (and a loader tile its duty)
-                lds_barrier4(); ring_duty(s, max_stages >> 1); lds_barrier4();
-                if constexpr (SPLIT) { lds_barrier4(); ring_duty(s + 1, max_stages >> 1); lds_barrier4(); }
+                lds_barrier(); ring_duty(s, max_stages >> 1); lds_barrier();
+                if constexpr (SPLIT) { lds_barrier(); ring_duty(s + 1, max_stages >> 1); lds_barrier(); }
             }
         }
-        for (int i = half; i < NH - 1; ++i) lds_barrier4();
+        for (int i = half; i < NH - 1; ++i) lds_barrier();
     } else if constexpr (SPLIT) {
         while (stage(P0{}, ra0) && stage(P1{}, ra0)) {}
     } else if constexpr (PF2) {
@@ -1193,237 +1106,12 @@ static hipError_t launch_v4_k(const ConvArgs& a, int total, int lds_b, size_t ld
     return hipGetLastError();
 }
 
-// DUO forms (f16x2, resident banks shared by the two halves): the plain A (RES) and B (RADD, + POOL) launches with 8-wave tiles
-// GRES (one channel group per workgroup, its banks resident): the B launches of the two-group 64 -> 64 blocks -- conv7.B (RADD), conv2_1.B
-// ("projection in B" + POOL; RADD + POOL when the development build switches the projection off)
-template <int NW, int NH, bool BRES, bool GRES = false>
-static hipError_t launch_v4_duo(const ConvArgs& a, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
-    if constexpr (GRES) {
-        static_assert(NH == 4 && NW == 4, "GRES: four 4-wave tiles");
-        if (a.proj_w) return a.pool_out ? launch_v4_k<1, NW, true, false, false, true, 1, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s)
-                                        : hipErrorInvalidValue;
-        if (a.pool_out) return launch_v4_k<1, NW, true, false, true, true, 0, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s);
-        return launch_v4_k<1, NW, true, false, true, false, 0, false, false, false, true, false, NH, true>(a, total, lds_b, lds, grid, s);
-    }
-    if constexpr (BRES && NH == 4) {
-        if (a.plain) return launch_v4_k<1, NW, true, false, false, false, 0, false, false, false, true, false, NH>(a, total, lds_b, lds, grid, s);
-    }
-    if (a.res_out) return launch_v4_k<1, NW, BRES, true, false, false, 0, false, false, false, true, false, NH>(a, total, lds_b, lds, grid, s);
-    if (a.pool_out) return launch_v4_k<1, NW, BRES, false, true, true, 0, false, false, false, true, false, NH>(a, total, lds_b, lds, grid, s);
-    return launch_v4_k<1, NW, BRES, false, true, false, 0, false, false, false, true, false, NH>(a, total, lds_b, lds, grid, s);
-}
-
-// f16x2 launches: A = RES (h and r out), B = RADD (+ POOL), conv9_1.B = RADD + FLAT, conv1_1.B = RANK1 + POOL
-template <int NT, int NW>
-static hipError_t launch_v4_split(const ConvArgs& a, bool bres, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
-    if constexpr (NT == 1 && NW == 8) {
-        if (a.rank1_src && a.first_w) return launch_v4_k<1, 8, true, false, false, true, 0, true, false, false, true, true>(a, total, lds_b, lds, grid, s);
-        if (a.rank1_src) return launch_v4_k<1, 8, true, false, false, true, 0, false, false, false, true, true>(a, total, lds_b, lds, grid, s);
-        if (a.flat_part && a.proj_w) return launch_v4_k<1, 8, true, false, false, false, 4, false, true, false, true>(a, total, lds_b, lds, grid, s);
-        if (a.flat_part) return launch_v4_k<1, 8, true, false, true, false, 0, false, true, false, true>(a, total, lds_b, lds, grid, s);
-        if (a.proj_w) return bres ? hipErrorInvalidValue : launch_v4_k<1, 8, false, false, false, true, 1, false, false, false, true>(a, total, lds_b, lds, grid, s);
-    }
-    if (a.res_out) return bres ? launch_v4_k<NT, NW, true, true, false, false, 0, false, false, false, true>(a, total, lds_b, lds, grid, s)
-                               : launch_v4_k<NT, NW, false, true, false, false, 0, false, false, false, true>(a, total, lds_b, lds, grid, s);
-    if (a.pool_out) return bres ? launch_v4_k<NT, NW, true, false, true, true, 0, false, false, false, true>(a, total, lds_b, lds, grid, s)
-                                : launch_v4_k<NT, NW, false, false, true, true, 0, false, false, false, true>(a, total, lds_b, lds, grid, s);
-    return bres ? launch_v4_k<NT, NW, true, false, true, false, 0, false, false, false, true>(a, total, lds_b, lds, grid, s)
-                : launch_v4_k<NT, NW, false, false, true, false, 0, false, false, false, true>(a, total, lds_b, lds, grid, s);
-}
-
-// two-stage prefetch where the launch is LDS-limited to two blocks per CU anyway (resident weights) and NT <= 2 keeps it under 128 registers
-static bool v4_pf2(bool bres, size_t lds, int NT, bool first, bool flat) {
-    static const int env = dev_env("SOFTSPOKEN_PF2", 1);
-    return env && bres && !first && !flat && NT <= 2 && lds * 3 > 160 * 1024;   // (callers exclude NT = 2 A launches: they would spill)
-}
-
-template <int NT, int NW, bool BRES, bool RES, bool RADD, bool POOL, int RP = 0, bool FIRST = false, bool FLAT = false>
-static hipError_t launch_v4_t(const ConvArgs& a, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
-    if constexpr (BRES && !FIRST && !FLAT && RP == 0 && NT <= 2 && NW == 8 && !(RES && NT == 2)) {
-        if (v4_pf2(true, lds, NT, false, false)) return launch_v4_k<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, true>(a, total, lds_b, lds, grid, s);
-    }
-    return launch_v4_k<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, false>(a, total, lds_b, lds, grid, s);
-}
-
-// K steps of the projection a stage of a "projection in B" launch carries: ceil(steps / chunks), one of 1, 2, 4
-static int v4_rp(const ConvArgs& a) {
-    if (!a.proj_w) return 0;
-    const int steps = (a.C0x + a.C1x) / 16, nch = (a.C0 + a.C1) / 32;
-    const int per = (steps + nch - 1) / nch;
-    return per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : per <= 6 ? 6 : -1;
-}
-
-template <int NT, int NW>
-static hipError_t launch_v4_kind(const ConvArgs& a, bool bres, int total, int lds_b, size_t lds, int grid, hipStream_t s) {
-    const int rp = v4_rp(a);
-    if constexpr (NT == 1 && NW == 8) {
-        if (a.first_w) return launch_v4_t<1, 8, true, false, false, true, 0, true>(a, total, lds_b, lds, grid, s);
-        if (a.flat_part) return rp == 4 ? launch_v4_t<1, 8, true, false, false, false, 4, false, true>(a, total, lds_b, lds, grid, s)
-                                        : launch_v4_t<1, 8, true, false, true, false, 0, false, true>(a, total, lds_b, lds, grid, s);
-    }
-    if (rp) {                                             // "projection in B" launches: the instantiations the network needs
-        if constexpr (NT == 2 && NW == 8) { if (bres && a.pool_out && rp == 1) return launch_v4_t<2, 8, true, false, false, true, 1>(a, total, lds_b, lds, grid, s); }
-        if constexpr (NT == 3 && NW == 8) { if (!bres && a.pool_out && rp == 2) return launch_v4_t<3, 8, false, false, false, true, 2>(a, total, lds_b, lds, grid, s); }
-        if constexpr (NT == 2 && NW == 8) { if (!bres && a.pool_out && rp == 2) return launch_v4_t<2, 8, false, false, false, true, 2>(a, total, lds_b, lds, grid, s); }
-        if constexpr (NT == 1 && NW == 4) { if (!bres && !a.pool_out && rp == 2) return launch_v4_t<1, 4, false, false, false, false, 2>(a, total, lds_b, lds, grid, s); }
-        if constexpr (NT == 2 && NW == 8) { if (bres && !a.pool_out && rp == 6) return launch_v4_t<2, 8, true, false, false, false, 6>(a, total, lds_b, lds, grid, s); }
-        return hipErrorInvalidValue;
-    }
-    if (a.plain) return bres ? launch_v4_t<NT, NW, true, false, false, false>(a, total, lds_b, lds, grid, s)
-                             : launch_v4_t<NT, NW, false, false, false, false>(a, total, lds_b, lds, grid, s);
-    if (a.res_out) return bres ? launch_v4_t<NT, NW, true, true, false, false>(a, total, lds_b, lds, grid, s)
-                               : launch_v4_t<NT, NW, false, true, false, false>(a, total, lds_b, lds, grid, s);
-    if (a.pool_out) return bres ? launch_v4_t<NT, NW, true, false, true, true>(a, total, lds_b, lds, grid, s)
-                                : launch_v4_t<NT, NW, false, false, true, true>(a, total, lds_b, lds, grid, s);
-    return bres ? launch_v4_t<NT, NW, true, false, true, false>(a, total, lds_b, lds, grid, s)
-                : launch_v4_t<NT, NW, false, false, true, false>(a, total, lds_b, lds, grid, s);
-}
-
-#ifndef SS_RPROJ_DEFAULT
-#define SS_RPROJ_DEFAULT 2
-#endif
-#ifndef SS_DUO_DEFAULT
-#define SS_DUO_DEFAULT 4
-#endif
-#ifndef SS_GRES_DEFAULT
-#define SS_GRES_DEFAULT 1
-#endif
-struct V4Choice { bool ok; int nw, total, lds_b, grid; bool bres; size_t lds; int duo; bool gres; };
-
-static V4Choice choose_v4(ConvArgs& a, int NT, int num_cus, int prec) {
-    V4Choice c{};
-    if (prec != 1 && prec != 2) return c;
-    const bool split = prec == 2;
-    if (!a.relu || a.R0 || a.R1) return c;
-    const bool first = a.first_w != nullptr, flat = a.flat_part != nullptr, proj = a.proj_w != nullptr;
-    const bool rank1 = split && a.rank1_src != nullptr;
-    if (split) {      // forms of the f16x2 mode: A with the r tensor, B adding it (+ pool, + flatten), conv1_1.B with the rank-1 residual
-        if (a.lo_delta <= 0) return c;
-        // "projection in B" (no r tensor): conv9_1.B (flatten form, four K steps on its one chunk) and conv2_1.B (two groups, pool, one
-        // step per chunk); their A launches are `plain` and exist in the four-tile resident form only (checked below)
-        // (conv9_1 in this form: A 4020 -> 3440 us per 1005 windows, its flatten B launch 2375 -> 2740 us with the four steps in two
-        // halves around part 1's loop -- with all eight fragments in flight at once it spilled 100 bytes and took 3640 us;
-        // SOFTSPOKEN_RPROJ in the dev build: 0 = no block, 1 = conv2_1 only, 2 = conv2_1 and conv9_1)
-        static const int rproj_env = dev_env("SOFTSPOKEN_RPROJ", SS_RPROJ_DEFAULT);
-        if (proj && !(NT == 1 && a.H % 16 == 0 && ((flat && v4_rp(a) == 4 && rproj_env == 2) || (!flat && a.pool_out && a.Cout == 64 && v4_rp(a) == 1)))) return c;
-        if (first && !rank1) return c;
-        if (rank1 && !(NT == 1 && a.rank1_w && a.pool_out && !a.res_out && !a.res_in && !flat && a.C0 == 32 && a.C1 == 0 && a.H % 16 == 0)) return c;
-        if (NT == 2 || !(NT == 1 || (a.H % 16 == 0))) return c;                                  // instantiated: NT = 1 (8- and 4-wave tiles), NT = 3 (8-wave)
-    }
-    const int rp = v4_rp(a);
-    if (flat && !(NT == 1 && a.Cout == 32 && a.C0 == 32 && a.C1 == 0 && a.H % 16 == 0 && a.flat_w4 && (a.res_in || rp == 4) && !a.pool_out && !first)) return c;
-    if (first) {                                                                                  // conv1_1.B: features in, c1 + p1 out
-        if (!(NT == 1 && a.Cout == 32 && a.C0 == 32 && a.C1 == 0 && a.H % 16 == 0 && a.first_b && a.rank1_src && a.rank1_w && a.pool_out &&
-              !a.res_out && !a.res_in && !proj && !a.plain)) return c;
-    } else if (proj) {                                                                            // B launch that computes the projection itself
-        if (a.rank1_src || a.res_out || a.res_in || a.plain || rp < 0 || !a.xp0 || a.C0x % 16 || a.C1x % 16 || (a.C1x && !a.xp1)) return c;
-        if (a.C0 != a.Cout || a.C1 != 0) return c;
-        if ((double)a.N * a.H * a.W * std::max(a.C0x, a.C1x) * 2.0 + kHdr >= 4294967296.0) return c;
-    } else if (a.plain) {                                                                         // A launch without the projection
-        if (a.rank1_src || a.res_out || a.res_in || a.pool_out) return c;
-    } else if (!rank1) {
-        if (a.rank1_src) return c;
-        if (!(a.res_out || a.res_in) || (a.res_out && (a.res_in || a.pool_out))) return c;        // A launch or B launch of a ResBlock
-    }
-    if (a.W % 16 != 0 || a.H % 8 != 0 || a.Cout % (32 * NT) != 0 || NT < 1 || NT > 3) return c;
-    if (a.C0 % 32 || a.C1 % 32 || (a.C1 && ((a.H | a.W) & 1))) return c;
-    if ((double)a.N * a.H * a.W * std::max(a.Cout, std::max(a.C0, a.C1)) * 2.0 + kHdr >= 4294967296.0) return c;   // 32-bit byte offsets
-    c.nw = (a.H % 16 == 0) ? 8 : 4;
-    const int th = 2 * c.nw;
-    a.tiles_y = a.H / th; a.tiles_x = a.W / 16;
-    const int ngroups = a.Cout / (32 * NT);
-    const long total_l = (long)a.N * a.tiles_y * a.tiles_x * ngroups;
-    if (total_l <= 0 || total_l > 0x7fffffff) return c;
-    c.total = (int)total_l;
-    const int tap_bytes = 2 * NT * 1024;
-    const int taps = a.res_out ? 10 : 9;
-    const int all_taps = ((a.C0 + a.C1) / 32) * taps;
-    static const int bres_kb = dev_env("SOFTSPOKEN_BRES_KB", 72);
-    const int banks = split ? 2 : 1;                                                              // f16x2: high and low halves of the weights
-    c.bres = ngroups == 1 && (size_t)all_taps * tap_bytes * banks <= (size_t)((first || flat || rank1) ? 72 : bres_kb) * 1024;
-    c.lds_b = c.bres ? all_taps * tap_bytes * banks : taps * tap_bytes * banks;
-    if ((first || flat || rank1) && !c.bres) return c;
-    if (proj && !flat && !((NT == 2 && c.nw == 8 && c.bres && a.pool_out && rp == 1) ||                       // conv2_1
-                           (NT == 3 && c.nw == 8 && !c.bres && ngroups == 1 && a.pool_out && rp == 2) ||      // conv3_1
-                           (NT == 2 && c.nw == 8 && !c.bres && ngroups > 1 && a.pool_out && rp == 2) ||       // conv4_1
-                           (NT == 1 && c.nw == 4 && !c.bres && ngroups > 1 && !a.pool_out && rp == 2) ||      // conv_bottleneck, encoder_out
-                           (split && NT == 1 && c.nw == 8 && !c.bres && ngroups > 1 && a.pool_out && rp == 1) ||      // conv2_1 in f16x2
-                           (NT == 2 && c.nw == 8 && c.bres && !a.pool_out && rp == 6)))                       // conv7: its A launch gains more
-                                                                                                              // (473 -> 349 us) than B loses (165 -> 222);
-                                                                                                              // conv8 in this form: -46 / +144 us, not taken
-        return c;                                                                                 // instantiated forms
-    // DUO (conv3x3_v4_kernel): several tiles per 16-wave workgroup, a beat apart; one workgroup per CU.  2 x 8 waves or 4 x 4 waves
-    // (SOFTSPOKEN_DUO in the dev build: 0, 2, 4)
-    static const int duo_env = dev_env("SOFTSPOKEN_DUO", SS_DUO_DEFAULT);
-    // (the four-tile form's tiles are 8 rows: it also takes the 8 x 16 level -- conv_bottleneck.A / encoder_out.A over the bank ring, one
-    // whole picture per tile -- where the independent 4-wave blocks ran at 190 TFLOP/s)
-    static const int duo8_env = dev_env("SOFTSPOKEN_DUO_H8", 1);
-    // GRES: one channel group per workgroup, that group's banks resident (kernels.h: gres_item).  A B launch with several groups whose
-    // ONE group's banks fit beside the patches: the 64 -> 64 blocks' (72 KB per group) -- conv7.B over four 8-row tiles, conv2_1.B
-    // ("projection in B") likewise.  The other forms stage those 72 KB per (tile, group) or per quad.  conv2_1.B as two 16-row tiles with
-    // the banks resident measured the same as the four 8-row tiles (tools/experiments/r06_conv2_1B_resident_two_tiles.patch).
-    // (SOFTSPOKEN_GRES=0 in the dev build: the forms below, as before)
-    static const int gres_env = dev_env("SOFTSPOKEN_GRES", SS_GRES_DEFAULT);
-    if (gres_env && duo_env == 4 && split && NT == 1 && ngroups > 1 && !first && !flat && !rank1 && !a.plain && !a.res_out &&
-        (proj ? (a.pool_out && rp == 1 && c.nw == 8) : a.res_in != nullptr) && (c.nw == 8 || duo8_env)) {
-        const int nh = 4, thd = 32 / nh;
-        const size_t group_b = (size_t)all_taps * tap_bytes * banks;
-        const size_t proj_b = proj ? (size_t)((a.C0x + a.C1x) / 16) * (a.Cout / 32) * 1024 * banks : 0;
-        const size_t lds = nh * (size_t)(thd + 2) * kRowPitch + group_b + proj_b + (size_t)a.Cout * 4;
-        const long total_pos = (long)a.N * (a.H / thd) * a.tiles_x;
-        const int grid = total_pos <= 0x7fffffff / ngroups ? gres_grid(num_cus, (int)total_pos, ngroups, nh) : 0;
-        if (lds <= 160 * 1024 && gres_grid_ok(grid, ngroups)) {
-            c.duo = nh; c.gres = true; c.bres = true; c.lds_b = (int)group_b; c.lds = lds;
-            c.nw = 16 / nh;
-            a.tiles_y = a.H / thd;
-            c.total = (int)(total_pos * ngroups);
-            c.grid = grid;
-            c.ok = true;
-            return c;
-        }
-    }
-    if ((duo_env == 2 || duo_env == 4) && split && NT == 1 && (c.nw == 8 || (duo_env == 4 && duo8_env)) && !first && !flat && !proj && !rank1) {
-        const int nh = duo_env, thd = 32 / nh;           // tile rows: 16 (8 waves) or 8 (4 waves)
-        const size_t fixed = nh * (size_t)(thd + 2) * kRowPitch + (size_t)a.Cout * 4 * (a.res_out ? 2 : 1);
-        const size_t chunk_b = (size_t)taps * tap_bytes * banks;
-        const size_t all_b = (size_t)ngroups * all_taps * tap_bytes * banks;    // every channel group's banks (conv2_1.A: 2 x 40 KB)
-        const bool bres = fixed + all_b <= 160 * 1024;
-        static const int ring_env = dev_env("SOFTSPOKEN_RING", 1);
-        // streamed banks: a two-slot ring shared by the four tiles.  A launches: conv7.A 1440 -> 1370 us, conv8.A 2040 -> 1960 us,
-        // conv4_1.A 415 -> 390 us per 1005 windows.  B launches (residual loads, the long epilogue): the large ones lost 6-7 % in this
-        // form in round 2; from the 32 x 64 level down it wins (round 3, same box: conv_bottleneck.B / encoder_out.B 186 -> 128 us,
-        // conv4_1.B 515 -> 500, conv7.B 564 -> 556; the 96-channel blocks' B launches as three groups: conv3_1.B 1233 -> 1197, conv6.B 306 -> 289)
-        const bool ring = !bres && nh == 4 && ring_env && (a.res_out != nullptr || ring_env == 2 || (a.H <= 32 && a.res_in != nullptr));
-        const size_t lds = fixed + (bres ? all_b : 2 * chunk_b);
-        // measured (tools/ab_layers.sh, f16x2, 1005 windows, alternating runs on one box): with shared resident banks conv9_1.A
-        // 4820 -> 4440 us as 2 x 8 waves and -> 4020 us as 4 x 4 waves (its 80 KB of banks fit beside the patches but not twice
-        // beside one), conv8.B 650 -> 607 us (4 x 4); with streamed banks the 2 x 8 form lost 2-8 % (a half's bank commit sits in
-        // the other half's multiply phase); conv9_1.B (FLAT) as 4 x 4: 2765 -> 2946 us, not taken (its epilogue is the long
-        // phase, and the 8-row tiles read 11 % more halo)
-        if (((bres && (!a.plain || nh == 4)) || (ring && !a.plain)) && lds <= 160 * 1024) {
-            c.duo = nh; c.bres = bres; c.lds_b = (int)(bres ? all_b : chunk_b); c.lds = lds;
-            c.nw = 16 / nh;
-            a.tiles_y = a.H / thd;
-            c.total = (int)((long)a.N * a.tiles_y * a.tiles_x * ngroups);
-            c.grid = (num_cus + 7) / 8 * 8;
-            if (c.grid * nh > c.total) c.grid = ((c.total + nh - 1) / nh + 7) / 8 * 8;
-            c.ok = true;
-            return c;
-        }
-    }
-    if (split && a.plain) return c;                       // (f16x2 plain A launches: the four-tile resident form above or none)
-    c.lds = (size_t)(th + 2) * kRowPitch + c.lds_b + (size_t)a.Cout * 4 * (a.res_out ? 2 : 1) + (first ? (size_t)(32 + (th + 5) * 20) * 4 : 0) +
-            (flat ? (size_t)c.nw * 2 * 64 * 4 : 0) + (proj && (ngroups == 1 || split) ? (size_t)((a.C0x + a.C1x) / 16) * (split ? a.Cout / 32 : NT) * 1024 * banks : 0);
-    int bpc = (int)((160 * 1024) / c.lds);
-    if (bpc < 1) return c;
-    if (bpc > 3) bpc = 3;
-    { static const int cap = dev_env("SOFTSPOKEN_BPC", 3); if (bpc > cap) bpc = cap; }      // (dev build: fewer blocks per CU)
-    c.grid = num_cus * bpc;
-    if (c.grid > c.total) c.grid = c.total;
-    c.grid = (c.grid + 7) / 8 * 8;
-    c.ok = true;
-    return c;
-}
+// the launch table: entry i launches the instantiation of kV4Forms[i] (conv4_forms.h: one list expands into both)
+typedef hipError_t (*V4Launch)(const ConvArgs&, int, int, size_t, int, hipStream_t);
+#define SS_V4_LAUNCH(...) &launch_v4_k<__VA_ARGS__>,
+static const V4Launch kV4Launch[] = {SS_V4_FORMS(SS_V4_LAUNCH)};
+#undef SS_V4_LAUNCH
+static_assert(sizeof kV4Launch / sizeof kV4Launch[0] == kV4FormCount, "one launch function per form");
 
 int conv_v4_flat_groups() { return 128 / 16; }
 
@@ -1432,58 +1120,18 @@ bool conv_v4_supports(const ConvArgs& a_in, int NT, int num_cus, int prec) {
     return choose_v4(a, NT, num_cus, prec).ok;
 }
 
-// conv3x3_v4_kernel<NT, NW, BRES, RES, RADD, POOL, RP, FIRST, FLAT, PF2, SPLIT, RANK1, NH, GRES> as rocprofv3 prints it
 const char* conv_v4_variant(const ConvArgs& a_in, int NT, int num_cus, int prec) {
-    static thread_local char buf[128];
     ConvArgs a = a_in;
     const V4Choice c = choose_v4(a, NT, num_cus, prec);
-    if (!c.ok) return "conv3x3_v4_kernel<invalid>";
-    auto tf = [](bool b) { return b ? "true" : "false"; };
-    const bool res = a.res_out != nullptr, first = a.first_w != nullptr, flat = a.flat_part != nullptr;
-    const int rp = v4_rp(a);
-    const bool split = prec == 2, rank1 = split && a.rank1_src != nullptr;
-    const bool radd = !res && !first && !a.plain && rp == 0 && !rank1;
-    const bool pf2 = !split && rp == 0 && c.nw == 8 && !(res && NT == 2) && v4_pf2(c.bres, c.lds, NT, first, flat);
-    if (split)
-        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, false, true, %s, %d, %s>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
-                 tf(!res && a.pool_out), rp, tf(first), tf(flat), tf(rank1), c.duo ? c.duo : 1, tf(c.gres));
-    else
-        snprintf(buf, sizeof buf, "conv3x3_v4_kernel<%d, %d, %s, %s, %s, %s, %d, %s, %s, %s, false, false, 1, false>", NT, c.nw, tf(c.bres), tf(res), tf(radd),
-                 tf(!res && a.pool_out), rp, tf(first), tf(flat), tf(pf2));
-    return buf;
+    return c.ok ? v4_form_name(c.form) : "conv3x3_v4_kernel<invalid>";
 }
 
 hipError_t launch_conv3x3_v4(const ConvArgs& a_in, int NT, int num_cus, int prec, hipStream_t s) {
     ConvArgs a = a_in;
     const V4Choice c = choose_v4(a, NT, num_cus, prec);
-    if (!c.ok) return hipErrorInvalidValue;
-    if (prec == 2) {
-        if (c.gres) return launch_v4_duo<4, 4, true, true>(a, c.total, c.lds_b, c.lds, c.grid, s);
-        if (c.duo == 2) return launch_v4_duo<8, 2, true>(a, c.total, c.lds_b, c.lds, c.grid, s);
-        if (c.duo == 4) return c.bres ? launch_v4_duo<4, 4, true>(a, c.total, c.lds_b, c.lds, c.grid, s)
-                                      : launch_v4_duo<4, 4, false>(a, c.total, c.lds_b, c.lds, c.grid, s);
-        if (c.nw == 8) {
-            switch (NT) {
-                case 1: return launch_v4_split<1, 8>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-                case 3: return launch_v4_split<3, 8>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-            }
-        } else if (NT == 1) return launch_v4_split<1, 4>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-        return hipErrorInvalidValue;
-    }
-    if (c.nw == 8) {
-        switch (NT) {
-            case 1: return launch_v4_kind<1, 8>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-            case 2: return launch_v4_kind<2, 8>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-            case 3: return launch_v4_kind<3, 8>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-        }
-    } else {
-        switch (NT) {
-            case 1: return launch_v4_kind<1, 4>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-            case 2: return launch_v4_kind<2, 4>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-            case 3: return launch_v4_kind<3, 4>(a, c.bres, c.total, c.lds_b, c.lds, c.grid, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    const int i = c.ok ? v4_form_index(c.form) : -1;
+    if (i < 0) return hipErrorInvalidValue;
+    return kV4Launch[i](a, c.total, c.lds_b, c.lds, c.grid, s);
 }
 
 }  // namespace ss

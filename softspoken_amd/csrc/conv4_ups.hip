@@ -24,6 +24,7 @@
 // resident -- conv9_1.A (32 skip + 32 upsampled channels: 36 + 64 KB of banks beside 4 x 14.4 KB of patches).  The other decoder blocks'
 // A launches stream their banks through conv4.hip's two-slot ring, which the class banks outgrow.
 #include "kernels.h"
+#include "mfma_util.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -31,15 +32,6 @@ namespace ss {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kHdr = 256;            // zero bytes in front of every activation tensor (engine.hip ensure_workspace)
 constexpr int kPix = 80;             // pixel pitch in LDS: 64 bytes of channels + 16
 constexpr int kRowR = 1472;          // skip-channel patch row: 9 even columns, 9 odd columns, 32 bytes of padding
 constexpr int kOdd = 720;            // offset of a row's odd columns
@@ -48,50 +40,6 @@ constexpr int kLowPlane = 6 * kRowU;                      // low-resolution patc
 constexpr int kPatchBytes = 10 * kRowR;                   // (the two low-resolution planes, 2 x 5376, live in the same buffer)
 constexpr int kBankR = 9 * 2048, kBankU = 16 * 2048;      // one bank (high or low halves) of a skip chunk / of an upsampled chunk
 constexpr int NW = 4, NH = 4, NTHR = 64 * NW;
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void vm_lds_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ uint32_t pack_f16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-__device__ __forceinline__ f32x2 unpack_f16(uint32_t v) { return __builtin_convertvector(__builtin_bit_cast(f16x2, v), f32x2); }
-// the largest high half seen so far, per 16-bit lane (the values are >= 0 behind the ReLU: as unsigned integers they order like the
-// values, infinity and NaN on top): one instruction per pair; the test for "all exponent bits set" happens once, on the maximum
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// lo = f16(x - hi) of a pair whose high halves are packed in `hi`: the mixed-precision FMA reads the f16 half and the fp32 value, subtracts in
-// fp32 (exactly: hi is x rounded) and rounds to f16 into one half of the destination -- two instructions for the pair instead of two
-// conversions back, two subtractions and a pack; bit for bit the same (tools/probes/fma_mix_split.hip)
-__device__ __forceinline__ uint32_t split_lo(uint32_t hi, float x0, float x1) {
-    uint32_t l;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi), "v"(x0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(hi), "v"(x1));
-    return l;
-}
-__device__ __forceinline__ f32x16 mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void half_swap(uint32_t& x, uint32_t& y) {
-    const u32x2 r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-    x = r[0]; y = r[1];
-}
-struct Packed { uint32_t p[4][2]; };
-// as conv4.hip: after the swaps a lane holds channels [8 hh, 8 hh + 8) in lo and [16 + 8 hh, 16 + 8 hh + 8) in hi
-__device__ __forceinline__ void to_runs(Packed& k, u32x4& lo, u32x4& hi) {
-    half_swap(k.p[0][0], k.p[1][0]); half_swap(k.p[0][1], k.p[1][1]);
-    half_swap(k.p[2][0], k.p[3][0]); half_swap(k.p[2][1], k.p[3][1]);
-    lo = u32x4{k.p[0][0], k.p[0][1], k.p[1][0], k.p[1][1]};
-    hi = u32x4{k.p[2][0], k.p[2][1], k.p[3][0], k.p[3][1]};
-}
-
-#ifdef SS_DEVBUILD
-int dev_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#else
-constexpr int dev_env(const char*, int dflt) { return dflt; }
-#endif
 
 }  // namespace
 
@@ -242,11 +190,7 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     int jit_n = 0;
     auto jitter = [&](int site) {
 #ifdef SS_DEVBUILD
-        if (a.dbg & 1024) {
-            const int pat = (a.dbg >> 11) & 3, w16 = half * NW + wave;
-            const bool z = pat == 0 ? ((w16 + site + jit_n) & 3) == 0 : pat == 1 ? w16 == 0 : pat == 2 ? w16 != 0 : (w16 & 1) != 0;
-            if (z) __builtin_amdgcn_s_sleep(32);
-        }
+        SS_JITTER_SLEEP(a.dbg, half * NW + wave, site, jit_n)
 #else
         (void)site;
 #endif
@@ -283,8 +227,8 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             for (int st = 0; st < 18; ++st) {
                 if (st + PM - 1 < 18) load3(st + PM - 1, (st + PM - 1) % PM);
                 const u32x4 pixv = pf[st % PM];
-                acc = mfma(wh_[st % PM], pixv, acc);
-                if constexpr (PART == 1) acc = mfma(wl_[st % PM], pixv, acc);
+                acc = mfma16<true>(wh_[st % PM], pixv, acc);
+                if constexpr (PART == 1) acc = mfma16<true>(wl_[st % PM], pixv, acc);
             }
         };
         using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
@@ -307,9 +251,9 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
 #pragma unroll
             for (int st = 0; st < 8; ++st) {
                 if (st + 1 < 8) load4(st + 1, (st + 1) % PM);
-                acc = mfma(wh_[st % PM], pl[st % PM], acc);
-                acc = mfma(wl_[st % PM], ph[st % PM], acc);
-                acc = mfma(wh_[st % PM], ph[st % PM], acc);
+                acc = mfma16<true>(wh_[st % PM], pl[st % PM], acc);
+                acc = mfma16<true>(wl_[st % PM], ph[st % PM], acc);
+                acc = mfma16<true>(wh_[st % PM], ph[st % PM], acc);
             }
         }
         if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);
@@ -331,9 +275,7 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     // ReLU as an integer max (negative floats are negative integers), then hi = f16(v), lo = f16(v - hi)
-                    const float a0 = acc[4 * g + 2 * h], a1 = acc[4 * g + 2 * h + 1];
-                    const int b0 = __builtin_bit_cast(int, a0), b1 = __builtin_bit_cast(int, a1);
-                    const float x0 = __builtin_bit_cast(float, b0 > 0 ? b0 : 0), x1 = __builtin_bit_cast(float, b1 > 0 ? b1 : 0);
+                    const float x0 = relu_i(acc[4 * g + 2 * h]), x1 = relu_i(acc[4 * g + 2 * h + 1]);
                     kh.p[g][h] = pack_f16(x0, x1);
                     ovf = pk_max_u16(ovf, kh.p[g][h]);
                     kl.p[g][h] = split_lo(kh.p[g][h], x0, x1);
@@ -583,7 +525,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     __syncthreads();
 
     f32x16 acc, racc;
-    auto mm = [&](const u32x4& w, const u32x4& x, const f32x16& c) -> f32x16 { return SS_ABL(16) ? c : mfma(w, x, c); };
+    auto mm = [&](const u32x4& w, const u32x4& x, const f32x16& c) -> f32x16 { return SS_ABL(16) ? c : mfma16<true>(w, x, c); };
     const int base_r = 2 * Y * kRowR + X * kPix + hh * 16;
     const int base_u = Y * kRowU + X * kPix + hh * 16;
     const int boff0 = lane * 16;
@@ -623,11 +565,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
             if (site != 0 || jit_n > 1) st_sum[seg] += t - st_prev;
             st_prev = t;
         }
-        if (a.dbg & 1024) {
-            const int pat = (a.dbg >> 11) & 3, w16 = half * NW + wave;
-            const bool z = pat == 0 ? ((w16 + site + jit_n) & 3) == 0 : pat == 1 ? w16 == 0 : pat == 2 ? w16 != 0 : (w16 & 1) != 0;
-            if (z) __builtin_amdgcn_s_sleep(32);
-        }
+        SS_JITTER_SLEEP(a.dbg, half * NW + wave, site, jit_n)
 #else
         (void)site;
 #endif
@@ -645,9 +583,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 // ReLU as an integer max (negative floats are negative integers), then hi = f16(v), lo = f16(v - hi)
-                const float a0 = acc_done[4 * g + 2 * h], a1 = acc_done[4 * g + 2 * h + 1];
-                const int b0 = __builtin_bit_cast(int, a0), b1 = __builtin_bit_cast(int, a1);
-                const float x0 = __builtin_bit_cast(float, b0 > 0 ? b0 : 0), x1 = __builtin_bit_cast(float, b1 > 0 ? b1 : 0);
+                const float x0 = relu_i(acc_done[4 * g + 2 * h]), x1 = relu_i(acc_done[4 * g + 2 * h + 1]);
                 kh.p[g][h] = pack_f16(x0, x1);
                 ovf = pk_max_u16(ovf, kh.p[g][h]);
                 kl.p[g][h] = split_lo(kh.p[g][h], x0, x1);

@@ -38,15 +38,6 @@ const char* thread_error();
             return ss::fail((c), SS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
-// Development switches (tools/, tests of alternate kernel forms): compiled into libsoftspoken_hip_dev.so only (-DSS_DEVBUILD).
-// The product library has every default fixed at build time and reads two environment variables in all: SOFTSPOKEN_CHUNK and
-// SOFTSPOKEN_PRECISION.
-#ifdef SS_DEVBUILD
-int dev_env(const char* name, int dflt);
-#else
-inline int dev_env(const char*, int dflt) { return dflt; }
-#endif
-
 // ---- weights blob ("SSWBLOB1") ---------------------------------------------------------------------------
 struct BlobEntry { char name[96]; uint32_t dtype, ndim; int64_t shape[4]; uint64_t offset, nbytes; };
 static_assert(sizeof(BlobEntry) == 152, "blob entry layout");

@@ -23,10 +23,6 @@ int fail(ss_ctx* c, int code, const std::string& msg) {
 }
 const char* thread_error() { return g_err.c_str(); }
 
-#ifdef SS_DEVBUILD
-int dev_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#endif
-
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static int stat_id(ss_ctx* c, const std::string& name) {

@@ -13,7 +13,7 @@
 namespace ss {
 
 // timing-only ablation bits of FrontendTables::dbg (results are wrong with them set).  Only the dev build's host code can set
-// them (engine.hip: dev_env); the kernel tests them at run time in both builds on purpose: with the tests folded away the compiler
+// them (kernels.h: dev_env); the kernel tests them at run time in both builds on purpose: with the tests folded away the compiler
 // schedules the frame loop differently and spills (256 VGPRs + 796 bytes of scratch per lane, 3.6 x slower on the GPU).
 #define SS_FEDBG(tb) ((tb).dbg)
 

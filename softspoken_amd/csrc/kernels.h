@@ -4,8 +4,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cstdlib>
 
 namespace ss {
+
+// Development switches (tools/, tests of alternate kernel forms): compiled into libsoftspoken_hip_dev.so only (-DSS_DEVBUILD).
+// The product library has every default fixed at build time and reads two environment variables in all: SOFTSPOKEN_CHUNK and
+// SOFTSPOKEN_PRECISION.
+#ifdef SS_DEVBUILD
+static inline int dev_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+#else
+static constexpr int dev_env(const char*, int dflt) { return dflt; }
+#endif
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: a process with contexts on several devices
 // (ss_create takes a device id) must set it on each, and contexts run on several host threads.  done: one bit per device, per kernel.
