@@ -6,7 +6,9 @@
  * point below names the reference code it stands behind (paths relative to the reference root):
  *
  *   ss_wav_parse, ss_resampled_length      root/code/backend/voice_activity.py:23-30   get_audio_data
- *   ss_plan_windows                        root/code/frontend/NNDetector.py:55-82      plan_detection_job
+ *   ss_plan_windows / ss_plan_windows_step root/code/frontend/NNDetector.py:55-82      plan_detection_job
+ *   ss_window_start_bin,                   NNDetector.py:69,175 + root/code/backend/settings.py:16   settings.step_size
+ *   ss_set_window_step / ss_get_window_step
  *   ss_create / ss_destroy                 NNDetector.py:21-34,42-53                   model build + load_checkpoint
  *   ss_upload_wav_batch_async              root/code/backend/worker.py:57 -> voice_activity.py:37 (sf.read of every file of the job)
  *   ss_add_pcm / ss_add_pcm_device /       voice_activity.py:32-69 load_audio  +  root/code/backend/worker.py:58-62 (3 s pad)
@@ -45,7 +47,10 @@ extern "C" {
 /* fixed properties of the path (reference settings.py:4-16, NNDetector.py:69-75) */
 #define SS_SAMPLE_RATE 22050
 #define SS_WINDOW_SAMPLES 66150   /* 3 s */
-#define SS_STEP_SAMPLES 13230     /* floor(22050 * 0.6) */
+#define SS_STEP_SAMPLES 13230     /* floor(22050 * 0.6): the sample step of the default window step (ss_set_window_step) */
+#define SS_STEP_DEFAULT 0.6       /* settings.py:16 step_size, seconds */
+#define SS_STEP_MIN 0.1           /* window steps a context accepts: SS_STEP_MIN <= step_s <= SS_STEP_MAX, finite */
+#define SS_STEP_MAX 3.0
 #define SS_N_MELS 128
 #define SS_N_FRAMES 256           /* time bins per window */
 
@@ -129,6 +134,15 @@ int64_t ss_resampled_length(int64_t frames, int sample_rate);
 /* Window start table of one file.  Returns the number of windows W (also when starts == NULL);
  * writes min(W, cap) entries.  starts[i] = i * 13230 into the 3 s-padded signal. */
 int64_t ss_plan_windows(double duration_s, int64_t* starts, int64_t cap);
+/* The same for a window step of step_s seconds (settings.step_size, NNDetector.py:69-78): per_step = floor(22050.0 * step_s),
+ * W = ceil((round(duration_s * 22050) + 6 * 22050 - 66150) / per_step), starts[i] = i * per_step.  ss_plan_windows(d, ...) is
+ * ss_plan_windows_step(d, 0.6, ...).  Returns -1 for a step outside [SS_STEP_MIN, SS_STEP_MAX] or not finite. */
+int64_t ss_plan_windows_step(double duration_s, double step_s, int64_t* starts, int64_t cap);
+/* First averaged bin of window i (NNDetector.py:175): int(round(i * step_size / (3 / 256))) as Python evaluates it -- the double
+ * product, the double quotient, then the nearest integer with ties to even (99 / 512 s gives 16.5 i: 16, 33, 50, 66, 82).  The sample
+ * step is floored and the bin step is not, so the two drift apart where 22050 * step_s is no integer (99 / 512 s: 0.48 s per hour of
+ * audio); that is the reference's arithmetic and it is reproduced, not corrected.  Returns -1 for a bad step or i < 0. */
+int64_t ss_window_start_bin(int64_t i, double step_s);
 /* Threshold + run-length + gap merge on averaged logits (double), exactly as the reference does it
  * through "%.4f" time strings; bin_idx[i] is the bin number of avg[i].  Returns regions in seconds
  * minus 3.  *n_out receives the number found; SS_ERR_CAPACITY if it exceeds cap. */
@@ -153,6 +167,17 @@ int ss_create(int device_id, const void* weights_blob, size_t nbytes, uint32_t f
 void ss_destroy(ss_ctx* ctx);
 /* windows processed per pass through the conv stack (activation workspace is sized for this) */
 int ss_set_chunk_windows(ss_ctx* ctx, int chunk);
+/* The window step of the context, seconds (settings.step_size; default SS_STEP_DEFAULT): ss_run, ss_run_begin*, ss_run_from_logits and
+ * the streams opened from now on plan with ss_plan_windows_step(duration, step_s) and average window i from bin
+ * ss_window_start_bin(i, step_s).  Accepted: SS_STEP_MIN <= step_s <= SS_STEP_MAX, finite -- inside that range every bin up to the last
+ * window's end has a window and at most 31 windows cover a bin; above 3 s bins between windows would have none; anything else is
+ * SS_ERR_ARG.  SS_ERR_STATE while a run is in flight.  The last ended run's results and getters are untouched, and a stream keeps the
+ * step it was opened with (or its image's, ss_stream_import).  With the default step every result is bit for bit what it was before
+ * the step could be set.  NOT following the step: ss_infer_windows and ss_features take explicit starts, and the separation silencer
+ * (ss_separation_plan / ss_separation_maps / ss_separate_pcm) stays on 0.6 s whatever the context's step -- its output is defined
+ * independently of detection settings, so that two users get the same bytes. */
+int ss_set_window_step(ss_ctx* ctx, double step_s);
+double ss_get_window_step(ss_ctx* ctx);   /* -1 for a NULL context */
 
 /* ---- signal arena: files of the current job, resident in HBM ------------------------------- */
 int ss_reset(ss_ctx* ctx);
@@ -234,8 +259,8 @@ int ss_features(ss_ctx* ctx, int file_id, const int64_t* starts, int n, float* f
 /* process_batch: mask_out[n][256] raw logits; spec_out (nullable) [n][2][128][256]. Any n >= 1. */
 int ss_infer_windows(ss_ctx* ctx, int file_id, const int64_t* starts, int n, float* mask_out, float* spec_out);
 /* Whole job over every file added since ss_reset: plan windows from each file's header duration,
- * front-end + conv stack over all windows in chunks (across file boundaries), overlap averaging on
- * the device, region finding on the host.  stop_flag (nullable) is polled between chunks. */
+ * (ss_plan_windows_step with the context's window step, ss_set_window_step), front-end + conv stack over all windows in chunks
+ * (across file boundaries), overlap averaging on the device, region finding on the host.  stop_flag (nullable) is polled between chunks. */
 int ss_run(ss_ctx* ctx, double threshold, double break_s, ss_progress_fn progress, void* user,
            const volatile int* stop_flag);
 /* The same job in two halves (worker.py:49-100 has no counterpart: its loop is synchronous).  ss_run_begin plans and enqueues
@@ -282,11 +307,11 @@ int ss_get_region_peaks(ss_ctx* ctx, int first_file, int n_channels, double* pea
 
 /* ---- streaming detection: one recording's PCM arriving in pieces, its final regions returned early -----------------------
  * A stream is one recording in one enum ss_pcm_format encoding, rate and channel count (the limits of ss_add_pcm), pushed in pieces
- * of any size down to one frame; its threshold and break are fixed when it is opened.  Each step takes every stream of the context as
+ * of any size down to one frame; its threshold, break and window step (the context's, ss_set_window_step) are fixed when it is opened.  Each step takes every stream of the context as
  * far as its pushed audio allows -- decode + mixdown + resample with carried state, every window that has become complete (in passes
  * of up to ss_set_chunk_windows windows, mixed across streams), the averaging of the bins that became final, the regions -- and
  * returns what became final.  Equality: the concatenation of every region and every averaged bin a stream returned equals what
- * ss_add_pcm + ss_run(threshold, break_s) give for the same frames on a context of the same precision (regions as ss_region values,
+ * ss_add_pcm + ss_run(threshold, break_s) give for the same frames on a context of the same precision and window step (regions as ss_region values,
  * averages as doubles, bit for bit), for any split into pieces, any cadence of steps and whichever streams shared the passes.
  * Returned results are final (never changed or withdrawn).
  *
@@ -294,14 +319,16 @@ int ss_get_region_peaks(ss_ctx* ctx, int first_file, int n_channels, double* pea
  * stream holds audio past t + B, and a region whose last above-threshold bin lies at t_end by the first step after it holds audio
  * past t_end + break_s + B, where
  *     B = 3 s + 2 x (3 / 256) s + half / sample_rate,        half = ceil(32 / min(1, 22050 / sample_rate)) (0 at 22 050 Hz):
- * the last window over a bin ends at most 3 s of audio after it (plus half a bin of the rounded start round(51.2 i)), the gap test
+ * the last window over a bin ends at most 3 s of audio after it (plus half a bin of the rounded start, ss_window_start_bin; the sample
+ * step is floored, so a window's audio never lies later than its nominal time i x step: B holds for every window step), the gap test
  * of a region needs one more bin past t_end + break_s (the 4-decimal rounding of bin times is below a bin), and a resampled sample
  * waits for `half` input frames after it.  16 kHz: 3.0254 s; 44.1 / 48 kHz: 3.0249 s; 8 kHz: 3.0274 s.  The bins and regions of
  * the last seconds are final at close, as in ss_run (the plan's window and bin counts depend on the total duration).
  *
- * State.  Between steps a stream holds the 22 050 Hz samples from its first window not yet run (< 3.6 s), its resampler's input
- * history (< 2 half + 1 frames), the logits of the <= 6 windows over its non-final bins, its open region and counters: a size that
- * does not grow with the stream.  Pushed pieces wait in library-owned host staging until a step takes them.
+ * State.  Between steps a stream holds the 22 050 Hz samples from its first window not yet run (< 3 s + step: 3.6 s at the default), its
+ * resampler's input history (< 2 half + 1 frames), the logits of the <= ceil(256 / s_b) + 1 windows over its non-final bins (s_b =
+ * step x 256 / 3 bins per window: 6 windows at the default, 31 at 0.1 s), its open region and counters: a size that does not grow with
+ * the stream.  Pushed pieces wait in library-owned host staging until a step takes them.
  * Streams and the job calls share a context without touching each other: a step reads none of the files, results or getters of
  * the last ended run, ss_run / ss_reset leave the streams alone; a step while ss_run_begin is in flight is SS_ERR_STATE. */
 typedef struct ss_stream_info {
@@ -337,7 +364,9 @@ int ss_stream_get_info(ss_ctx* ctx, int stream_id, ss_stream_info* out);
 int ss_stream_free(ss_ctx* ctx, int stream_id);
 /* A stream's whole state (staging included, the last step's results excluded) as a byte image: *n_out = its size (buf may be NULL
  * to ask); SS_ERR_CAPACITY when cap is smaller.  ss_stream_import makes a new stream of another (or the same) context from it --
- * of any precision: what the f16x2 fallback and a feed that moves to another device need. */
+ * of any precision: what the f16x2 fallback and a feed that moves to another device need.  The image carries the stream's window
+ * step (a stream with the default step writes the image it always wrote, "SSSTRM01"; any other step writes "SSSTRM02", the step appended
+ * to the header); ss_stream_import reads both and the new stream keeps the image's step whatever the context's. */
 int ss_stream_export(ss_ctx* ctx, int stream_id, void* buf, int64_t cap, int64_t* n_out);
 int ss_stream_import(ss_ctx* ctx, const void* buf, int64_t n, int* stream_id);
 
@@ -348,7 +377,8 @@ int ss_stream_import(ss_ctx* ctx, const void* buf, int64_t n, int* stream_id);
  * (pytorch_neural_nets.py:125-130,184-185: "env / speech separation", a ReLU'd (2, 128, 256) map per window that process_batch
  * returns as speech_pred, NNDetector.py:84-101, and worker.py:78-79 drops).  Outside the intervals the output is bit for bit
  * ss_silence_pcm's.  Definition, step by step:
- *  1. Windows and bins follow the detector: ss_plan_windows' windows over the ss_add_pcm signal, window i covers the bins
+ *  1. Windows and bins follow the detector at its default window step of 0.6 s (whatever ss_set_window_step says: two users get the same
+ *     bytes): ss_plan_windows' windows over the ss_add_pcm signal, window i covers the bins
  *     round(51.2 i) .. + 255 (NNDetector.py:168-186), bin j is centred at (j + 0.5) 3 / 256 - 3 s (the reference's 3 / 256 s bin;
  *     the true hop is 256 / 22050 s).  The spec head runs on every window that covers a needed bin (step 3) and on no other.
  *     Each needed bin averages both channels over the windows that cover it: a float64 sum in ascending window order divided by

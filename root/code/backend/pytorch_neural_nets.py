@@ -93,10 +93,20 @@ class SpecUNet_2D(nn.Module):
         """settings.hip_precision, or 'fp32' once the f16x2 mode has refused these weights (with_range_fallback)."""
         return "fp32" if (self.precision == "f16x2" and self._fp32_for == self._weights_version()) else self.precision
 
+    @staticmethod
+    def _with_step(ctx):
+        """settings.step_size (the reference reads it at NNDetector.py:69,175) on a context about to be used: set when it differs, so
+        that a value edited between two jobs reaches the contexts that are reused.  A value the library does not take raises ValueError
+        naming the limits (native.check_step)."""
+        step = _native.check_step(settings.step_size)
+        if ctx.window_step != step:
+            ctx.set_window_step(step)
+        return ctx
+
     def hip_context(self, which: int = 0) -> _native.Context:
-        """The device context of these weights.  which = 1: a second context of the same weights and precision, created when first asked
-        for -- ProcessWorker.run alternates its files between the two, so that the next file's launches are queued (on the other
-        context's stream) before the current file's last launch ends."""
+        """The device context of these weights, its window step settings.step_size.  which = 1: a second context of the same weights and
+        precision, created when first asked for -- ProcessWorker.run alternates its files between the two, so that the next file's
+        launches are queued (on the other context's stream) before the current file's last launch ends."""
         ver = self._weights_version()
         prec = self.effective_precision()
         if self._ctx is None or ver != self._ctx_version or self._ctx.precision != prec:
@@ -124,11 +134,11 @@ class SpecUNet_2D(nn.Module):
                 self._ctx.close()                       # f16x2 loses precision on THESE weights without overflowing: fp32 from here on
                 self._ctx = _native.Context(blob, self.device_index, precision="fp32", chunk=chunk)
         if which == 0:
-            return self._ctx
+            return self._with_step(self._ctx)
         if self._ctx2 is None:
             self._ctx2 = _native.Context(_ckpt.pack_state_dict(self.state_dict()), self.device_index, precision=self._ctx.precision,
                                          chunk=settings.hip_chunk_windows or None)
-        return self._ctx2
+        return self._with_step(self._ctx2)
 
     def _note_fallback(self, ver, err):
         if self._fp32_for != ver:
@@ -189,7 +199,7 @@ class SpecUNet_2D(nn.Module):
         if self._fp32_tmp is None or not self._fp32_tmp.alive:
             self._fp32_tmp = _native.Context(_ckpt.pack_state_dict(self.state_dict()), self.device_index, precision="fp32",
                                              chunk=settings.hip_chunk_windows or None)
-        return self._fp32_tmp
+        return self._with_step(self._fp32_tmp)
 
     def range_refused(self, key, err) -> bool:
         """Book a run-time SS_ERR_RANGE of the f16x2 mode for the input `key` -> True when the detector now runs everything in fp32.

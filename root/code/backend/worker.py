@@ -13,6 +13,9 @@ batches and a file interrupted half-way leaves no rows (worker.py:72,86-87).
 Differences: the file is decoded, mixed down, resampled, padded and kept in HBM by the library
 (one upload per file, not per batch), averaging runs on the GPU, and a file that cannot be decoded
 is reported through signals.message and skipped (the reference crashes on len(None), worker.py:60).
+settings.step_size is applied to whichever device context a file runs on (SpecUNet_2D.hip_context / fp32_context read it on every
+use), so the windows run and the totals of fileProgressChanged are the device's plan at that step; a value the library does not take
+(outside 0.1 .. 3.0 s) raises from plan_detection_job, and a job started without it reports the same ValueError per file.
 """
 from __future__ import annotations
 

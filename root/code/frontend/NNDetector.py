@@ -80,6 +80,9 @@ class NNDetector():
 
     # -- planning -------------------------------------------------------------------------------------------
     def plan_detection_job(self):
+        # settings.step_size outside what the library takes: ValueError naming the limits, before anything is planned -- the device
+        # would refuse the same value, and a plan it does not follow is worse than none
+        _native.check_step(settings.step_size)
         plan = self.detections_project
         for file in plan.keys():
             logging.info(f"Analyzing file: {file}")

@@ -104,6 +104,17 @@ extern "C" int ss_set_chunk_windows(ss_ctx* c, int chunk) {
     return SS_OK;
 }
 
+// settings.step_size of the reference (settings.py:16): the plan of the next run and of the streams opened from now on
+extern "C" int ss_set_window_step(ss_ctx* c, double step_s) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    if (!step_ok(step_s)) return fail(c, SS_ERR_ARG, "ss_set_window_step: the step must be a finite number of seconds in [0.1, 3.0]");
+    c->step = step_s;
+    return SS_OK;
+}
+
+extern "C" double ss_get_window_step(ss_ctx* c) { return c ? c->step : -1.0; }
+
 // ------------------------------------------------------------------------------------------------------
 // arena
 // ------------------------------------------------------------------------------------------------------

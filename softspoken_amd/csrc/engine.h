@@ -126,6 +126,7 @@ struct ss_ctx {
     hipStream_t copy_stream = nullptr; hipEvent_t ev_copy = nullptr; bool copy_pending = false;
     std::string err;
     int chunk = 1024;                                      // most windows per pass of the network
+    double step = SS_STEP_DEFAULT;                         // window step, seconds (ss_set_window_step): the next run's plan, the streams opened from now on
     int num_cus = 256;
 
     // tables + weights on device
@@ -281,6 +282,9 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
 void free_separation(ss_ctx* c);
 // host.hip
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
+bool step_ok(double step_s);                              // a window step ss_set_window_step accepts
+int64_t step_samples(double step_s);                      // floor(22050 step): samples between window starts
+inline double step_bins(double step_s) { return step_s * 256.0 / 3.0; }   // s_b: bins between window starts, before the rounding of a start
 std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);
 double now_ms();
 

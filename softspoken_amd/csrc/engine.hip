@@ -510,7 +510,8 @@ static int launch_post(ss_ctx* c, size_t n_files, int64_t total, int64_t total_b
     const size_t words = (size_t)((total_bins + 255) / 256) * 4 + 1;
     {
         ScopedLaunch sl(c, c->stream, "average", 0.0, (double)total * 1024 * 5 + (double)total_bins * 12);
-        HIPCHK(c, launch_average(c->d_logits, c->d_avgfiles, (int)n_files, c->d_starts, c->d_avg, c->d_count, max_bins, c->stream));
+        // (c->step is the run's: ss_set_window_step is refused while it is in flight)
+        HIPCHK(c, launch_average(c->d_logits, c->d_avgfiles, (int)n_files, c->d_starts, step_bins(c->step), c->d_avg, c->d_count, max_bins, c->stream));
     }
     if (total_bins) {
         ScopedLaunch sl(c, c->stream, "bin_masks", 0.0, (double)total_bins * 12 + (double)words * 16);
@@ -566,7 +567,9 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
     hipSetDevice(c->device);
     int rc;
     c->t_in = now_ms();
-    // ---- plan (NNDetector.py:55-82) ----
+    // ---- plan (NNDetector.py:55-82) with the context's window step (settings.step_size) ----
+    const double step = c->step;
+    const int64_t per_step = step_samples(step);
     int64_t total = 0, total_bins = 0; int max_bins = 0;
     std::vector<int64_t> off;
     std::vector<int32_t> starts;
@@ -574,16 +577,16 @@ int run_begin(ss_ctx* c, double threshold, double break_s, bool track, const vol
     af.assign(c->files.size(), AvgFile{});
     for (size_t fi = 0; fi < c->files.size(); ++fi) {
         FileRec& f = c->files[fi];
-        f.W = ss_plan_windows(f.duration, nullptr, 0);
+        f.W = ss_plan_windows_step(f.duration, step, nullptr, 0);
         // the plan comes from the header duration, the data from the resampler: clamp to what fits
-        while (f.W > 0 && (f.W - 1) * (int64_t)SS_STEP_SAMPLES + SS_WINDOW_SAMPLES > f.n_padded) --f.W;
+        while (f.W > 0 && (f.W - 1) * per_step + SS_WINDOW_SAMPLES > f.n_padded) --f.W;
         f.win_base = total;
         const double secs = (double)f.n_padded / 22050.0;
         const int n_bins = (int)std::nearbyint(secs * 256.0 / 3.0);          // NNDetector.py:168
         af[fi].logit_off = total; af[fi].bin_off = total_bins; af[fi].W = (int32_t)f.W; af[fi].n_bins = n_bins; af[fi].start_off = total;
         for (int64_t i = 0; i < f.W; ++i) {
-            off.push_back(f.off + i * SS_STEP_SAMPLES);
-            starts.push_back((int32_t)std::nearbyint((double)i * 0.6 / (3.0 / 256.0)));   // NNDetector.py:175
+            off.push_back(f.off + i * per_step);
+            starts.push_back((int32_t)ss_window_start_bin(i, step));                       // NNDetector.py:175
         }
         total += f.W; total_bins += n_bins; max_bins = std::max(max_bins, n_bins);
     }

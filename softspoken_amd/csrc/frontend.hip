@@ -1213,16 +1213,18 @@ hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, in
 }
 
 // =========================================================================================================
-// Overlap averaging (NNDetector.py:168-186): window i adds its 256 logits at bin start[i] = round(51.2 i);
-// float64 sum in window order, divided by the count; bins never covered keep count 0 and are dropped later.
+// Overlap averaging (NNDetector.py:168-186): window i adds its 256 logits at bin start[i] = round(i step / (3 / 256)) (round(51.2 i) at
+// the default step); float64 sum in window order, divided by the count; bins never covered keep count 0 and are dropped later.
 // =========================================================================================================
 // One bin's average: the windows i < W whose 256 bins [start(i), start(i) + 256) hold bin j, their logit(i, j - start(i)) summed in
 // float64 in window order, divided by their count c (0.0 and c = 0 when none does).  Shared by the whole-file and the streaming kernel.
+// s_b: bins between window starts (window step x 256 / 3); start(i) lies within half a bin of i s_b, so the candidates [lo, hi] below
+// hold every covering window for any step of the accepted range (the test on d picks them: the bounds only limit the search).
 template <class StartOf, class LogitOf>
-__device__ __forceinline__ double average_bin(int j, int W, StartOf start, LogitOf logit, int& c) {
-    int lo = (int)((double)(j - 255) / 51.2) - 1;
+__device__ __forceinline__ double average_bin(int j, int W, double s_b, StartOf start, LogitOf logit, int& c) {
+    int lo = (int)((double)(j - 255) / s_b) - 1;
     if (lo < 0) lo = 0;
-    int hi = (int)((double)j / 51.2) + 1;
+    int hi = (int)((double)j / s_b) + 1;
     if (hi > W - 1) hi = W - 1;
     double s = 0.0;
     c = 0;
@@ -1234,14 +1236,14 @@ __device__ __forceinline__ double average_bin(int j, int W, StartOf start, Logit
 }
 
 __global__ __launch_bounds__(256) void average_kernel(const float* __restrict__ logits, const AvgFile* __restrict__ files,
-                                                      const int32_t* __restrict__ starts, double* __restrict__ avg,
+                                                      const int32_t* __restrict__ starts, double s_b, double* __restrict__ avg,
                                                       int32_t* __restrict__ count) {
     const AvgFile fi = files[blockIdx.y];
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= fi.n_bins) return;
     const int32_t* st = starts + fi.start_off;
     int c = 0;
-    avg[fi.bin_off + j] = average_bin(j, fi.W, [&](int i) { return st[i]; },
+    avg[fi.bin_off + j] = average_bin(j, fi.W, s_b, [&](int i) { return st[i]; },
                                       [&](int i, int d) { return logits[(fi.logit_off + i) * 256 + d]; }, c);
     count[fi.bin_off + j] = c;
 }
@@ -1295,11 +1297,11 @@ hipError_t launch_region_peaks(const double* avg, const int32_t* count, const in
     return hipGetLastError();
 }
 
-hipError_t launch_average(const float* logits, const AvgFile* files, int n_files, const int32_t* starts, double* avg, int32_t* count,
-                          int max_bins, hipStream_t s) {
+hipError_t launch_average(const float* logits, const AvgFile* files, int n_files, const int32_t* starts, double s_b, double* avg,
+                          int32_t* count, int max_bins, hipStream_t s) {
     if (n_files <= 0 || max_bins <= 0) return hipSuccess;
     hipLaunchKernelGGL(average_kernel, dim3((unsigned)((max_bins + 255) / 256), (unsigned)n_files), dim3(256), 0, s, logits, files,
-                       starts, avg, count);
+                       starts, s_b, avg, count);
     return hipGetLastError();
 }
 
@@ -1356,8 +1358,9 @@ __global__ __launch_bounds__(256) void stream_resample_kernel(const StreamResamp
 }
 
 // the bins [b0, b0 + nb) of a stream that became final: average_bin over the stream's windows [w0, W) whose logits lie back to back
-// from `logits` (window w0 first), start(i) = round(51.2 i) (= (512 i + 5) div 10: 256 i / 5 is never a tie), then the two bits
-// bin_masks_kernel makes of a bin with the stream's threshold (1: covered by a window, 2: average above the threshold)
+// from `logits` (window w0 first), start(i) = rint((i step) / (3 / 256)) in correctly rounded double operations, ties to even -- the
+// host's ss_window_start_bin, which fills the whole-file run's start table --, then the two bits bin_masks_kernel makes of a bin with
+// the stream's threshold (1: covered by a window, 2: average above the threshold)
 __global__ __launch_bounds__(256) void stream_average_kernel(const StreamAvg* __restrict__ as, int n, double* __restrict__ avg,
                                                              unsigned char* __restrict__ flags) {
     for (int k = blockIdx.y; k < n; k += gridDim.y) {
@@ -1365,7 +1368,7 @@ __global__ __launch_bounds__(256) void stream_average_kernel(const StreamAvg* __
         for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < a.nb; t += (int64_t)gridDim.x * 256) {
             const int j = (int)(a.b0 + t);
             int c = 0;
-            const double v = average_bin(j, a.W, [](int i) { return (int)(((int64_t)512 * i + 5) / 10); },
+            const double v = average_bin(j, a.W, a.s_b, [&](int i) { return (int)rint(__ddiv_rn(__dmul_rn((double)i, a.step), 3.0 / 256.0)); },
                                          [&](int i, int d) { return i >= a.w0 ? a.logits[(int64_t)(i - a.w0) * 256 + d] : __builtin_nanf(""); }, c);
             const bool cov = c >= 1, abv = cov && v > a.threshold;
             avg[a.out_off + t] = v;

@@ -108,13 +108,29 @@ extern "C" int64_t ss_resampled_length(int64_t frames, int sample_rate) {
     return (frames * SS_SAMPLE_RATE + sample_rate - 1) / sample_rate;
 }
 
+// settings.step_size (settings.py:16) as the library takes it: SS_STEP_MIN <= step <= SS_STEP_MAX, finite
+bool ss::step_ok(double step_s) { return std::isfinite(step_s) && step_s >= SS_STEP_MIN && step_s <= SS_STEP_MAX; }
+int64_t ss::step_samples(double step_s) { return (int64_t)std::floor(22050.0 * step_s); }   // NNDetector.py:75
+
 // NNDetector.py:66-80
-extern "C" int64_t ss_plan_windows(double duration_s, int64_t* starts, int64_t cap) {
+extern "C" int64_t ss_plan_windows_step(double duration_s, double step_s, int64_t* starts, int64_t cap) {
+    if (!step_ok(step_s)) return -1;
+    const int64_t per_step = step_samples(step_s);
     const double L = std::nearbyint(duration_s * 22050.0) + 6.0 * 22050.0;
-    int64_t W = (int64_t)std::ceil((L - 66150.0) / 13230.0);
+    int64_t W = (int64_t)std::ceil((L - 66150.0) / (double)per_step);
     if (W < 0) W = 0;
-    if (starts) for (int64_t i = 0; i < W && i < cap; ++i) starts[i] = i * SS_STEP_SAMPLES;
+    if (starts) for (int64_t i = 0; i < W && i < cap; ++i) starts[i] = i * per_step;
     return W;
+}
+
+extern "C" int64_t ss_plan_windows(double duration_s, int64_t* starts, int64_t cap) {
+    return ss_plan_windows_step(duration_s, SS_STEP_DEFAULT, starts, cap);
+}
+
+// NNDetector.py:175: int(round(i * step_size / time_resolution)), Python's round (ties to even), the reference's operation order
+extern "C" int64_t ss_window_start_bin(int64_t i, double step_s) {
+    if (!step_ok(step_s) || i < 0) return -1;
+    return (int64_t)std::nearbyint(((double)i * step_s) / (3.0 / 256.0));
 }
 
 double ss::bin_time(int64_t idx) {    // float(f"{idx / (256 / 3):.4f}")  (NNDetector.py:185, worker.py:100)

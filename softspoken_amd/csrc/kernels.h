@@ -242,8 +242,9 @@ hipError_t launch_resample_fused_channels(const void* pcm, int format, int chann
                                           int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s);
 
 // ---- overlap averaging (NNDetector.py:153-190), double accumulation ---------------------------------
+// s_b: bins between window starts (window step x 256 / 3), from which a bin's candidate windows are bounded; starts: the windows' first bins
 struct AvgFile { int64_t logit_off; int64_t bin_off; int32_t W; int32_t n_bins; int64_t start_off; };
-hipError_t launch_average(const float* logits, const AvgFile* files, int n_files, const int32_t* starts, double* avg,
+hipError_t launch_average(const float* logits, const AvgFile* files, int n_files, const int32_t* starts, double s_b, double* avg,
                           int32_t* count, int max_bins, hipStream_t s);
 // covered / above-threshold bit per bin, 64 bins per word (words = ceil(total_bins / 64), both arrays)
 hipError_t launch_bin_masks(const double* avg, const int32_t* count, int64_t total_bins, double threshold, unsigned long long* above,
@@ -258,8 +259,9 @@ struct StreamCopy { const float* src; float* dst; int64_t n; };                 
 struct StreamDecode { int64_t pcm_off; int64_t frames; float* dst; int32_t format, channels; };
 // outputs [m0, m0 + n) -> out[0 .. n); input sample idx is mono[idx - mono_base] for mono_base <= idx < frames, zero past `frames`
 struct StreamResample { const float* mono; int64_t mono_base, frames; const float* taps; float* out; int64_t m0, n; int32_t L, M, half, pad; };
-// bins [b0, b0 + nb) from the windows [w0, W) whose logits lie back to back at `logits`; results at avg / flags [out_off ..)
-struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, nb, out_off; double threshold; };
+// bins [b0, b0 + nb) from the windows [w0, W) whose logits lie back to back at `logits`; results at avg / flags [out_off ..); step: the
+// stream's window step in seconds (window i starts at bin rint(i step / (3 / 256)), as ss_window_start_bin), s_b = step x 256 / 3
+struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, nb, out_off; double threshold, step, s_b; };
 hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s);
 hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s);
 hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s);

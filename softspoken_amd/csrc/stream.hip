@@ -17,13 +17,12 @@ namespace ss {
 namespace {
 
 constexpr int64_t kPad = SS_WINDOW_SAMPLES;          // 3 s of zeros in front of and behind the recording (worker.py:58-62)
-constexpr int64_t kStep = SS_STEP_SAMPLES;
-
-int64_t win_start_bin(int64_t i) { return (512 * i + 5) / 10; }     // round(51.2 i), NNDetector.py:175 (256 i / 5 is never a tie)
 
 struct StreamRec {
     int format = 0, sr = 0, ch = 0;
     double thr = 0;                                   // (break_s: mg.brk)
+    // the window step the stream was opened with (the context's then, or its image's): seconds, and floor(22050 step) samples
+    double step = SS_STEP_DEFAULT; int64_t per_step = SS_STEP_SAMPLES;
     int L = 1, M = 1, half = 0;                       // 22 050 Hz: decoded straight into the signal (no resampler)
     float* d_taps = nullptr;
     int64_t frames_in = 0;                            // frames decoded so far
@@ -61,11 +60,14 @@ struct StreamPlan {
 
 int64_t n22_of(const StreamRec& s, int64_t F) { return ss_resampled_length(F, s.sr); }
 
+// first bin of the stream's window i (NNDetector.py:175): the whole-file run's start table
+int64_t win_start_bin(const StreamRec& s, int64_t i) { return ss_window_start_bin(i, s.step); }
+
 // run_begin's plan of a file of F frames: window count (clamped to the padded signal) and bin count
 void file_plan(const StreamRec& s, int64_t F, int64_t& W, int64_t& n_bins) {
     const int64_t n_padded = n22_of(s, F) + 2 * kPad;
-    W = ss_plan_windows((double)F / (double)s.sr, nullptr, 0);
-    while (W > 0 && (W - 1) * kStep + SS_WINDOW_SAMPLES > n_padded) --W;
+    W = ss_plan_windows_step((double)F / (double)s.sr, s.step, nullptr, 0);
+    while (W > 0 && (W - 1) * s.per_step + SS_WINDOW_SAMPLES > n_padded) --W;
     n_bins = (int64_t)std::nearbyint((double)n_padded / 22050.0 * 256.0 / 3.0);
 }
 
@@ -89,7 +91,7 @@ StreamPlan plan_stream(const StreamRec& s) {
         p.kb = std::min(std::max(k0, s.mono_base), s.frames_in);
         p.mono_keep = s.frames_in - p.kb;
     }
-    p.base_new = s.win_run * kStep;
+    p.base_new = s.win_run * s.per_step;
     const int64_t sig_end = s.sig_base + s.sig_n;
     p.sig_keep = sig_end - p.base_new;
     p.pre = sig_end < kPad ? kPad - sig_end : 0;      // a new stream: the 3 s in front
@@ -100,9 +102,10 @@ StreamPlan plan_stream(const StreamRec& s) {
         p.i_end = W_plan;
         p.b_end = nb_plan;
     } else {
-        // window i reads the unpadded samples [i 13230 - 66150, i 13230); the plan of F frames is a lower bound of the final one
-        p.i_end = std::min(p.m_end / kStep + 1, W_plan);
-        p.b_end = std::min(win_start_bin(p.i_end), nb_plan);       // every window that starts at or before such a bin has run
+        // window i reads the unpadded samples [i per_step - 66150, i per_step) (13230 i at the default step); the plan of F frames is a
+        // lower bound of the final one
+        p.i_end = std::min(p.m_end / s.per_step + 1, W_plan);
+        p.b_end = std::min(win_start_bin(s, p.i_end), nb_plan);    // every window that starts at or before such a bin has run
     }
     p.i_end = std::max(p.i_end, s.win_run);
     p.b_end = std::max(p.b_end, s.bins_done);
@@ -111,10 +114,11 @@ StreamPlan plan_stream(const StreamRec& s) {
     return p;
 }
 
-// windows whose logits the bins from b on still need: start(i) + 256 > b
-int64_t first_window_for_bin(int64_t b) {
-    int64_t i = std::max<int64_t>(0, (b - 256) * 10 / 512 - 1);
-    while (win_start_bin(i) + 256 <= b) ++i;
+// windows whose logits the bins from b on still need: start(i) + 256 > b (start(i) lies within half a bin of i s_b: the first guess
+// is at or below the answer)
+int64_t first_window_for_bin(const StreamRec& s, int64_t b) {
+    int64_t i = std::max<int64_t>(0, (int64_t)std::floor((double)(b - 256) / step_bins(s.step)) - 1);
+    while (win_start_bin(s, i) + 256 <= b) ++i;
     return i;
 }
 
@@ -176,6 +180,7 @@ extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double thre
     hipSetDevice(c->device);
     StreamRec s;
     s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.mg.brk = break_s;
+    s.step = c->step; s.per_step = step_samples(c->step);
     if ((rc = init_rates(c, s))) return rc;
     StreamSet& S = streams_of(c);
     *id = S.next_id++;
@@ -291,6 +296,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
     float* cur_arena = S.arena[S.cur];
     auto al = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
     int64_t arena_need = 0, up_bytes = 0, total_w = 0, total_b = 0;
+    double avg_reads = 0;                                   // logits the averaging reads: 256 / s_b windows per bin
     for (auto& [sp, p] : act) {
         const StreamRec& s = *sp;
         if (s.sr != SS_SAMPLE_RATE) { p.mono_off = arena_need; arena_need = al(arena_need + p.mono_len(), 64); }
@@ -363,13 +369,14 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         }
         // windows [win_run, i_end): arena offsets, their logits behind the carried ones
         const int64_t nw = p.i_end - s.win_run;
-        for (int64_t i = s.win_run; i < p.i_end; ++i) winoff.push_back(p.sig_off + (i * kStep - p.base_new));
+        for (int64_t i = s.win_run; i < p.i_end; ++i) winoff.push_back(p.sig_off + (i * s.per_step - p.base_new));
         if (nw > 0) post.push_back(StreamCopy{S.d_newlg + (size_t)w_at * 256, A + p.lg_off + (s.win_run - p.lw0) * 256, nw * 256});
         w_at += nw;
         const int64_t nb = p.b_end - s.bins_done;
         if (nb > 0) {
-            avg.push_back(StreamAvg{A + p.lg_off, p.lw0, p.W_avg, 0, s.bins_done, nb, b_at, s.thr});
+            avg.push_back(StreamAvg{A + p.lg_off, p.lw0, p.W_avg, 0, s.bins_done, nb, b_at, s.thr, s.step, step_bins(s.step)});
             max_bins = std::max(max_bins, nb);
+            avg_reads += (double)nb * 256.0 / step_bins(s.step);
         }
         b_at += nb;
     }
@@ -415,7 +422,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         HIPCHK(c, launch_stream_copy((const StreamCopy*)(S.d_up + o_post), (int)post.size(), mx, c->stream));
     }
     {
-        ScopedLaunch sl(c, c->stream, "stream_average", 0.0, (double)total_b * 1024 * 5 / 51.2 + (double)total_b * 9);
+        ScopedLaunch sl(c, c->stream, "stream_average", 0.0, avg_reads * 4 + (double)total_b * 9);
         HIPCHK(c, launch_stream_average((const StreamAvg*)(S.d_up + o_avg), (int)avg.size(), max_bins, S.d_avg, S.d_flags, c->stream));
     }
     S.h_avg.resize((size_t)total_b); S.h_flags.resize((size_t)total_b);
@@ -458,8 +465,8 @@ extern "C" int ss_stream_step(ss_ctx* c) {
             const int64_t k0 = std::min(std::max(p.kb, (p.m_end * s.M) / s.L - s.half + 1), p.F);
             s.mono_base = k0; s.mono_n = p.F - k0; s.mono_off = p.mono_off + (k0 - p.kb);
         }
-        s.sig_base = p.i_end * kStep; s.sig_n = sig_end - s.sig_base; s.sig_off = p.sig_off + (s.sig_base - p.base_new);
-        const int64_t w0 = std::min(std::max(first_window_for_bin(p.b_end), p.lw0), p.i_end);
+        s.sig_base = p.i_end * s.per_step; s.sig_n = sig_end - s.sig_base; s.sig_off = p.sig_off + (s.sig_base - p.base_new);
+        const int64_t w0 = std::min(std::max(first_window_for_bin(s, p.b_end), p.lw0), p.i_end);
         s.lg_w0 = w0; s.lg_n = p.i_end - w0; s.lg_off = p.lg_off + (w0 - p.lw0) * 256;
     }
     S.cur = nxt;
@@ -476,18 +483,22 @@ struct ImageHdr {
     double thr, brk, cur_start, cur_end;
     int64_t frames_in, staged_frames, staged_bytes, mono_base, mono_n, sig_base, sig_n, lg_w0, lg_n, m_next, win_run, bins_done, run_first, run_last;
 };
+// "SSSTRM01": a stream with the default window step -- the header, then the data.  "SSSTRM02": any other step -- the header, the step
+// (a double), then the data.
 constexpr char kMagic[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '1'};
+constexpr char kMagicStep[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '2'};
 }  // namespace
 
 extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64_t* n_out) {
     StreamRec* s = find_stream(c, id);
     if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_export: bad argument");
-    const int64_t need = (int64_t)sizeof(ImageHdr) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
+    const bool with_step = s->step != SS_STEP_DEFAULT;
+    const int64_t need = (int64_t)sizeof(ImageHdr) + (with_step ? 8 : 0) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
     *n_out = need;
     if (!buf) return SS_OK;
     if (cap < need) return fail(c, SS_ERR_CAPACITY, "ss_stream_export: capacity < " + std::to_string(need));
     ImageHdr h{};
-    memcpy(h.magic, kMagic, 8);
+    memcpy(h.magic, with_step ? kMagicStep : kMagic, 8);
     h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->mg.have; h.run_open = s->run_open;
     h.thr = s->thr; h.brk = s->mg.brk; h.cur_start = s->mg.cur.start; h.cur_end = s->mg.cur.end;
     h.frames_in = s->frames_in; h.staged_frames = s->staged_frames; h.staged_bytes = (int64_t)s->staged.size();
@@ -495,6 +506,7 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     h.m_next = s->m_next; h.win_run = s->win_run; h.bins_done = s->bins_done; h.run_first = s->run_first; h.run_last = s->run_last;
     unsigned char* o = (unsigned char*)buf;
     memcpy(o, &h, sizeof h); o += sizeof h;
+    if (with_step) { memcpy(o, &s->step, 8); o += 8; }
     if (!s->staged.empty()) memcpy(o, s->staged.data(), s->staged.size());
     o += s->staged.size();
     float* f = (float*)o;                                 // (unaligned host memory is fine for memcpy / hipMemcpy)
@@ -518,21 +530,26 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
     ImageHdr h;
     memcpy(&h, buf, sizeof h);
     static const unsigned char one[8] = {0};
-    if (memcmp(h.magic, kMagic, 8) != 0 || check_pcm_args(c, one, h.format, h.sr, h.ch, 0) != SS_OK || h.staged_bytes < 0 || h.mono_n < 0 ||
+    const bool with_step = memcmp(h.magic, kMagicStep, 8) == 0;
+    int64_t hdr_bytes = (int64_t)sizeof h;
+    double step = SS_STEP_DEFAULT;
+    if (with_step && n >= hdr_bytes + 8) { memcpy(&step, (const unsigned char*)buf + hdr_bytes, 8); hdr_bytes += 8; }
+    if ((memcmp(h.magic, kMagic, 8) != 0 && !(with_step && hdr_bytes > (int64_t)sizeof h && step_ok(step))) || check_pcm_args(c, one, h.format, h.sr, h.ch, 0) != SS_OK || h.staged_bytes < 0 || h.mono_n < 0 ||
         h.sig_n < 0 || h.lg_n < 0 || h.lg_n > 64 || h.mono_n > ((int64_t)1 << 32) || h.sig_n > ((int64_t)1 << 32) ||
-        n != (int64_t)sizeof h + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) ||
+        n != hdr_bytes + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) ||
         h.staged_bytes != h.staged_frames * h.ch * (int64_t)pcm_bytes_per_sample(h.format))
         return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
     hipSetDevice(c->device);
     StreamRec s;
     s.format = h.format; s.sr = h.sr; s.ch = h.ch; s.closed = h.closed; s.finished = h.finished; s.mg.have = h.have; s.run_open = h.run_open;
     s.thr = h.thr; s.mg.brk = h.brk; s.mg.cur = ss_region{h.cur_start, h.cur_end};
+    s.step = step; s.per_step = step_samples(step);
     s.frames_in = h.frames_in; s.staged_frames = h.staged_frames;
     s.mono_base = h.mono_base; s.mono_n = h.mono_n; s.sig_base = h.sig_base; s.sig_n = h.sig_n; s.lg_w0 = h.lg_w0; s.lg_n = h.lg_n;
     s.m_next = h.m_next; s.win_run = h.win_run; s.bins_done = h.bins_done; s.run_first = h.run_first; s.run_last = h.run_last;
     int rc = init_rates(c, s);
     if (rc) return rc;
-    const unsigned char* p = (const unsigned char*)buf + sizeof h;
+    const unsigned char* p = (const unsigned char*)buf + hdr_bytes;
     s.staged.assign(p, p + h.staged_bytes); p += h.staged_bytes;
     s.h_mono.resize(h.mono_n); s.h_sig.resize(h.sig_n); s.h_lg.resize(h.lg_n * 256);
     memcpy(s.h_mono.data(), p, h.mono_n * 4); p += h.mono_n * 4;

@@ -37,7 +37,9 @@ _BPS = {PCM_U8: 1, PCM_S16: 2, PCM_S24: 3, PCM_S32: 4, PCM_F32: 4, PCM_F64: 8,
         PCM_S8: 1, PCM_S16BE: 2, PCM_S24BE: 3, PCM_S32BE: 4, PCM_F32BE: 4, PCM_F64BE: 8}     # bytes per sample of enum ss_pcm_format
 SAMPLE_RATE = 22050
 WINDOW_SAMPLES = 66150
-STEP_SAMPLES = 13230
+STEP_SAMPLES = 13230              # floor(22050 * 0.6): the default window step (Context.window_step; STEP_MIN <= step <= STEP_MAX)
+DEFAULT_STEP = 0.6
+STEP_MIN, STEP_MAX = 0.1, 3.0
 
 
 class WavInfo(C.Structure):
@@ -86,12 +88,16 @@ _SIGS = {
     "ss_wav_parse": (C.c_int, [_P, C.c_size_t, C.POINTER(WavInfo)]),
     "ss_resampled_length": (C.c_int64, [C.c_int64, C.c_int]),
     "ss_plan_windows": (C.c_int64, [C.c_double, _P, C.c_int64]),
+    "ss_plan_windows_step": (C.c_int64, [C.c_double, C.c_double, _P, C.c_int64]),
+    "ss_window_start_bin": (C.c_int64, [C.c_int64, C.c_double]),
     "ss_find_regions": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_find_regions_union": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_format_csv_rows": (C.c_int64, [C.c_char_p, C.c_char_p, _P, C.c_int64, C.c_int64, _P, C.c_int64]),
     "ss_create": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_uint32, C.POINTER(_P)]),
     "ss_destroy": (None, [_P]),
     "ss_set_chunk_windows": (C.c_int, [_P, C.c_int]),
+    "ss_set_window_step": (C.c_int, [_P, C.c_double]),
+    "ss_get_window_step": (C.c_double, [_P]),
     "ss_reset": (C.c_int, [_P]),
     "ss_reset_generation": (C.c_uint64, [_P]),
     "ss_add_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int)]),
@@ -206,12 +212,30 @@ def wav_parse(buf) -> WavInfo:
     return info
 
 
-def plan_windows(duration_s: float) -> np.ndarray:
-    n = lib().ss_plan_windows(float(duration_s), None, 0)
+def check_step(step) -> float:
+    """step as a float, or ValueError naming the limits (the library answers SS_ERR_ARG / -1 for the same values)."""
+    try:
+        s = float(step)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not (STEP_MIN <= s <= STEP_MAX):                   # (a NaN compares false)
+        raise ValueError(f"window step must be a finite number of seconds in [{STEP_MIN}, {STEP_MAX}], not {step!r}")
+    return s
+
+
+def plan_windows(duration_s: float, step: float = DEFAULT_STEP) -> np.ndarray:
+    """Window starts in the 3 s-padded signal: i * floor(22050 * step) (ss_plan_windows_step)."""
+    step = check_step(step)
+    n = lib().ss_plan_windows_step(float(duration_s), step, None, 0)
     out = np.zeros(max(n, 0), dtype=np.int64)
     if n > 0:
-        lib().ss_plan_windows(float(duration_s), _ptr(out), n)
+        lib().ss_plan_windows_step(float(duration_s), step, _ptr(out), n)
     return out
+
+
+def window_start_bin(i: int, step: float = DEFAULT_STEP) -> int:
+    """First averaged bin of window i: int(round(i * step / (3 / 256))), ties to even (ss_window_start_bin)."""
+    return int(lib().ss_window_start_bin(int(i), check_step(step)))
 
 
 def find_regions(avg, bin_idx, threshold=0.1, break_s=0.5):
@@ -328,6 +352,15 @@ class Context:
 
     def set_chunk(self, n):
         self._ck(lib().ss_set_chunk_windows(self._h, int(n)))
+
+    def set_window_step(self, step: float):
+        """settings.step_size of the reference: seconds between window starts, STEP_MIN <= step <= STEP_MAX (ValueError otherwise).
+        Holds for the next run / run_begin / run_from_logits and for streams opened afterwards; not while a run is in flight."""
+        self._ck(lib().ss_set_window_step(self._h, check_step(step)))
+
+    @property
+    def window_step(self) -> float:
+        return float(lib().ss_get_window_step(self._h))
 
     def reset(self):
         self._ck(lib().ss_reset(self._h))

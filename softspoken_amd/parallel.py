@@ -168,7 +168,7 @@ def detect_recording_sharded(ctx, pcm, fmt: int, sample_rate: int, channels: int
     from . import native
     ctx.reset()
     fid = ctx.add_pcm(pcm, fmt, sample_rate, channels, frames)
-    starts = native.plan_windows(frames / sample_rate)
+    starts = native.plan_windows(frames / sample_rate, ctx.window_step)       # (run_from_logits plans with the same step)
     # the plan comes from the header duration, the data from the resampler: clamp to what fits, as ss_run does
     n_padded = ctx.signal_length(fid, padded=True)
     while len(starts) and starts[-1] + native.WINDOW_SAMPLES > n_padded:

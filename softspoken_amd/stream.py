@@ -47,10 +47,20 @@ class Stream:
 
 
 class StreamDetector:
-    def __init__(self, blob=None, device: int = 0, precision: str = "f16x2", chunk: int | None = None, context_factory=None):
+    def __init__(self, blob=None, device: int = 0, precision: str = "f16x2", chunk: int | None = None, context_factory=None,
+                 step: float | None = None):
         """context_factory(precision) -> a native.Context (or a stand-in with its stream_* methods); default: one of `blob`'s weights
-        on `device`."""
-        self._factory = context_factory or (lambda p: _native.Context(blob, device, precision=p, chunk=chunk))
+        on `device`.  step: seconds between window starts of the streams opened here (the reference's settings.step_size; None: the
+        contexts' own, 0.6 s unless the factory set another) -- a stream keeps the step it was opened with, also across a move to fp32."""
+        make = context_factory or (lambda p: _native.Context(blob, device, precision=p, chunk=chunk))
+        self.window_step = None if step is None else _native.check_step(step)
+
+        def factory(p):
+            ctx = make(p)
+            if self.window_step is not None:
+                ctx.set_window_step(self.window_step)
+            return ctx
+        self._factory = factory
         self._main = self._factory(precision)
         self._fp32 = self._main if precision == "fp32" else None
         self._streams: list[Stream] = []
