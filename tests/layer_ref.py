@@ -314,10 +314,21 @@ def flatten_weights(sd):
     return w, b
 
 
-def flatten_scale(e_c9) -> int:
-    """The common exponent of conv9_1's channels that the flatten partial sums carry (weights.hip: the median, s_common)."""
-    e = torch.as_tensor(e_c9, dtype=torch.int64)
-    return int(torch.sort(e).values[len(e) // 2])
+def flatten_log2_rms(sd, e_c9) -> float:
+    """log2 of the rms of conv_flatten's weights with their columns on conv9_1's normalised channels (wf 2^-e[ci])."""
+    wf, _ = flatten_weights(sd)
+    return float(torch.log2(torch.sqrt((scale_w(wf, None, torch.as_tensor(e_c9, dtype=torch.int64)) ** 2).mean())))
+
+
+def flatten_scale(sd, e_c9, mode: str) -> int:
+    """The common exponent that the flatten partial sums carry (weights.hip s_common): f16x2 puts the rms of the filter, columns on
+    normalised inputs, at 2^-4: -round(log2 rms) - 4, clamped to [-60, 60] (0 for an all-zero filter); fp32 and bf16 scale nothing.
+    (Until the checkpoint zoo it was the median of conv9_1's exponents, which is the same number while those lie together and says
+    nothing about the filter once they do not: weights.hip build_model.)"""
+    if mode != "f16x2":
+        return 0
+    l = flatten_log2_rms(sd, e_c9)
+    return int(max(-60, min(60, -round(l) - 4))) if np.isfinite(l) else 0
 
 
 def ref_flatten(sd, c9n: torch.Tensor, e_c9, mode: str):
@@ -328,7 +339,7 @@ def ref_flatten(sd, c9n: torch.Tensor, e_c9, mode: str):
     (2^-25 sum |c9|)."""
     e = torch.as_tensor(e_c9, dtype=torch.int64)
     wf, _ = flatten_weights(sd)
-    wfs = scale_w(wf, torch.full((4,), flatten_scale(e)), e).to(torch.float32).to(torch.float64)
+    wfs = scale_w(wf, torch.full((4,), flatten_scale(sd, e, mode)), e).to(torch.float32).to(torch.float64)
     if mode == "bf16":
         wfs = bf16_rn(wfs)
     ref = conv(c9n, wfs, pad=0).squeeze(2)
@@ -338,11 +349,11 @@ def ref_flatten(sd, c9n: torch.Tensor, e_c9, mode: str):
     return ref, bound
 
 
-def ref_head(sd, parts: torch.Tensor, e_c9):
+def ref_head(sd, parts: torch.Tensor, e_c9, mode: str):
     """mask_head_parts from the device's partial sums parts (N, G, 4, W): sum over the row groups, x 2^-s_common, + conv_flatten's
     bias, ReLU, ResBlock1D + Conv1d -> logits (N, 1, W).  The kernel is fp32 in every mode: bound 2^-17 M, M the head's magnitude
     graph on sum_g |parts| 2^-s_common + |b| (the fixed-order fp32 sum of at most 16 partials included)."""
-    fscale = 2.0 ** -flatten_scale(e_c9)
+    fscale = 2.0 ** -flatten_scale(sd, e_c9, mode)
     _, bfl = flatten_weights(sd)
     s = parts.sum(1) * fscale
     logits = mask_head(sd, F.relu(s + bfl.view(1, -1, 1)))

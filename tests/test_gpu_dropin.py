@@ -451,6 +451,49 @@ def test_load_time_check_keeps_fp32_when_f16x2_loses_precision_without_overflow(
     assert r.returncode == 0 and "SELFCHECK_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 
 
+_ZOO_SCRIPT = _DEVJOB_PRELUDE + r"""
+# the load-time check on checkpoints of tests/checkpoint_zoo.py, saved the way a trained one is
+sys.path.insert(0, os.path.join({root!r}, "tests"))
+import checkpoint_zoo as Z
+fallbacks = []
+class Catch(logging.Handler):
+    def emit(self, record):
+        if "fp32 mode" in record.getMessage(): fallbacks.append(record.getMessage())
+logging.getLogger().addHandler(Catch(level=logging.WARNING))
+wav = os.path.join(tmp, "c1_10s.wav")
+synth.write_wav(wav, synth.to_pcm16(synth.synth_audio(1001, 10.0, 16000, 1)), 16000)
+def saved(name):
+    ck = os.path.join(tmp, name + ".pth")
+    torch.save({{"model_state_dict": synth.to_torch_state_dict(Z.build(name)), "epoch": 0}}, ck)
+    return ck
+for name in ("spread6", "signs", "dead"):
+    got, det, ev = job([wav], saved(name), os.path.join(tmp, name + ".csv"), n_ctx=1)
+    print("ZOO", name, det.model.selfcheck_delta, det.model.effective_precision(), len(fallbacks), flush=True)
+    assert not [e for e in ev if e[0] == "msg"], ev
+    assert det.model.selfcheck_delta <= 5e-5 and det.model.effective_precision() == "f16x2" and det.model.hip_context().precision == "f16x2"
+    assert not fallbacks, fallbacks
+ck = saved("runaway")
+got, det, ev = job([wav], ck, os.path.join(tmp, "runaway.csv"), n_ctx=1)
+print("ZOO runaway", det.model.selfcheck_delta, det.model.effective_precision(), fallbacks, flush=True)
+assert not [e for e in ev if e[0] == "msg"], ev
+assert det.model.effective_precision() == "fp32" and det.model.hip_context().precision == "fp32"
+assert len(fallbacks) == 1, fallbacks
+want, det32, _ = job([wav], ck, os.path.join(tmp, "runaway32.csv"), prec="fp32", n_ctx=1)
+assert got == want and len(fallbacks) == 1
+print("ZOO_OK")
+"""
+
+
+def test_load_time_check_on_the_checkpoint_zoo(tmp_path, build_all):
+    """Checkpoints with per-channel gains of 10^+-6, negative gammas and dead channels (tests/checkpoint_zoo.py) through NNDetector and
+    ProcessWorker with the product library, on a 10 s recording: the load-time check passes (f16x2 within 5e-5 of fp32), the detector
+    stays in f16x2 and logs no fall-back.  The runaway checkpoint (BatchNorm scales of 316 compounding: scores ~1e33) ends in fp32 with
+    exactly one fall-back message, and its CSV equals the fp32 detector's."""
+    r = _run_script(_ZOO_SCRIPT, tmp_path, dev=False)
+    print("\n".join(l for l in r.stdout.splitlines() if l.startswith("ZOO")))
+    assert r.returncode == 0 and "ZOO_OK" in r.stdout, (r.stdout[-800:], r.stderr[-3000:])
+
+
 _NOMEM_SCRIPT = _DEVJOB_PRELUDE + r"""
 ck = os.path.join(tmp, "ck.pth")
 synth.save_checkpoint(ck, 0, epoch=0)

@@ -5,7 +5,10 @@ oracle.
 The per-launch checks run in child processes on the development build (SOFTSPOKEN_LIB: ss_debug_activation reads the workspace back).
 A child prints one line per launch,
     LAUNCH <config> <pass> <launch> <max |delta| / bound> <window,y,x,c of the max> <count over the bound> <exact-check mismatches>
-and one COVER line for every plan name of kernel_stats() that has no check; the parent asserts on them."""
+and one COVER line for every plan name of kernel_stats() that has no check; the parent asserts on them.  An f16x2 child also prints
+    EXPONENTS <config> <channels whose exponent is not the host emulation's> <channels excused as rounding ties> <the first few>
+for the exponents ss_debug_activation reports for h1 ... hs, c1 ... s9 and the flatten's partial sums (tests/checkpoint_zoo.py
+exponent_chain)."""
 import os
 import subprocess
 import sys
@@ -27,8 +30,9 @@ from softspoken_amd import synth, native, checkpoint
 from oracle import oracle_np as O
 import layer_ref as R
 import frontend_ref as FR
-tag, mode, hostile, n_sel, out_npy = {tag!r}, {mode!r}, {hostile!r}, {n_sel!r}, {out_npy!r}
-sd = synth.make_state_dict(0, hostile=hostile)
+import checkpoint_zoo as Z
+tag, mode, ckpt, n_sel, out_npy = {tag!r}, {mode!r}, {ckpt!r}, {n_sel!r}, {out_npy!r}
+sd = Z.build(ckpt)
 sig = np.load({sig_npy!r})
 starts = O.plan_windows(len(sig) / 22050.0)
 ctx = native.Context(checkpoint.pack_state_dict(sd), 0, precision=mode, chunk=5)
@@ -121,7 +125,7 @@ def check_pass(pname, n, with_spec, spec, logits):
             if pname == "spec":
                 saved.update({{t: raw[t] for t in ("c1", "c8", "h9")}}, flat_part=parts)
     parts = torch.from_numpy(ctx.debug_activation("flat_part", 0, n)["planes"][0].astype(np.float64))
-    lg, bound = R.ref_head(sd, parts, exps("c9"))
+    lg, bound = R.ref_head(sd, parts, exps("c9"), mode)
     report(pname, "mask_head_parts", R.ratio_report(torch.from_numpy(logits[-n:]).double(), lg, bound))
     if with_spec:
         s9, e_s9 = have["s9"]
@@ -142,6 +146,11 @@ def run(pname, with_spec, chunk):
 
 mask = run("spec", True, 5)
 np.save(out_npy, mask)
+if mode == "f16x2":
+    # the exponents the device chose against the stated rule, -round(log2(sqrt(1/2 sum w^2 + b^2))) through the whole graph on the host
+    # (checkpoint_zoo.exponent_chain): the bounds above are in the device's own units and would hold for any choice
+    bad, ties = Z.exponent_mismatches({{t: ctx.debug_activation(t, 0, 0)["exponents"] for t in Z.EXPONENT_TENSORS}}, sd)
+    print("EXPONENTS", tag, len(bad), ties, ";".join("%s[%d]:%d!=%d" % b for b in bad[:8]), flush=True)
 run("nospec", False, 5)
 if n_sel == 5:
     run("ragged", True, 2)
@@ -181,21 +190,28 @@ def layer_signal(tmp_path_factory):
     return dict(dir=str(d), sig=str(d / "sig.npy"), sel=sel, starts=starts)
 
 
-def _child(tag, mode, env, layer_signal, n_sel=5, hostile=False):
+def _child(tag, mode, env, layer_signal, n_sel=5, hostile=False, ckpt=None):
+    """ckpt: a checkpoint of tests/checkpoint_zoo.py by name; without one, `hostile` picks between the two the suite had before it."""
     from softspoken_amd import build as hip_build
+    ckpt = ckpt or ("hostile" if hostile else "seed0")
     out_npy = os.path.join(layer_signal["dir"], tag + ".npy")
-    code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), tag=tag, mode=mode, hostile=hostile, n_sel=n_sel, out_npy=out_npy,
+    code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), tag=tag, mode=mode, ckpt=ckpt, n_sel=n_sel, out_npy=out_npy,
                          sig_npy=layer_signal["sig"], sel=layer_signal["sel"])
     e = dict(os.environ); e.update(env); e["SOFTSPOKEN_LIB"] = hip_build.DEV_LIB
     r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=900)
     lines = r.stdout.splitlines()
-    print("\n".join(l for l in lines if l.startswith(("LAUNCH", "COVER"))))
+    print("\n".join(l for l in lines if l.startswith(("LAUNCH", "COVER", "EXPONENTS"))))
     assert r.returncode == 0 and any(l.startswith("CHILD_OK") for l in lines), r.stdout[-3000:] + r.stderr[-3000:]
     launches = [l.split() for l in lines if l.startswith("LAUNCH")]
     uncovered = [l for l in lines if l.startswith("COVER")]
     assert not uncovered, "launches without a check: " + "; ".join(uncovered)
     bad = [" ".join(l) for l in launches if not (float(l[4]) <= 1.0 and int(l[6]) == 0 and int(l[7]) == 0)]
     assert not bad, "launches over their bound:\n" + "\n".join(bad)
+    expo = [l.split() for l in lines if l.startswith("EXPONENTS")]
+    assert len(expo) == (1 if mode == "f16x2" else 0), expo
+    assert all(int(l[2]) == 0 for l in expo), "device exponents off the rule: " + " ".join(expo[0])
+    # the checkpoints are fixed, and none has a channel on a rounding tie: the excuse must not be where a wrong rule hides
+    assert all(int(l[3]) == 0 for l in expo), "channels excused as rounding ties: " + " ".join(expo[0])
     return out_npy
 
 
@@ -272,6 +288,18 @@ def test_every_launch_of_the_alternate_forms(env, mode, layer_signal, build_all)
     """The switch sets of test_gpu_parity's test_alternate_kernel_structures and test_conv1_streaming_kernel_variants_agree, whose
     forms are otherwise held only to the score bars: two windows (the pad and the noise)."""
     _child("alt", mode, env, layer_signal, n_sel=2)
+
+
+ZOO = [(name, mode) for name in ("seed7", "spread3", "spread6", "signs", "dead", "tinyvar") for mode in ("f16x2", "fp32")] + \
+      [("spread3", "bf16"), ("dead", "bf16")]
+
+
+@pytest.mark.parametrize("name,mode", ZOO, ids=[f"{n}-{m}" for n, m in ZOO])
+def test_every_launch_on_the_checkpoint_zoo(name, mode, layer_signal, build_all):
+    """The checkpoints of tests/checkpoint_zoo.py (another draw, per-channel gains of 10^+-3 and 10^+-6, negative gammas, dead channels,
+    variances of zero), two windows (the pad and the noise): the same bounds, unchanged, and in f16x2 the device's exponents against
+    the host emulation of the rule.  Dead channels are exact on both sides (0 / 0 counts as exact in ratio_report)."""
+    _child("zoo_" + name, mode, {}, layer_signal, n_sel=2, ckpt=name)
 
 
 @pytest.mark.parametrize("mode,hostile", [("fp32", False), ("f16x2", False), ("bf16", False), ("f16x2", True), ("fp32", True)])

@@ -311,7 +311,7 @@ def _flatten_head(sd, mode, defect=None, groups=8):
     e = torch.tensor([(i % 5) - 2 for i in range(32)], dtype=torch.int64) if mode == "f16x2" else torch.zeros(32, dtype=torch.int64)
     c9n = R.scale(c9, e).to(torch.float32).to(torch.float64)
     wf, bfl = R.flatten_weights(sd)
-    wfs = R.scale_w(wf, torch.full((4,), R.flatten_scale(e)), e).to(torch.float32).to(torch.float64)
+    wfs = R.scale_w(wf, torch.full((4,), R.flatten_scale(sd, e, mode)), e).to(torch.float32).to(torch.float64)
     if mode == "bf16":
         c9n, wfs = R.bf16_rn(c9n), R.bf16_rn(wfs)
     if mode == "f16x2":
@@ -337,7 +337,7 @@ def _flatten_head(sd, mode, defect=None, groups=8):
     ref, bound = R.ref_flatten(sd, c9n, e, mode)
     flat_rep = R.ratio_report(parts.sum(1), ref, bound)
     # the head kernel (fp32) from the partial sums
-    fscale = 2.0 ** -R.flatten_scale(e)
+    fscale = 2.0 ** -R.flatten_scale(sd, e, mode)
     s = (parts.sum(1) * fscale).to(torch.float32).to(torch.float64)
     b = torch.zeros_like(bfl) if defect == "missing_flatten_bias" else bfl
     xin = F.relu(s + b.view(1, -1, 1))
@@ -351,7 +351,7 @@ def _flatten_head(sd, mode, defect=None, groups=8):
     else:
         got = R.mask_head(sd, xin)
     got = got.to(torch.float32).to(torch.float64)
-    lg, hb = R.ref_head(sd, parts, e)
+    lg, hb = R.ref_head(sd, parts, e, mode)
     return flat_rep, R.ratio_report(got, lg, hb)
 
 
