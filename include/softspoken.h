@@ -458,6 +458,10 @@ int64_t ss_workspace_bytes(ss_ctx* ctx);
  * error; nth < 0 switches it off.  The context must come out of such a failure without a workspace (and allocate one afresh on
  * the next call), never with dangling tensors. */
 int ss_debug_fail_workspace_alloc(ss_ctx* ctx, int nth);
+/* ss_separate_pcm holds at most `frames` resynthesised STFT frames at once (never fewer than 16) in place of the number that fits its
+ * 256 MB frame buffer, so that a short recording meets the cuts of a long one: a chunk ends when the next piece would pass the number,
+ * an interval is cut into pieces of (frames - 8) hops.  frames <= 0: the product's number again.  The bytes written must not depend on it. */
+int ss_debug_set_separation_budget(ss_ctx* ctx, int64_t frames);
 /* Activation tensors of the context's last network pass, for per-launch tests.  name: a tensor of the activation workspace ("h1" ... "s9"),
  * "feat" (the pass's features) or "flat_part" (conv_flatten's row-group partial sums, fp32 [n][groups][4][256] read as H = groups,
  * W = 4, C = 256; exponents: the common power of two they carry).  Copies windows [first_window, first_window + n_windows) of one plane as stored, [n][H][W][C]: fp32,

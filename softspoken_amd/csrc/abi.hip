@@ -881,6 +881,11 @@ extern "C" int ss_debug_fail_workspace_alloc(ss_ctx* c, int nth) {
     c->fail_alloc_after = nth < 0 ? -1 : nth;
     return SS_OK;
 }
+extern "C" int ss_debug_set_separation_budget(ss_ctx* c, int64_t frames) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    c->sep_budget = frames < 0 ? 0 : frames;
+    return SS_OK;
+}
 extern "C" int ss_debug_activation(ss_ctx* c, const char* name, int plane, int64_t first_window, int64_t n_windows, void* out, int64_t out_bytes,
                                    int32_t* shape, int32_t* exponents) {
     return debug_activation(c, name, plane, first_window, n_windows, out, out_bytes, shape, exponents);

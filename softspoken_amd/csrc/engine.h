@@ -164,6 +164,7 @@ struct ss_ctx {
     hipStream_t lane_stream = nullptr; hipEvent_t lane_ev_in = nullptr, lane_ev_out = nullptr;
     int* d_range_flag = nullptr; int* h_range_flag = nullptr;    // f16x2: set by the conv kernels when a value does not fit an f16
     int fail_alloc_after = -1;                            // dev build's test hook (ss_debug_fail_workspace_alloc): the n-th workspace allocation from now fails
+    int64_t sep_budget = 0;                               // dev build's test hook (ss_debug_set_separation_budget): frames per chunk of ss_separate_pcm; 0: from kSepFrameBytes
     bool split_range_ok = true;                           // f16x2: cleared while packing when a folded weight has no f16 representation
     // f16x2: power-of-two channel exponents of every activation tensor, by tensor name (weights.hip; all zero in the other modes and under
     // SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c

@@ -530,7 +530,11 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
         SepTables* tb = nullptr;
         if ((rc = sep_tables(c, sr, &tb))) return rc;
         const int N = pl.N, hop = pl.hop, npairs = (ch + 1) / 2;
+#ifdef SS_DEVBUILD      // ss_debug_set_separation_budget: the tests move the piece and chunk cuts through short recordings
+        const int64_t budget = std::max<int64_t>(16, c->sep_budget > 0 ? c->sep_budget : (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2))));
+#else
         const int64_t budget = std::max<int64_t>(16, (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2))));
+#endif
         const int64_t piece = (budget - 8) * hop;
         std::vector<SepFrame> fr;
         std::vector<SepSeg> sg;

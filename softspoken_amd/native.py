@@ -160,6 +160,7 @@ EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
 _DEV_SIGS = {
     "ss_debug_fail_workspace_alloc": (C.c_int, [_P, C.c_int]),
+    "ss_debug_set_separation_budget": (C.c_int, [_P, C.c_int64]),
     "ss_debug_activation": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 
@@ -579,6 +580,10 @@ class Context:
     def debug_fail_workspace_alloc(self, nth: int):
         """Development build only (SOFTSPOKEN_LIB=libsoftspoken_hip_dev.so)."""
         self._ck(lib().ss_debug_fail_workspace_alloc(self._h, int(nth)))
+
+    def debug_set_separation_budget(self, frames: int):
+        """Development build only: separate_pcm holds at most `frames` STFT frames at once (floor 16; <= 0: the product's number)."""
+        self._ck(lib().ss_debug_set_separation_budget(self._h, int(frames)))
 
     def debug_activation(self, name: str, first: int, n: int) -> dict:
         """Development build only: tensor `name` ("h1" ... "s9", "feat", "flat_part") of the last network pass, windows [first, first + n)

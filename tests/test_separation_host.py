@@ -117,3 +117,93 @@ def test_reference_gains():
     assert np.allclose(R.band_gains(m, min_gain=0.7), 0.7)
     w = R.freq_weights(1024, 48000)
     assert np.allclose(w.sum(axis=1)[: int(8000 * 1024 / 48000) + 1], 1.0) and not w[int(np.ceil(8000 * 1024 / 48000)):].any()
+
+
+# ---- the unrounded output, the float32 restatement and the crafted heads (CPU oracle only) -------------------------------------
+def _random_case(sr, ch, seconds, seed):
+    """A recording, regions and per-window maps from a seeded generator (no network): enough for the reference's own arithmetic."""
+    rng = np.random.default_rng(seed)
+    frames = int(seconds * sr)
+    x = rng.uniform(-0.5, 0.5, size=(frames, ch)).astype(np.float32)
+    W, _ = R.file_geometry(sr, frames)
+    base = rng.uniform(0.0, 1.2, size=(2, 128, 256 + 52 * W))
+    by_win = {i: np.maximum(base[:, :, R.win_start(i):R.win_start(i) + 256] - 0.2, 0.0).astype(np.float32) for i in range(W)}
+    return x, [(-1.0, 0.11), (0.3, 0.3 + 1.0 / sr), (0.5, 0.74), (0.7, 0.8), (seconds - 0.1, 99.0)], by_win
+
+
+# sha256 of separate()'s int16 bytes as it stood before it learnt to return the unrounded output, on _random_case's inputs
+_BEFORE = {(48000, 2): "29054345f876556921bae8c80e6c3f0f29600770ca45bff307d9c291f227b12a", (8000, 1): "1634bd9aa4ee26e649adb6af93049fd7c92fa76083469f180d4be370efe2390b", (96000, 3): "7dcc6903948e708dc8ec074cf0c3f0ad1ea9264fa94c693f93e9973e37762fbc"}
+
+
+@pytest.mark.parametrize("sr,ch", list(_BEFORE))
+def test_unrounded_output_rounds_to_the_int16_output(sr, ch):
+    import hashlib
+    x, regions, by_win = _random_case(sr, ch, 1.0, 7)
+    kw = dict(fade_s=0.02, min_gain=0.05, above_fmax="keep")
+    out = R.separate(x, sr, regions, by_win, **kw)
+    out2, y64 = R.separate(x, sr, regions, by_win, unrounded=True, **kw)
+    assert out.dtype == np.int16 and np.array_equal(out, out2)
+    assert hashlib.sha256(out.tobytes()).hexdigest() == _BEFORE[(sr, ch)]
+    assert y64.dtype == np.float64 and np.array_equal(np.rint(y64).astype(np.int64).astype(np.int16), out)
+    m = np.zeros(len(x), dtype=bool)
+    for a, b in R.merged_intervals(regions, sr, len(x)):
+        m[a:b] = True
+    assert np.array_equal(y64[~m], (x[~m] * np.float32(32767.0)).astype(np.float64))        # outside: the float32 transcode's value
+    y32 = R.separate_f32(x, sr, regions, by_win, **kw)
+    assert y32.dtype == np.float32 and np.array_equal(y32[~m].astype(np.float64), y64[~m])
+    assert 0.0 < np.abs(y32.astype(np.float64) - y64).max() <= 0.05
+
+
+@pytest.fixture(scope="module")
+def oracle_cases(sd_np):
+    """The GPU tests' FFT-size cases (test_gpu_separation.B1_CASES) with the fp32 CPU oracle in the device's place: per case and head,
+    the recording and the spec maps of the plan's windows."""
+    import test_gpu_separation as T
+    from softspoken_amd import native
+    from oracle import oracle_np as O
+    heads = dict(spread=R.spread_head(sd_np), mixed=R.mixed_head(sd_np))
+    cache = {}
+
+    def get(head, sr, ch, fmt):
+        key = (head, sr, ch, fmt)
+        if key not in cache:
+            data, info, x, wav = T._make(fmt, sr, ch, T.B1_SECONDS, T.B1_SEED, scale=0.5)
+            plan = native.separation_plan(sr, info.frames, T.B1_REGIONS)
+            wins = sorted({i for r in plan["ranges"] for i in range(r["win_first"], r["win_last"] + 1)})
+            sig, _, _ = O.load_audio_from_bytes(wav)
+            spec = R._oracle_spec(heads[head], O.pad_3s(sig), wins)
+            cache[key] = (x, {w: spec[t] for t, w in enumerate(wins)}, plan)
+        return cache[key]
+    return get
+
+
+def test_crafted_heads_meet_their_conditions(oracle_cases):
+    """Conditions on the inputs of the GPU parity cases, met by the oracle alone: the spread head's gains move with band and with time
+    around 0.5; the mixed head has cells of gain exactly 0, exactly 1 and in between."""
+    import test_gpu_separation as T
+    for sr, ch, fmt in [c[0:1] + c[2:] for c in T.B1_CASES] + [(48000, 2, "pcm16")]:
+        x, by_win, plan = oracle_cases("spread", sr, ch, fmt)
+        st = R.gain_stats([R.band_gains(R.average_maps(by_win, range(r["bin_first"], r["bin_last"] + 1))) for r in plan["ranges"]])
+        print("spread", sr, ch, st)
+        R.assert_spread(st)
+        assert st["zero"] == 0.0 and st["one"] == 0.0
+    for sr, ch, fmt in ((48000, 2, "pcm16"), (8000, 1, "pcm16")):
+        x, by_win, plan = oracle_cases("mixed", sr, ch, fmt)
+        st = R.gain_stats([R.band_gains(R.average_maps(by_win, range(r["bin_first"], r["bin_last"] + 1))) for r in plan["ranges"]])
+        print("mixed", sr, ch, st)
+        R.assert_mixed(st)
+
+
+def test_float32_restatement_stays_near_the_reference(oracle_cases):
+    """separate_f32 (complex64 FFTs, float32 overlap-add and blend) against the unrounded float64 output on the GPU tests' cases: a
+    sanity cap of 0.05 LSB (measured: 0.0008 - 0.0012), so that tau = 4 e32 of the device's bound stays far below the rounding's 0.5."""
+    import test_gpu_separation as T
+    for sr, n_fft, ch, fmt in T.B1_CASES:
+        x, by_win, plan = oracle_cases("spread", sr, ch, fmt)
+        ivs = []
+        out, y64 = R.separate(x, sr, T.B1_REGIONS, by_win, unrounded=True, info=ivs)
+        y32 = R.separate_f32(x, sr, T.B1_REGIONS, by_win)
+        e32 = float(np.abs(y32.astype(np.float64) - y64).max())
+        print(f"N={n_fft} sr={sr} ch={ch} {fmt}: e32 = {e32:.5f} LSB")
+        assert plan["n_fft"] == n_fft and len(ivs) == 4 and 0.0 < e32 <= 0.05
+        assert np.array_equal(np.rint(y64).astype(np.int64).astype(np.int16), out)
