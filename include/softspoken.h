@@ -370,6 +370,65 @@ int ss_stream_free(ss_ctx* ctx, int stream_id);
 int ss_stream_export(ss_ctx* ctx, int stream_id, void* buf, int64_t cap, int64_t* n_out);
 int ss_stream_import(ss_ctx* ctx, const void* buf, int64_t n, int* stream_id);
 
+/* ---- streaming silencer: a stream's frames back as final 16-bit PCM, the detected speech zeroed ------------------------------
+ * A stream opened with ss_stream_open_output also returns, after every step, the next run of the recording's frames as interleaved
+ * 16-bit PCM (ss_stream_output).  Returned frames are final and contiguous: every step continues where the last one ended.
+ * Equality: the concatenation of everything ss_stream_output returned from open until the stream finished equals, byte for byte,
+ *     ss_silence_pcm(the whole recording, E(R)),    R = the concatenation of the regions the same stream returned,
+ * for any split into pieces, any cadence of steps, whichever streams shared the step, and across ss_stream_export / _import.
+ *
+ * Erase table E(R; pad_s, min_len_s) (ss_erase_table): every region with end - start <= min_len_s is dropped (the review screen's
+ * filter, on the table's doubles), every other one becomes [start - pad_s, end + pad_s]; ss_silence_pcm then rounds, clamps and merges
+ * as it always does.  Both parameters are finite and >= 0; NULL means 0, 0.  (A voice starts before its score crosses the threshold:
+ * pad_s; nobody reviews a live feed: min_len_s.)
+ *
+ * Which frames a step returns.  A frame is decided when its output value is the same for every continuation of the recording.  With b
+ * final bins and P the merged candidate that is not final yet (the walk's current region, joined with the open run of bins above the
+ * threshold when that run starts within break_s of its end), the limit time is
+ *     no P:                              L = (bin_time(b) - 3) - pad_s       (no later region can start earlier)
+ *     P already passes the filter:       L = (P.end - 3) + pad_s             (P only grows: up to there it is erased whatever follows)
+ *     P does not pass the filter yet:    L = (P.start - 3) - pad_s
+ * and the step returns the frames [frames_out, min(max(nearbyint(L x sample_rate), frames_out), frames decoded)); at close, all of
+ * them (ss_stream_output_limit is this rule, host only).  A current region that an open run can no longer reach (the run started more
+ * than break_s behind its end) is final though not returned yet, and is erased as such.
+ *
+ * Latency bound D.  A frame at audio time t is returned by the first step after the stream holds audio past t + D,
+ *     D = B + break_s + pad_s + min_len_s         (B: the bound of the bins above).
+ * Derivation: with audio held up to H every bin before H - B + (3 / 256) s is final (B carries one bin more than a bin needs), so
+ * bin_time(b) - 3 >= H - B + 3 / 256.  An open run ends at bin b - 1; a current region without an open run ends at most break_s before
+ * bin b - 1 (or the walk had returned it); a P that fails the filter is at most min_len_s long.  So in every case
+ * L >= bin_time(b - 1) - 3 - break_s - min_len_s - pad_s >= H - D.  (Bins no window covers neither open nor close a run; a whole-file
+ * plan has them only behind the last window, where the close decides.)
+ *
+ * State.  A stream with output also carries its raw PCM from the first frame not returned to the last one decoded, on the device, in
+ * its own encoding: at most D seconds plus what one step decoded, whatever the stream's length; ss_stream_info.state_bytes counts it.
+ * A refused f16x2 step (SS_ERR_RANGE) commits nothing of the output either. */
+typedef struct ss_stream_erase { double pad_s, min_len_s; } ss_stream_erase;
+typedef struct ss_stream_output_info {
+    int64_t frames_out;        /* frames returned so far: the next step's first_frame */
+    int64_t frames_held;       /* frames pushed and not returned yet (carried on the device, or staged) */
+    int64_t frames_erased;     /* of the frames returned: zeroed */
+    double pad_s, min_len_s;   /* the stream's erase parameters */
+} ss_stream_output_info;
+/* E(R) as regions (host only): *n_out = count, SS_ERR_CAPACITY when it exceeds cap (out may be NULL to ask for the count).  Rows that
+ * hold a NaN stay (ss_silence_pcm passes over them). */
+int ss_erase_table(const ss_region* regions, int64_t n, const ss_stream_erase* erase, ss_region* out, int64_t cap, int64_t* n_out);
+/* The limit frame nearbyint(L x sample_rate) of the rule above, before the clamp to [frames_out, frames decoded] (host only).
+ * pending != 0: P exists; pending_start / pending_end are the bin times of its first and last bin BEFORE the reference's -3 s (the
+ * filter is evaluated on (end - 3) - (start - 3), the values the table will hold).  INT64_MIN on a bad argument. */
+int64_t ss_stream_output_limit(int sample_rate, int64_t bins_final, int pending, double pending_start, double pending_end,
+                               const ss_stream_erase* erase);
+/* ss_stream_open with output; erase == NULL: pad_s = min_len_s = 0.  The threshold may be infinite here (+inf: the plain transcode;
+ * -inf: every bin a window covers is speech).  Everything else of the stream is ss_stream_open's. */
+int ss_stream_open_output(ss_ctx* ctx, int format, int sample_rate, int channels, double threshold, double break_s,
+                          const ss_stream_erase* erase, int* stream_id);
+/* The frames the last step returned: frames [*first_frame, *first_frame + *n_frames) of the recording as *n_frames x channels int16.
+ * out == NULL asks for the two counts; SS_ERR_CAPACITY when cap_frames < *n_frames; SS_ERR_STATE on a stream opened without output. */
+int ss_stream_output(ss_ctx* ctx, int stream_id, int16_t* out, int64_t cap_frames, int64_t* first_frame, int64_t* n_frames);
+int ss_stream_get_output_info(ss_ctx* ctx, int stream_id, ss_stream_output_info* out);
+/* Images: a stream with output exports "SSSTRM03" (the header, the step, the erase parameters, frames_out, the decided ranges still
+ * ahead and the held PCM); ss_stream_import reads all three, and a stream without output writes the image it always wrote. */
+
 /* ---- separation silencer: remove the speech part of the spectrum inside the erased intervals ---------------------------
  * The second silencing method.  ss_silence_pcm zeroes every reviewed interval (silencer_ui.py:974-998), and with it whatever
  * environmental sound overlaps the voice.  This one rebuilds the audio inside the same intervals from an STFT at the file's native

@@ -287,6 +287,10 @@ bool step_ok(double step_s);                              // a window step ss_se
 int64_t step_samples(double step_s);                      // floor(22050 step): samples between window starts
 inline double step_bins(double step_s) { return step_s * 256.0 / 3.0; }   // s_b: bins between window starts, before the rounding of a start
 std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);
+// the streaming silencer's erase table (ss_erase_table): the length filter and the padding of one region of the table
+bool erase_ok(const ss_stream_erase* e);                  // NULL, or both parameters finite and >= 0
+inline bool erase_keeps(const ss_region& r, double min_len_s) { return !(r.end - r.start <= min_len_s); }
+inline ss_region erase_padded(const ss_region& r, double pad_s) { return ss_region{r.start - pad_s, r.end + pad_s}; }
 double now_ms();
 
 }  // namespace ss

@@ -1377,6 +1377,80 @@ __global__ __launch_bounds__(256) void stream_average_kernel(const StreamAvg* __
     }
 }
 
+// Streaming silencer: frames [frame0, frame0 + n) of every stream with output as interleaved 16-bit PCM, the frames inside the step's
+// ranges zeroed -- silence_encode_kernel's arithmetic sample for sample (decode_sample, x * 32767 without contraction, round to nearest
+// even, no clipping), so the bytes equal ss_silence_pcm's by construction.  The frames come from two segments in the stream's native
+// encoding: the first n0 from seg0 (the raw PCM carried from earlier steps), the rest from seg1 (this step's pieces in the upload); both
+// start at a frame and are aligned to a sample, which is all decode_sample's typed reads ask for (24-bit samples are read by bytes, so a
+// frame boundary of 3 or 9 bytes needs no more).  Four samples per thread; the 8-byte store is taken only where the output address is
+// 8-byte aligned (the host places every stream's output at a multiple of 16 bytes, so it is whenever four samples are left).
+__global__ __launch_bounds__(256) void stream_silence_kernel(const StreamSilence* __restrict__ ds, int n, short* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamSilence d = ds[k];
+        const int64_t total = d.n * d.channels, split = d.n0 * d.channels;
+        short* o = out + d.out_off;
+        for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 1024) {
+            short v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t idx = i + q;
+                if (idx >= total) { v[q] = 0; continue; }
+                const int64_t fr = d.frame0 + idx / d.channels;
+                int lo = 0, hi = d.n_ranges;                  // first range whose end is beyond fr
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (d.ranges[2 * mid + 1] <= fr) lo = mid + 1; else hi = mid;
+                }
+                const bool cut = lo < d.n_ranges && d.ranges[2 * lo] <= fr;
+                const float x = (idx < split ? decode_sample(d.seg0, d.format, idx) : decode_sample(d.seg1, d.format, idx - split)) * 32767.0f;
+                v[q] = cut ? (short)0 : (short)__float2int_rn(x);
+            }
+            if (i + 3 < total && ((uintptr_t)(o + i) & 7) == 0) {
+                *(uint2*)(o + i) = make_uint2((unsigned)(unsigned short)v[0] | ((unsigned)(unsigned short)v[1] << 16),
+                                              (unsigned)(unsigned short)v[2] | ((unsigned)(unsigned short)v[3] << 16));
+            } else {
+                for (int q = 0; q < 4 && i + q < total; ++q) o[i + q] = v[q];
+            }
+        }
+    }
+}
+
+// raw PCM carried into the other half of the byte arena: n bytes from src to dst, any two addresses.  The bytes in front of dst's first
+// 16-byte boundary and behind its last one are copied one by one; in between every thread stores 16 aligned bytes, which it loads as
+// one 16-byte word where src is congruent to dst modulo 16, as four 4-byte words where it is modulo 4 (16-bit stereo, 32-bit samples),
+// and byte by byte otherwise (24-bit and odd channel counts: a frame boundary falls anywhere)
+__global__ __launch_bounds__(256) void stream_copy_bytes_kernel(const StreamCopyBytes* __restrict__ segs, int n_segs) {
+    for (int k = blockIdx.y; k < n_segs; k += gridDim.y) {
+        const StreamCopyBytes sg = segs[k];
+        const int64_t to16 = (int64_t)((16 - ((uintptr_t)sg.dst & 15)) & 15);
+        const int64_t head = to16 < sg.n ? to16 : sg.n;
+        const int64_t body = (sg.n - head) / 16;            // 16-byte words
+        const int64_t tail0 = head + body * 16;
+        const unsigned rel = (unsigned)(((uintptr_t)sg.src + (uintptr_t)head) & 15);
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < body + 32; t += (int64_t)gridDim.x * 256) {
+            if (t >= body) {                                 // the (at most 15 + 15) bytes around the body
+                const int64_t e = t - body;
+                const int64_t at = e < 16 ? e : tail0 + (e - 16);
+                if (e < 16 ? e < head : at < sg.n) sg.dst[at] = sg.src[at];
+                continue;
+            }
+            const unsigned char* s = sg.src + head + t * 16;
+            uint4 w;
+            if (rel == 0) w = *(const uint4*)s;
+            else if ((rel & 3) == 0) { const unsigned* s4 = (const unsigned*)s; w = make_uint4(s4[0], s4[1], s4[2], s4[3]); }
+            else {
+                unsigned b[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    b[q] = (unsigned)s[4 * q] | ((unsigned)s[4 * q + 1] << 8) | ((unsigned)s[4 * q + 2] << 16) | ((unsigned)s[4 * q + 3] << 24);
+                w = make_uint4(b[0], b[1], b[2], b[3]);
+            }
+            *(uint4*)(sg.dst + head + t * 16) = w;
+        }
+    }
+}
+
 static dim3 stream_grid(int n, int64_t max_elems) {
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_elems + 255) / 256, 1024));
     return dim3(gx, (unsigned)std::min(n, 65535));
@@ -1400,6 +1474,16 @@ hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n,
 hipError_t launch_stream_average(const StreamAvg* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s) {
     if (n <= 0 || max_bins <= 0) return hipSuccess;
     hipLaunchKernelGGL(stream_average_kernel, stream_grid(n, max_bins), dim3(256), 0, s, d, n, avg, flags);
+    return hipGetLastError();
+}
+hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s) {
+    if (n <= 0 || max_samples <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_silence_kernel, stream_grid(n, (max_samples + 3) / 4), dim3(256), 0, s, d, n, out);
+    return hipGetLastError();
+}
+hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s) {
+    if (n <= 0 || max_bytes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_copy_bytes_kernel, stream_grid(n, max_bytes / 16 + 32), dim3(256), 0, s, d, n);
     return hipGetLastError();
 }
 

@@ -280,6 +280,43 @@ std::vector<int64_t> ss::silence_ranges(const ss_region* regions, int64_t n, int
     }
     return out;
 }
+// ------------------------------------------------------------------------------------------------------
+// streaming silencer (stream.hip): the erase table of a region table, and the frame up to which a stream's output is decided
+// ------------------------------------------------------------------------------------------------------
+bool ss::erase_ok(const ss_stream_erase* e) {
+    return !e || (std::isfinite(e->pad_s) && std::isfinite(e->min_len_s) && e->pad_s >= 0 && e->min_len_s >= 0);
+}
+
+// E(R): the review screen's length filter on the table's own doubles (review.py:31 drops end - start <= min length; a NaN row compares
+// false and stays, for silence_ranges to pass over), then pad_s on either side.  silence_ranges does the rest.
+extern "C" int ss_erase_table(const ss_region* regions, int64_t n, const ss_stream_erase* erase, ss_region* out, int64_t cap, int64_t* n_out) {
+    if (n < 0 || (n > 0 && !regions) || !n_out || !erase_ok(erase)) return fail(nullptr, SS_ERR_ARG, "ss_erase_table: bad argument");
+    const ss_stream_erase e = erase ? *erase : ss_stream_erase{0, 0};
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; ++i) m += erase_keeps(regions[i], e.min_len_s) ? 1 : 0;
+    *n_out = m;
+    if (!out) return SS_OK;
+    if (cap < m) return fail(nullptr, SS_ERR_CAPACITY, "ss_erase_table: capacity < " + std::to_string(m));
+    m = 0;
+    for (int64_t i = 0; i < n; ++i) if (erase_keeps(regions[i], e.min_len_s)) out[m++] = erase_padded(regions[i], e.pad_s);
+    return SS_OK;
+}
+
+// The limit time L of include/softspoken.h, rounded as silence_ranges rounds a region's edge.  pending_start / pending_end are the walk's
+// bin times (RunMerger::cur's, before the -3 s); the filter is evaluated on the values the table will hold.
+extern "C" int64_t ss_stream_output_limit(int sr, int64_t bins_final, int pending, double pending_start, double pending_end,
+                                          const ss_stream_erase* erase) {
+    if (sr <= 0 || bins_final < 0 || !erase_ok(erase) || (pending && !(pending_end >= pending_start))) return INT64_MIN;
+    const ss_stream_erase e = erase ? *erase : ss_stream_erase{0, 0};
+    double L;
+    if (!pending) L = (bin_time(bins_final) - 3.0) - e.pad_s;
+    else {
+        const ss_region r{pending_start - 3.0, pending_end - 3.0};
+        L = erase_keeps(r, e.min_len_s) ? erase_padded(r, e.pad_s).end : erase_padded(r, e.pad_s).start;
+    }
+    const double f = std::nearbyint(L * (double)sr);
+    return (int64_t)std::min(std::max(f, -9.0e18), 9.0e18);
+}
 // Canonical 44-byte RIFF/WAVE header of a 16-bit PCM file (what libsndfile writes for subtype PCM_16).
 extern "C" int ss_wav_header_pcm16(int sr, int ch, int64_t frames, void* out44) {
     const int64_t data = frames * ch * 2;

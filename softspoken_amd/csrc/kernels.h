@@ -262,6 +262,14 @@ struct StreamResample { const float* mono; int64_t mono_base, frames; const floa
 // bins [b0, b0 + nb) from the windows [w0, W) whose logits lie back to back at `logits`; results at avg / flags [out_off ..); step: the
 // stream's window step in seconds (window i starts at bin rint(i step / (3 / 256)), as ss_window_start_bin), s_b = step x 256 / 3
 struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, nb, out_off; double threshold, step, s_b; };
+// streaming silencer: frames [frame0, frame0 + n) of a stream -> out[out_off ..) as interleaved int16; the first n0 frames are read from
+// seg0, the others from seg1 (native encoding, each aligned to a sample); frames inside ranges (n_ranges disjoint ascending [begin, end)
+// pairs of recording frame numbers) are zero
+struct StreamSilence { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, frame0, n, out_off;
+                       int32_t n_ranges, format, channels, pad; };
+struct StreamCopyBytes { const unsigned char* src; unsigned char* dst; int64_t n; };   // n bytes, any alignment
+hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s);
+hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s);
 hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s);
 hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s);
 hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s);

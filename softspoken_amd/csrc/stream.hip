@@ -5,6 +5,8 @@
 //   -> new logits behind the carried ones -> averaging of the bins that became final -> regions continued on the host.
 // Nothing of the stream state changes before the step has completed without SS_ERR_RANGE: the arena half the streams live in is only
 // read, and the host records are updated at the end (commit), so a refused step leaves every stream as it was.
+// Streams opened with output (ss_stream_open_output) then get their decided frames back as 16-bit PCM with the detected speech zeroed
+// (step_output, behind the commit): the raw PCM not returned yet is carried in a byte arena of the same two-half discipline.
 #include "engine.h"
 
 #include <algorithm>
@@ -39,6 +41,14 @@ struct StreamRec {
     bool run_open = false; int64_t run_first = 0, run_last = 0; RunMerger mg;
     // the last step's results
     std::vector<ss_region> r_out; std::vector<double> a_out; std::vector<int64_t> b_out;
+    // output (ss_stream_open_output): frames [0, frames_out) are returned; the raw PCM of [frames_out, frames_in) is carried in the
+    // current half of the byte arena (byte offset raw_off, a multiple of 16) -- or in h_raw after an import (on_host); er_rng: the frame
+    // ranges [begin, end) of the returned regions' erase table that reach past frames_out (ascending, merged)
+    bool out_on = false; ss_stream_erase er{0, 0};
+    int64_t frames_out = 0, erased = 0, raw_off = 0;
+    std::vector<int64_t> er_rng; std::vector<unsigned char> h_raw;
+    int64_t o_first = 0, o_n = 0, o_off = 0;          // the last step's frames: o_n of them at the pinned output buffer + o_off (int16s)
+    int64_t frame_bytes() const { return (int64_t)ch * (int64_t)pcm_bytes_per_sample(format); }
 };
 
 // what the next step does with a stream (host arithmetic only)
@@ -52,7 +62,8 @@ struct StreamPlan {
     int64_t b_end = 0; int W_avg = 0;                 // bins [bins_done, b_end) become final
     int64_t lw0 = 0;                                  // logits in the step's arena: windows [lw0, i_end)
     // offsets in the next arena half
-    int64_t mono_off = 0, sig_off = 0, lg_off = 0, up_off = 0, host_off = 0;
+    int64_t mono_off = 0, sig_off = 0, lg_off = 0, up_off = 0, host_off = 0, raw_up_off = 0;
+    int64_t f0 = 0; bool was_host = false;            // frames decoded before the step; the carried state came from an image
     int64_t mono_len() const { return F - kb; }
     int64_t sig_len() const { return sig_keep + pre + (m_end - m_next_) + post; }
     int64_t m_next_ = 0;
@@ -75,6 +86,7 @@ StreamPlan plan_stream(const StreamRec& s) {
     StreamPlan p;
     p.m_next_ = s.m_next;
     p.F = s.frames_in + s.staged_frames;
+    p.f0 = s.frames_in; p.was_host = s.on_host;
     p.closing = s.closed;
     const bool direct = s.sr == SS_SAMPLE_RATE;
     // outputs whose taps all lie inside the input (or past a closed stream's end)
@@ -134,15 +146,23 @@ struct StreamSet {
     double* d_avg = nullptr; size_t avg_cap = 0;
     unsigned char* d_flags = nullptr; size_t flags_cap = 0;
     std::vector<double> h_avg; std::vector<unsigned char> h_flags;
+    // streams with output: the carried raw PCM in two halves like the arena, the step's second (small) upload of descriptors and
+    // ranges, the step's output on the device and in pinned memory
+    unsigned char* barena[2] = {nullptr, nullptr}; size_t barena_cap[2] = {0, 0}; int bcur = 0;
+    unsigned char* d_up2 = nullptr; size_t up2_cap = 0;
+    unsigned char* h_up2 = nullptr; size_t h_up2_cap = 0;
+    short* d_out = nullptr; size_t out_cap = 0;
+    unsigned char* h_out = nullptr; size_t h_out_cap = 0;
 };
 
 void free_streams(ss_ctx* c) {
     StreamSet* S = c->streams;
     if (!S) return;
     for (float* a : S->arena) if (a) hipFree(a);
-    void* ds[] = {S->d_up, S->d_newlg, S->d_avg, S->d_flags};
+    void* ds[] = {S->d_up, S->d_newlg, S->d_avg, S->d_flags, S->barena[0], S->barena[1], S->d_up2, S->d_out};
     for (void* p : ds) if (p) hipFree(p);
-    if (S->h_up) hipHostFree(S->h_up);
+    void* hs[] = {S->h_up, S->h_up2, S->h_out};
+    for (void* p : hs) if (p) hipHostFree(p);
     delete S;
     c->streams = nullptr;
 }
@@ -163,7 +183,8 @@ static StreamRec* find_stream(ss_ctx* c, int id) {
 }
 
 static int64_t state_bytes(const StreamRec& s) {
-    return (int64_t)sizeof(StreamRec) + 4 * (s.mono_n + s.sig_n + s.lg_n * 256);
+    return (int64_t)sizeof(StreamRec) + 4 * (s.mono_n + s.sig_n + s.lg_n * 256) +
+           (s.out_on ? (s.frames_in - s.frames_out) * s.frame_bytes() + 8 * (int64_t)s.er_rng.size() : 0);
 }
 
 static int init_rates(ss_ctx* c, StreamRec& s) {
@@ -171,21 +192,33 @@ static int init_rates(ss_ctx* c, StreamRec& s) {
     return get_taps(c, s.sr, s.L, s.M, s.half, &s.d_taps);
 }
 
-extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, int* id) {
+static int open_stream(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase, bool out_on, int* id) {
     static const unsigned char one[8] = {0};
     int rc = check_pcm_args(c, one, format, sr, ch, 0);
     if (rc) return rc;
-    if (!id || !std::isfinite(threshold) || !std::isfinite(break_s)) return fail(c, SS_ERR_ARG, "ss_stream_open: bad argument");
+    // (a stream with output takes an infinite threshold: +inf is the plain transcode, -inf erases everything a window covers)
+    if (!id || (out_on ? std::isnan(threshold) : !std::isfinite(threshold)) || !std::isfinite(break_s)) return fail(c, SS_ERR_ARG, "ss_stream_open: bad argument");
+    if (!erase_ok(erase)) return fail(c, SS_ERR_ARG, "ss_stream_open_output: pad_s and min_len_s must be finite and >= 0");
     if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
     hipSetDevice(c->device);
     StreamRec s;
     s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.mg.brk = break_s;
     s.step = c->step; s.per_step = step_samples(c->step);
+    s.out_on = out_on; if (erase) s.er = *erase;
     if ((rc = init_rates(c, s))) return rc;
     StreamSet& S = streams_of(c);
     *id = S.next_id++;
     S.s.emplace(*id, std::move(s));
     return SS_OK;
+}
+
+extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, int* id) {
+    return open_stream(c, format, sr, ch, threshold, break_s, nullptr, false, id);
+}
+
+extern "C" int ss_stream_open_output(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
+                                     int* id) {
+    return open_stream(c, format, sr, ch, threshold, break_s, erase, true, id);
 }
 
 extern "C" int ss_stream_push(ss_ctx* c, int id, const void* pcm, int64_t frames) {
@@ -249,6 +282,27 @@ extern "C" int ss_stream_avg(ss_ctx* c, int id, double* avg, int64_t* bin_idx, i
     return SS_OK;
 }
 
+extern "C" int ss_stream_output(ss_ctx* c, int id, int16_t* out, int64_t cap_frames, int64_t* first_frame, int64_t* n_frames) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !first_frame || !n_frames) return fail(c, SS_ERR_ARG, "ss_stream_output: bad argument");
+    if (!s->out_on) return fail(c, SS_ERR_STATE, "ss_stream_output: the stream was opened without output (ss_stream_open_output)");
+    *first_frame = s->o_first; *n_frames = s->o_n;
+    if (!out) return SS_OK;
+    if (cap_frames < s->o_n) return fail(c, SS_ERR_CAPACITY, "ss_stream_output: capacity < " + std::to_string(s->o_n));
+    if (s->o_n) memcpy(out, (const int16_t*)c->streams->h_out + s->o_off, (size_t)(s->o_n * s->ch) * 2);
+    return SS_OK;
+}
+
+extern "C" int ss_stream_get_output_info(ss_ctx* c, int id, ss_stream_output_info* out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !out) return fail(c, SS_ERR_ARG, "ss_stream_get_output_info: bad argument");
+    if (!s->out_on) return fail(c, SS_ERR_STATE, "ss_stream_get_output_info: the stream was opened without output (ss_stream_open_output)");
+    memset(out, 0, sizeof(*out));
+    out->frames_out = s->frames_out; out->frames_held = s->frames_in + s->staged_frames - s->frames_out; out->frames_erased = s->erased;
+    out->pad_s = s->er.pad_s; out->min_len_s = s->er.min_len_s;
+    return SS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // the step
 // ------------------------------------------------------------------------------------------------------
@@ -280,6 +334,139 @@ static int ensure_pinned(ss_ctx* c, unsigned char** p, size_t* cap, size_t need)
     return SS_OK;
 }
 
+// ---- the output of the streams opened with it (include/softspoken.h: which frames a step returns) ----
+// [begin, end) of one region of the erase table as silence_ranges rounds it, clamped at frame 0 (the clamp to the recording's length
+// is the limit's: no frame at or past it is looked at)
+static void erase_frames(const ss_region& padded, int sr, int64_t& lo, int64_t& hi) {
+    const double a = std::nearbyint(padded.start * (double)sr), b = std::nearbyint(padded.end * (double)sr);
+    lo = (int64_t)std::min(std::max(a, 0.0), 9.0e18); hi = (int64_t)std::min(std::max(b, 0.0), 9.0e18);
+}
+
+static void merge_ranges(std::vector<int64_t>& r) {      // sorted by begin, overlapping and touching ranges joined, as silence_ranges
+    std::vector<std::pair<int64_t, int64_t>> v;
+    for (size_t i = 0; i + 1 < r.size(); i += 2) if (r[i + 1] > r[i]) v.emplace_back(r[i], r[i + 1]);
+    std::sort(v.begin(), v.end());
+    r.clear();
+    for (const auto& p : v) {
+        if (!r.empty() && p.first <= r.back()) r.back() = std::max(r.back(), p.second);
+        else { r.push_back(p.first); r.push_back(p.second); }
+    }
+}
+
+// After the commit: the streams' walks have taken in the step's bins, frames_in counts the step's frames, the staged bytes still lie
+// in the upload.  One launch encodes every stream's decided frames, one copies the raw PCM that stays into the other half of the byte
+// arena, one copy brings all output to pinned memory.
+static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*, StreamPlan>>& act) {
+    struct OutPlan { StreamRec* s; const StreamPlan* p; int64_t limit, rng_at, n_rng, out_off, raw_off, erased; };
+    std::vector<OutPlan> ops;
+    std::vector<int64_t> rng_all;
+    auto al = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
+    int64_t total_out = 0, raw_need = 0;
+    for (auto& [sp, p] : act) {
+        StreamRec& s = *sp;
+        if (!s.out_on) continue;
+        OutPlan o{sp, &p, 0, (int64_t)rng_all.size(), 0, 0, 0, 0};
+        auto add_region = [&](std::vector<int64_t>& to, const ss_region& r) {
+            if (!erase_keeps(r, s.er.min_len_s)) return;
+            int64_t lo, hi;
+            erase_frames(erase_padded(r, s.er.pad_s), s.sr, lo, hi);
+            if (hi > lo) { to.push_back(lo); to.push_back(hi); }
+        };
+        for (const ss_region& r : s.r_out) add_region(s.er_rng, r);       // what the step returned (everything, at close)
+        merge_ranges(s.er_rng);
+        std::vector<int64_t> rng = s.er_rng;
+        if (s.finished) o.limit = s.frames_in;
+        else {
+            // P: the current region joined with the open run where RunMerger::add would join them; a current region the open run
+            // cannot reach any more is final (the walk returns it when the run closes) and is erased as a decided one
+            bool pending = false; double ps = 0, pe = 0;
+            if (s.run_open) {
+                const double rs = bin_time(s.run_first), re = bin_time(s.run_last);
+                pending = true; ps = rs; pe = re;
+                if (s.mg.have) {
+                    if (rs - s.mg.cur.end <= s.mg.brk) ps = s.mg.cur.start;
+                    else add_region(rng, ss_region{s.mg.cur.start - 3.0, s.mg.cur.end - 3.0});
+                }
+            } else if (s.mg.have) { pending = true; ps = s.mg.cur.start; pe = s.mg.cur.end; }
+            if (pending) add_region(rng, ss_region{ps - 3.0, pe - 3.0});   // its certain part (nothing when it fails the filter)
+            const int64_t lim = ss_stream_output_limit(s.sr, s.bins_done, pending, ps, pe, &s.er);
+            o.limit = std::min(std::max(lim, s.frames_out), s.frames_in);
+            merge_ranges(rng);
+        }
+        for (size_t i = 0; i + 1 < rng.size(); i += 2) {                   // the part inside [frames_out, limit)
+            const int64_t lo = std::max(rng[i], s.frames_out), hi = std::min(rng[i + 1], o.limit);
+            if (hi > lo) { rng_all.push_back(lo); rng_all.push_back(hi); o.erased += hi - lo; }
+        }
+        o.n_rng = ((int64_t)rng_all.size() - o.rng_at) / 2;
+        o.out_off = total_out; total_out = al(total_out + (o.limit - s.frames_out) * s.ch, 8);
+        o.raw_off = raw_need; raw_need = al(raw_need + (s.frames_in - o.limit) * s.frame_bytes(), 16);
+        ops.push_back(o);
+    }
+    if (ops.empty()) return SS_OK;
+    int rc;
+    const int bnxt = S.bcur ^ 1;
+    if ((rc = ensure(c, &S.barena[bnxt], &S.barena_cap[bnxt], (size_t)std::max<int64_t>(raw_need, 16)))) return rc;
+    if ((rc = ensure(c, &S.d_out, &S.out_cap, (size_t)std::max<int64_t>(total_out, 8)))) return rc;
+    if ((rc = ensure_pinned(c, &S.h_out, &S.h_out_cap, (size_t)std::max<int64_t>(total_out, 8) * 2))) return rc;
+    const size_t o_sil = 0, o_cpb = (size_t)al((int64_t)(ops.size() * sizeof(StreamSilence)), 64);
+    const size_t o_rng = o_cpb + (size_t)al((int64_t)(2 * ops.size() * sizeof(StreamCopyBytes)), 64);
+    const size_t up2 = o_rng + rng_all.size() * 8 + 64;
+    if ((rc = ensure(c, &S.d_up2, &S.up2_cap, up2))) return rc;
+    if ((rc = ensure_pinned(c, &S.h_up2, &S.h_up2_cap, up2))) return rc;
+    std::vector<StreamSilence> sil;
+    std::vector<StreamCopyBytes> cpb;
+    int64_t max_samples = 0, max_bytes = 0;
+    double in_bytes = 0, carried = 0;
+    for (const OutPlan& o : ops) {
+        StreamRec& s = *o.s;
+        const StreamPlan& p = *o.p;
+        const int64_t fb = s.frame_bytes(), n = o.limit - s.frames_out;
+        // the frames [frames_out, f0) carried from earlier steps, and the step's own [f0, frames_in) in the upload
+        const unsigned char* seg0 = p.was_host ? S.d_up + p.raw_up_off : S.barena[S.bcur] + s.raw_off;
+        const unsigned char* seg1 = S.d_up + p.up_off;
+        if (n > 0) {
+            sil.push_back(StreamSilence{seg0, seg1, (const int64_t*)(S.d_up2 + o_rng) + o.rng_at, std::min(n, p.f0 - s.frames_out), s.frames_out, n,
+                                        o.out_off, (int32_t)o.n_rng, s.format, s.ch, 0});
+            max_samples = std::max(max_samples, n * s.ch);
+            in_bytes += (double)(n * fb);
+        }
+        unsigned char* dst = S.barena[bnxt] + o.raw_off;
+        const size_t k0 = cpb.size();
+        if (o.limit < p.f0) {
+            cpb.push_back(StreamCopyBytes{seg0 + (o.limit - s.frames_out) * fb, dst, (p.f0 - o.limit) * fb});
+            dst += (p.f0 - o.limit) * fb;
+        }
+        const int64_t from = std::max(o.limit, p.f0);
+        if (from < s.frames_in) cpb.push_back(StreamCopyBytes{seg1 + (from - p.f0) * fb, dst, (s.frames_in - from) * fb});
+        for (size_t k = k0; k < cpb.size(); ++k) { max_bytes = std::max(max_bytes, cpb[k].n); carried += (double)cpb[k].n; }
+    }
+    if (!sil.empty()) memcpy(S.h_up2 + o_sil, sil.data(), sil.size() * sizeof(StreamSilence));
+    if (!cpb.empty()) memcpy(S.h_up2 + o_cpb, cpb.data(), cpb.size() * sizeof(StreamCopyBytes));
+    if (!rng_all.empty()) memcpy(S.h_up2 + o_rng, rng_all.data(), rng_all.size() * 8);
+    HIPCHK(c, hipMemcpyAsync(S.d_up2, S.h_up2, o_rng + rng_all.size() * 8, hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedLaunch sl(c, c->stream, "stream_silence_kernel", 0.0, in_bytes + 2.0 * (double)total_out);
+        HIPCHK(c, launch_stream_silence((const StreamSilence*)(S.d_up2 + o_sil), (int)sil.size(), max_samples, S.d_out, c->stream));
+    }
+    {
+        ScopedLaunch sl(c, c->stream, "stream_copy_bytes", 0.0, 2.0 * carried);
+        HIPCHK(c, launch_stream_copy_bytes((const StreamCopyBytes*)(S.d_up2 + o_cpb), (int)cpb.size(), max_bytes, c->stream));
+    }
+    if (!sil.empty()) HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, (size_t)total_out * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resolve_events(c);
+    for (const OutPlan& o : ops) {
+        StreamRec& s = *o.s;
+        s.o_first = s.frames_out; s.o_n = o.limit - s.frames_out; s.o_off = o.out_off;
+        s.frames_out = o.limit; s.erased += o.erased; s.raw_off = o.raw_off;
+        std::vector<int64_t> keep;
+        for (size_t i = 0; i + 1 < s.er_rng.size(); i += 2) if (s.er_rng[i + 1] > o.limit) { keep.push_back(s.er_rng[i]); keep.push_back(s.er_rng[i + 1]); }
+        s.er_rng.swap(keep);
+    }
+    S.bcur = bnxt;
+    return SS_OK;
+}
+
 extern "C" int ss_stream_step(ss_ctx* c) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
     if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
@@ -305,6 +492,8 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         p.up_off = up_bytes; up_bytes = al(up_bytes + (int64_t)s.staged.size(), 16);
         p.host_off = up_bytes;
         if (s.on_host) up_bytes = al(up_bytes + 4 * (int64_t)(s.h_mono.size() + s.h_sig.size() + s.h_lg.size()), 16);
+        p.raw_up_off = up_bytes;
+        if (s.on_host && s.out_on) up_bytes = al(up_bytes + (int64_t)s.h_raw.size(), 16);
         total_w += p.i_end - s.win_run;
         total_b += p.b_end - s.bins_done;
     }
@@ -332,6 +521,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         const StreamRec& s = *sp;
         unsigned char* hu = S.h_up;
         if (!s.staged.empty()) memcpy(hu + p.up_off, s.staged.data(), s.staged.size());
+        if (s.on_host && s.out_on && !s.h_raw.empty()) memcpy(hu + p.raw_up_off, s.h_raw.data(), s.h_raw.size());
         const float* hm = nullptr; const float* hs = nullptr; const float* hl = nullptr;
         if (s.on_host) {
             float* h = (float*)(hu + p.host_off);
@@ -437,7 +627,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; nothing of the step is committed: "
                                      "move the streams that had windows in it to an fp32 context (ss_stream_export / ss_stream_import)");
     // ---- commit ----
-    for (auto& kv : S.s) { kv.second.r_out.clear(); kv.second.a_out.clear(); kv.second.b_out.clear(); }
+    for (auto& kv : S.s) { kv.second.r_out.clear(); kv.second.a_out.clear(); kv.second.b_out.clear(); kv.second.o_first = kv.second.frames_out; kv.second.o_n = 0; }
     b_at = 0;
     for (auto& [sp, p] : act) {
         StreamRec& s = *sp;
@@ -453,7 +643,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         const int64_t sig_end = p.base_new + p.sig_len();
         s.frames_in = p.F; s.m_next = p.m_end; s.win_run = p.i_end; s.bins_done = p.b_end;
         s.staged.clear(); s.staged.shrink_to_fit(); s.staged_frames = 0;
-        s.on_host = false; s.h_mono.clear(); s.h_sig.clear(); s.h_lg.clear();
+        s.on_host = false; s.h_mono.clear(); s.h_sig.clear(); s.h_lg.clear(); s.h_raw.clear(); s.h_raw.shrink_to_fit();
         if (p.closing) {
             finish_regions(s);
             s.finished = true;
@@ -470,7 +660,7 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         s.lg_w0 = w0; s.lg_n = p.i_end - w0; s.lg_off = p.lg_off + (w0 - p.lw0) * 256;
     }
     S.cur = nxt;
-    return SS_OK;
+    return step_output(c, S, act);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -487,18 +677,24 @@ struct ImageHdr {
 // (a double), then the data.
 constexpr char kMagic[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '1'};
 constexpr char kMagicStep[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '2'};
+// "SSSTRM03": a stream with output -- the header, the step, ImageOut, n_er int64s (the decided ranges still ahead), the staged bytes,
+// the floats, then the held raw PCM (raw_bytes: frames [frames_out, frames_in) in the stream's encoding)
+constexpr char kMagicOut[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '3'};
+struct ImageOut { double pad_s, min_len_s; int64_t frames_out, erased, raw_bytes, n_er; };
 }  // namespace
 
 extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64_t* n_out) {
     StreamRec* s = find_stream(c, id);
     if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_export: bad argument");
-    const bool with_step = s->step != SS_STEP_DEFAULT;
-    const int64_t need = (int64_t)sizeof(ImageHdr) + (with_step ? 8 : 0) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
+    const bool with_step = s->out_on || s->step != SS_STEP_DEFAULT;
+    const int64_t raw_bytes = s->out_on ? (s->frames_in - s->frames_out) * s->frame_bytes() : 0;
+    const int64_t need = (int64_t)sizeof(ImageHdr) + (with_step ? 8 : 0) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256) +
+                         (s->out_on ? (int64_t)sizeof(ImageOut) + 8 * (int64_t)s->er_rng.size() + raw_bytes : 0);
     *n_out = need;
     if (!buf) return SS_OK;
     if (cap < need) return fail(c, SS_ERR_CAPACITY, "ss_stream_export: capacity < " + std::to_string(need));
     ImageHdr h{};
-    memcpy(h.magic, with_step ? kMagicStep : kMagic, 8);
+    memcpy(h.magic, s->out_on ? kMagicOut : with_step ? kMagicStep : kMagic, 8);
     h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->mg.have; h.run_open = s->run_open;
     h.thr = s->thr; h.brk = s->mg.brk; h.cur_start = s->mg.cur.start; h.cur_end = s->mg.cur.end;
     h.frames_in = s->frames_in; h.staged_frames = s->staged_frames; h.staged_bytes = (int64_t)s->staged.size();
@@ -507,12 +703,20 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     unsigned char* o = (unsigned char*)buf;
     memcpy(o, &h, sizeof h); o += sizeof h;
     if (with_step) { memcpy(o, &s->step, 8); o += 8; }
+    if (s->out_on) {
+        const ImageOut io{s->er.pad_s, s->er.min_len_s, s->frames_out, s->erased, raw_bytes, (int64_t)s->er_rng.size()};
+        memcpy(o, &io, sizeof io); o += sizeof io;
+        if (!s->er_rng.empty()) memcpy(o, s->er_rng.data(), s->er_rng.size() * 8);
+        o += s->er_rng.size() * 8;
+    }
     if (!s->staged.empty()) memcpy(o, s->staged.data(), s->staged.size());
     o += s->staged.size();
     float* f = (float*)o;                                 // (unaligned host memory is fine for memcpy / hipMemcpy)
+    unsigned char* raw = o + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
     if (s->on_host) {
         memcpy(f, s->h_mono.data(), s->mono_n * 4); memcpy(f + s->mono_n, s->h_sig.data(), s->sig_n * 4);
         memcpy(f + s->mono_n + s->sig_n, s->h_lg.data(), s->lg_n * 1024);
+        if (raw_bytes) memcpy(raw, s->h_raw.data(), (size_t)raw_bytes);
         return SS_OK;
     }
     hipSetDevice(c->device);
@@ -521,6 +725,7 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     if (s->mono_n) HIPCHK(c, hipMemcpy(f, a + s->mono_off, s->mono_n * 4, hipMemcpyDeviceToHost));
     if (s->sig_n) HIPCHK(c, hipMemcpy(f + s->mono_n, a + s->sig_off, s->sig_n * 4, hipMemcpyDeviceToHost));
     if (s->lg_n) HIPCHK(c, hipMemcpy(f + s->mono_n + s->sig_n, a + s->lg_off, s->lg_n * 1024, hipMemcpyDeviceToHost));
+    if (raw_bytes) HIPCHK(c, hipMemcpy(raw, c->streams->barena[c->streams->bcur] + s->raw_off, (size_t)raw_bytes, hipMemcpyDeviceToHost));
     return SS_OK;
 }
 
@@ -530,13 +735,29 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
     ImageHdr h;
     memcpy(&h, buf, sizeof h);
     static const unsigned char one[8] = {0};
-    const bool with_step = memcmp(h.magic, kMagicStep, 8) == 0;
+    const bool with_out = memcmp(h.magic, kMagicOut, 8) == 0;
+    const bool with_step = with_out || memcmp(h.magic, kMagicStep, 8) == 0;
     int64_t hdr_bytes = (int64_t)sizeof h;
     double step = SS_STEP_DEFAULT;
     if (with_step && n >= hdr_bytes + 8) { memcpy(&step, (const unsigned char*)buf + hdr_bytes, 8); hdr_bytes += 8; }
+    ImageOut io{0, 0, 0, 0, 0, 0};
+    int64_t out_bytes = 0;                                // what an image with output holds beyond the others: ImageOut, the ranges, the raw PCM
+    if (with_out) {
+        bool ok = n >= hdr_bytes + (int64_t)sizeof io;
+        if (ok) {
+            memcpy(&io, (const unsigned char*)buf + hdr_bytes, sizeof io);
+            const ss_stream_erase e{io.pad_s, io.min_len_s};
+            ok = erase_ok(&e) && io.n_er >= 0 && io.n_er <= ((int64_t)1 << 24) && io.n_er % 2 == 0 && io.frames_out >= 0 && io.frames_out <= h.frames_in &&
+                 io.erased >= 0 && io.erased <= io.frames_out && h.ch > 0 && h.ch <= 64 && io.raw_bytes >= 0 && io.raw_bytes <= n;
+        }
+        if (!ok) return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
+        hdr_bytes += (int64_t)sizeof io + 8 * io.n_er;
+        out_bytes = io.raw_bytes;
+    }
     if ((memcmp(h.magic, kMagic, 8) != 0 && !(with_step && hdr_bytes > (int64_t)sizeof h && step_ok(step))) || check_pcm_args(c, one, h.format, h.sr, h.ch, 0) != SS_OK || h.staged_bytes < 0 || h.mono_n < 0 ||
         h.sig_n < 0 || h.lg_n < 0 || h.lg_n > 64 || h.mono_n > ((int64_t)1 << 32) || h.sig_n > ((int64_t)1 << 32) ||
-        n != hdr_bytes + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) ||
+        n != hdr_bytes + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) + out_bytes ||
+        (with_out && io.raw_bytes != (h.frames_in - io.frames_out) * h.ch * (int64_t)pcm_bytes_per_sample(h.format)) ||
         h.staged_bytes != h.staged_frames * h.ch * (int64_t)pcm_bytes_per_sample(h.format))
         return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
     hipSetDevice(c->device);
@@ -554,7 +775,15 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
     s.h_mono.resize(h.mono_n); s.h_sig.resize(h.sig_n); s.h_lg.resize(h.lg_n * 256);
     memcpy(s.h_mono.data(), p, h.mono_n * 4); p += h.mono_n * 4;
     memcpy(s.h_sig.data(), p, h.sig_n * 4); p += h.sig_n * 4;
-    memcpy(s.h_lg.data(), p, h.lg_n * 1024);
+    memcpy(s.h_lg.data(), p, h.lg_n * 1024); p += h.lg_n * 1024;
+    if (with_out) {
+        s.out_on = true; s.er = ss_stream_erase{io.pad_s, io.min_len_s}; s.frames_out = io.frames_out; s.erased = io.erased;
+        const unsigned char* q = (const unsigned char*)buf + hdr_bytes - 8 * io.n_er;
+        s.er_rng.resize((size_t)io.n_er);
+        if (io.n_er) memcpy(s.er_rng.data(), q, (size_t)io.n_er * 8);
+        s.h_raw.assign(p, p + io.raw_bytes);
+        s.o_first = s.frames_out;
+    }
     s.on_host = true;
     StreamSet& S = streams_of(c);
     *id = S.next_id++;

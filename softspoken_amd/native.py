@@ -61,6 +61,15 @@ class StreamInfo(C.Structure):
                 ("final_until_s", C.c_double), ("closed", C.c_int32), ("finished", C.c_int32), ("state_bytes", C.c_int64)]
 
 
+class StreamErase(C.Structure):
+    _fields_ = [("pad_s", C.c_double), ("min_len_s", C.c_double)]
+
+
+class StreamOutputInfo(C.Structure):
+    _fields_ = [("frames_out", C.c_int64), ("frames_held", C.c_int64), ("frames_erased", C.c_int64), ("pad_s", C.c_double),
+                ("min_len_s", C.c_double)]
+
+
 class SeparationParams(C.Structure):
     _fields_ = [("fade_s", C.c_double), ("min_gain", C.c_double), ("above_fmax", C.c_int32), ("speech_channel", C.c_int32)]
 
@@ -152,6 +161,11 @@ _SIGS = {
     "ss_stream_free": (C.c_int, [_P, C.c_int]),
     "ss_stream_export": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_stream_import": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
+    "ss_erase_table": (C.c_int, [_P, C.c_int64, C.POINTER(StreamErase), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_output_limit": (C.c_int64, [C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase)]),
+    "ss_stream_open_output": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.POINTER(C.c_int)]),
+    "ss_stream_output": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ss_stream_get_output_info": (C.c_int, [_P, C.c_int, C.POINTER(StreamOutputInfo)]),
     "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
@@ -286,6 +300,40 @@ def _regions(regions):
     for i, (s, e) in enumerate(regions):
         arr[i].start, arr[i].end = float(s), float(e)
     return arr
+
+
+def _erase(erase):
+    """None, a dict(pad_s=, min_len_s=) or a (pad_s, min_len_s) pair -> struct ss_stream_erase (None: 0, 0)."""
+    if erase is None:
+        return StreamErase(0.0, 0.0)
+    if isinstance(erase, dict):
+        unknown = set(erase) - {"pad_s", "min_len_s"}
+        if unknown:
+            raise ValueError(f"erase: unknown keys {sorted(unknown)}")
+        return StreamErase(float(erase.get("pad_s", 0.0)), float(erase.get("min_len_s", 0.0)))
+    pad_s, min_len_s = erase
+    return StreamErase(float(pad_s), float(min_len_s))
+
+
+def erase_table(regions, pad_s: float = 0.0, min_len_s: float = 0.0):
+    """E(R) of include/softspoken.h (ss_erase_table, host only): regions of end - start <= min_len_s dropped, the others padded."""
+    arr = _regions(regions)
+    e = StreamErase(float(pad_s), float(min_len_s))
+    out = (Region * max(1, len(regions)))()
+    n = C.c_int64(0)
+    _check(lib().ss_erase_table(arr, len(regions), C.byref(e), out, len(regions), C.byref(n)))
+    return [(out[i].start, out[i].end) for i in range(n.value)]
+
+
+def stream_output_limit(sr: int, bins_final: int, pending=None, pad_s: float = 0.0, min_len_s: float = 0.0) -> int:
+    """The frame up to which a stream's output is decided (ss_stream_output_limit, host only), before the clamp to the frames
+    decoded.  pending: None, or the (start, end) bin times of the merged candidate that is not final yet, before the -3 s."""
+    e = StreamErase(float(pad_s), float(min_len_s))
+    ps, pe = pending if pending is not None else (0.0, 0.0)
+    v = lib().ss_stream_output_limit(int(sr), int(bins_final), int(pending is not None), float(ps), float(pe), C.byref(e))
+    if v == -2 ** 63:
+        raise ValueError("ss_stream_output_limit: bad argument")
+    return int(v)
 
 
 def separation_params(fade_s: float = 0.01, min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> SeparationParams:
@@ -688,6 +736,28 @@ class Context:
         sid = C.c_int(-1)
         self._ck(lib().ss_stream_open(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s), C.byref(sid)))
         return sid.value
+
+    def stream_open_output(self, fmt: int, sr: int, channels: int, threshold: float = 0.1, break_s: float = 0.5, erase=None) -> int:
+        """A stream that also returns its frames as final 16-bit PCM with the detected speech zeroed (stream_output after every
+        step).  erase: None, dict(pad_s=, min_len_s=) or a pair."""
+        sid = C.c_int(0)
+        e = _erase(erase)
+        self._ck(lib().ss_stream_open_output(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s), C.byref(e), C.byref(sid)))
+        return sid.value
+
+    def stream_output(self, sid: int, channels: int):
+        """The frames the last step returned -> (first_frame, int16 array [n, channels])."""
+        first, n = C.c_int64(0), C.c_int64(0)
+        self._ck(lib().ss_stream_output(self._h, int(sid), None, 0, C.byref(first), C.byref(n)))
+        out = np.zeros((n.value, int(channels)), dtype=np.int16)
+        if n.value:
+            self._ck(lib().ss_stream_output(self._h, int(sid), _ptr(out), n.value, C.byref(first), C.byref(n)))
+        return first.value, out
+
+    def stream_output_info(self, sid: int) -> dict:
+        info = StreamOutputInfo()
+        self._ck(lib().ss_stream_get_output_info(self._h, int(sid), C.byref(info)))
+        return {k: getattr(info, k) for k, _ in StreamOutputInfo._fields_}
 
     def stream_push(self, sid: int, pcm: np.ndarray, frames: int | None = None, channels: int = 1, fmt: int | None = None):
         """pcm: interleaved samples of the stream's encoding (any dtype whose bytes are that encoding); frames defaults to

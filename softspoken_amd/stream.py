@@ -8,6 +8,12 @@ run gives for the same frames.
     for stream, (regions, avg, bin_idx) in det.step().items(): ...
     s.close(); det.step()              # the last results
 
+A stream opened with erase= also returns its frames as final 16-bit PCM with the detected speech zeroed (the streaming silencer):
+
+    s = det.open(PCM_S16, 48000, 2, erase=dict(pad_s=0.05, min_len_s=0.3))
+    with StreamWavWriter("feed.wav", 48000, 2) as w:
+        ...; s.push(samples); det.step(); w.write(s.output())      # (first_frame, int16 [n, channels]): contiguous from step to step
+
 The f16x2 mode reports SS_ERR_RANGE for a step whose passes met a value without an f16 representation (a NaN or Inf sample of a
 float stream), and commits nothing of it.  The rule of the drop-in (SpecUNet_2D.range_refused): the first such step says nothing about
 the checkpoint -- the streams that had windows in it move to an fp32 context of the same weights (ss_stream_export / import) and
@@ -25,9 +31,10 @@ from . import native as _native
 class Stream:
     """One recording of a StreamDetector.  Hashable: step() returns its results keyed by it."""
 
-    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int):
+    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None):
         self._det, self._ctx, self._sid = det, ctx, sid
         self.format, self.sample_rate, self.channels = fmt, sr, channels
+        self.erase = erase                                 # None: opened without output
 
     def push(self, pcm: np.ndarray):
         """Interleaved samples in the stream's encoding (int16 for PCM_S16, float32 for PCM_F32, raw bytes for 24-bit, ...)."""
@@ -40,6 +47,14 @@ class Stream:
 
     def info(self) -> dict:
         return self._ctx.stream_info(self._sid)
+
+    def output(self):
+        """The frames the last step returned: (first_frame, int16 array [n, channels]) -- final, contiguous from step to step, the
+        detected speech zeroed.  Only on a stream opened with erase=."""
+        return self._ctx.stream_output(self._sid, self.channels)
+
+    def output_info(self) -> dict:
+        return self._ctx.stream_output_info(self._sid)
 
     @property
     def precision(self) -> str:
@@ -76,9 +91,16 @@ class StreamDetector:
             self._fp32 = self._factory("fp32")
         return self._fp32
 
-    def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5) -> Stream:
+    def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5, erase=None) -> Stream:
+        """erase: None -- detection only; dict(pad_s=, min_len_s=) (either may be left out: 0) -- the stream also returns its frames
+        as 16-bit PCM with the detected speech zeroed (Stream.output() after every step)."""
         ctx = self._fp32_ctx() if self._switched else self._main
-        s = Stream(self, ctx, ctx.stream_open(fmt, sr, channels, threshold, break_s), fmt, sr, channels)
+        if erase is None:
+            sid = ctx.stream_open(fmt, sr, channels, threshold, break_s)
+        else:
+            erase = dict(pad_s=float(erase.get("pad_s", 0.0)), min_len_s=float(erase.get("min_len_s", 0.0)))
+            sid = ctx.stream_open_output(fmt, sr, channels, threshold, break_s, erase)
+        s = Stream(self, ctx, sid, fmt, sr, channels, erase)
         self._streams.append(s)
         return s
 
@@ -130,3 +152,43 @@ class StreamDetector:
         for c in {id(c): c for c in (self._main, self._fp32) if c is not None}.values():
             if hasattr(c, "close"):
                 c.close()
+
+
+class StreamWavWriter:
+    """A 16-bit PCM WAV file that grows with a stream's output: write() appends what a step returned, close() rewrites the 44-byte
+    header (ss_wav_header_pcm16) with the final frame count.
+
+        with StreamWavWriter(path, 16000, 1) as w:
+            ...; det.step(); w.write(s.output())
+    """
+
+    def __init__(self, path, sr: int, channels: int):
+        self.sample_rate, self.channels, self.frames = int(sr), int(channels), 0
+        self._f = open(path, "wb")
+        self._f.write(_native.wav_header_pcm16(self.sample_rate, self.channels, 0))
+
+    def write(self, output):
+        """output: Stream.output()'s pair, or an int16 array [n, channels]; a pair must continue where the file ends."""
+        if isinstance(output, tuple):
+            first, a = output
+            if first != self.frames:
+                raise ValueError(f"output starts at frame {first}, the file holds {self.frames}")
+        else:
+            a = output
+        a = np.ascontiguousarray(a, dtype="<i2").reshape(-1, self.channels)
+        self._f.write(a.tobytes())
+        self.frames += len(a)
+
+    def close(self):
+        if self._f is None:
+            return
+        self._f.seek(0)
+        self._f.write(_native.wav_header_pcm16(self.sample_rate, self.channels, self.frames))
+        self._f.close()
+        self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
