@@ -164,7 +164,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     };
 
     // ---- this thread's patch pieces: geometry fixed for the kernel's lifetime ----
-    uint32_t pix_full[AIT], pix_half[AIT], lds_off[AIT], flags = 0;
+    constexpr bool kNoUp = FIRST || FLAT || RANK1;      // forms whose input has no upsampled half (C1 == 0, choose_v4): no pix_half to hold
+    uint32_t pix_full[AIT], pix_half[kNoUp ? 1 : AIT], lds_off[AIT], flags = 0;
     const uint32_t part16 = (tid & 3) * 16;              // NTHR % 4 == 0: a thread always moves the same 16-byte part of a pixel
     {
         const int Wh = W >> 1;
@@ -175,7 +176,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             const int pyy = pix / kPatch, pxx = pix - pyy * kPatch;
             lds_off[it] = pyy * kRowPitch + pxx * kPixPitch + part16;
             pix_full[it] = pyy * W + pxx;                                   // from the patch origin (y0-1, x0-1)
-            pix_half[it] = ((pyy + 1) >> 1) * Wh + ((pxx + 1) >> 1);       // nearest-upsampled source, from (y0/2-1, x0/2-1)
+            if constexpr (!kNoUp) pix_half[it] = ((pyy + 1) >> 1) * Wh + ((pxx + 1) >> 1);       // nearest-upsampled source, from (y0/2-1, x0/2-1)
             const uint32_t f = (pyy == 0 ? 1u : 0u) | (pyy == PR - 1 ? 2u : 0u) | (pxx == 0 ? 4u : 0u) | (pxx == kPatch - 1 ? 8u : 0u) |
                                (p >= NPA ? 16u : 0u);
             flags |= f << (8 * it);
@@ -201,7 +202,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         const int ch = (SPLIT ? ci >> 1 : ci) * KC;
         const int64_t plane = (SPLIT && !(ci & 1)) ? a.lo_delta : 0;      // part 0 multiplies the low halves
         const char* base; uint32_t cs2, toff; bool up;
-        if (ch < a.C0) {
+        if (kNoUp || ch < a.C0) {
             base = (const char*)a.src0 - kHdr + plane; cs2 = 2u * a.C0; up = false;
             toff = kHdr + ((((uint32_t)d.n * H + d.y0 - 1) * W + d.x0 - 1) * a.C0 + ch) * 2u;            // mod 2^32; valid pieces land >= kHdr
         } else {
@@ -213,7 +214,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         const uint32_t tp = toff + part16;
 #pragma unroll
         for (int it = 0; it < AIT; ++it) {
-            const uint32_t pix = up ? pix_half[it] : pix_full[it];
+            const uint32_t pix = (!kNoUp && up) ? pix_half[kNoUp ? 0 : it] : pix_full[it];
             uint32_t off = __umul24(pix, cs2) + tp;
             if (flags & (tm << (8 * it))) off = 0;        // the zero header
             ra[it] = *(const u32x4*)(base + off);
@@ -633,24 +634,38 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                     }
                 }
         }
-        auto proj_products = [&](auto k0c, auto k1c) {     // + conv1x1(x): steps [K0, K1) of this chunk, their fragments in slots 0 ..
+        // + conv1x1(x): steps [K0, K1) of this chunk, their pixel fragments in slots 0 ..  The weight fragments of (step, tile) j + 1
+        // are read in front of the three products of j (mfma_util.h frag_fence); those of j = 0 by proj_first -- in front of the
+        // products, or (`early`) by the caller, in front of the last step of the loop before
+        u32x4 pwh[2], pwl[2];
+        auto proj_load = [&](auto k0c, int j) {
+            constexpr int K0 = decltype(k0c)::value;
+            const int k = K0 + j / NT, nt = j % NT;
+            const int sidx = (ci >> 1) * RP + k < proj_steps ? (ci >> 1) * RP + k : 0;   // (a step past the end multiplies zeros)
+            const int wt = (sidx * proj_tiles + (int)(co0 >> 5) + nt) * 1024 + lane * 16;
+            pwh[j & 1] = *(const u32x4*)(sProj + wt); pwl[j & 1] = *(const u32x4*)(sProj + proj_bank + wt);
+        };
+        auto proj_products = [&](auto k0c, auto k1c, auto early_c) {
             constexpr int K0 = decltype(k0c)::value, K1 = decltype(k1c)::value;
+            constexpr int NJ = (K1 - K0) * NT;
+            if constexpr (NJ > 0 && !decltype(early_c)::value) proj_load(k0c, 0);
+            frag_fence();
 #pragma unroll
-            for (int k = K0; k < K1; ++k) {
-                const int sidx = (ci >> 1) * RP + k < proj_steps ? (ci >> 1) * RP + k : 0;   // (a step past the end multiplies zeros)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int wt = (sidx * proj_tiles + (int)(co0 >> 5) + nt) * 1024 + lane * 16;
-                    const u32x4 wh = *(const u32x4*)(sProj + wt), wl = *(const u32x4*)(sProj + proj_bank + wt);
-                    acc[nt] = mfma16<true>(wh, pxl[k - K0], acc[nt]);
-                    acc[nt] = mfma16<true>(wl, pxh[k - K0], acc[nt]);
-                    acc[nt] = mfma16<true>(wh, pxh[k - K0], acc[nt]);
-                }
+            for (int j = 0; j < NJ; ++j) {
+                const int k = K0 + j / NT, nt = j % NT;
+                if (j + 1 < NJ) proj_load(k0c, j + 1);
+                frag_fence();
+                acc[nt] = mfma16<true>(pwh[j & 1], pxl[k - K0], acc[nt]);
+                acc[nt] = mfma16<true>(pwl[j & 1], pxh[k - K0], acc[nt]);
+                acc[nt] = mfma16<true>(pwh[j & 1], pxh[k - K0], acc[nt]);
+                frag_fence();
             }
         };
+        // the second half of a stage's projection steps follows the merged loop: its first weight fragments are read in that loop's last step
+        constexpr bool kProjEarly = SPLIT && RP > RPH && PART == 1 && NSTEP == 36 && NT == 1 && !(NW == 4 && NH == 1 && !BRES);
         using KZ_ = std::integral_constant<int, 0>; using KH_ = std::integral_constant<int, RPH>; using KR_ = std::integral_constant<int, RP>;
         if constexpr (SPLIT && RP > 0 && PART == 1) {     // the steps requested in part 0's off-phase; then the request for the others
-            proj_products(KZ_{}, KH_{});
+            proj_products(KZ_{}, KH_{}, std::false_type{});
             __builtin_amdgcn_sched_barrier(0);            // (their operands are dead before anything else is requested)
             if constexpr (RP > RPH) issue_proj(cur, ci >> 1, KH_{}, KR_{});
         }
@@ -659,7 +674,16 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             // (resident banks of several channel groups -- DUO only -- lie as in memory: [group][chunk][bank])
             const char* bbase = sB + boff0 + (BRES ? ((DUO && !GRES ? cur.g * nch : 0) + (SPLIT ? (ci >> 1) * 2 : ci)) * TAPS * kTapBytes
                                                    : RING ? ((stage_no >> 1) & 1) * lds_b_bytes : 0);
-            constexpr int PD = (NT == 1) ? 4 : 2;        // fragment prefetch depth (NT = 2 at depth 4 spills under its 128-register cap)
+            // fragment slots.  f16x2 (kFence): the reads of step st + PD - 1 (PM - 1 in the merged loop) are issued in front of the
+            // products of step st and held there by fences (mfma_util.h frag_fence): two or three products ahead in the binary
+            // (tools/frag_distance.py).  Without the fences the scheduler sinks every read to just in front of its product.  One
+            // slot more measured no faster where it fits and spills in the forms at the 128-register cap.  bf16 and the single
+            // 4-wave tile over streamed banks (no launch of the network takes it; fenced it spills at any depth) keep the
+            // scheduler's order: there PD is what the source offers, not what the binary does.
+            // (NT = 2 at depth 4 spills under its 128-register cap)
+            constexpr bool kFence = SPLIT && !(NW == 4 && NH == 1 && !BRES);
+            auto fence = [&]() { if constexpr (kFence) frag_fence(); };
+            constexpr int PD = (NT == 1) ? (kFence ? 3 : 4) : 2;
             u32x4 af[PD], bfr[PD][NT];
             u32x4 rfr[RES ? 2 : 1][RES ? NT : 1];
             if (a.dbg & 32) __builtin_amdgcn_s_setprio(kMfmaPrio);
@@ -667,8 +691,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             // product instead of 2: the LDS array is as busy as the matrix pipe in these stages)
             constexpr bool kMerged = SPLIT && NSTEP == 36 && NT == 1;
             if constexpr (kMerged) {
-                constexpr int PM = 3;
-                u32x4 pf[PM], wh_[PM], wl_[PM], rh_[RES ? 2 : 1], rl_[RES ? 2 : 1];
+                constexpr int PM = kFence ? 2 : 3;
+                u32x4 pf[PM], wh_[PM], wl_[PM], rh_, rl_;   // (rh_ / rl_: the projection's fragments, one slot: sub-step 0 is read two steps ahead, 1 behind 0's products)
                 const char* bb0 = bbase; const char* bb1 = bbase + TAPS * kTapBytes;
                 auto load3 = [&](int st, int slot) {
                     const int tap = st >> 1, sub = st & 1, dy = tap / 3, dx = tap % 3;
@@ -678,27 +702,29 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                 };
 #pragma unroll
                 for (int st = 0; st < PM - 1; ++st) load3(st, st);
+                fence();
 #pragma unroll
                 for (int st = 0; st < 18; ++st) {
                     if (st + PM - 1 < 18) load3(st + PM - 1, (st + PM - 1) % PM);
+                    if constexpr (kProjEarly) { if (st == 17) proj_load(KH_{}, 0); }      // (the last step has no reads of its own)
                     if constexpr (RES) {
-                        if (st == 6) {
-#pragma unroll
-                            for (int sub = 0; sub < 2; ++sub) {
-                                rh_[sub] = *(const u32x4*)(bb0 + 9 * kTapBytes + sub * 1024);
-                                rl_[sub] = *(const u32x4*)(bb1 + 9 * kTapBytes + sub * 1024);
-                            }
+                        if (st == 6 || st == 9) {
+                            rh_ = *(const u32x4*)(bb0 + 9 * kTapBytes + (st == 9) * 1024);
+                            rl_ = *(const u32x4*)(bb1 + 9 * kTapBytes + (st == 9) * 1024);
                         }
                     }
+                    fence();
                     const u32x4 pixv = pf[st % PM];
                     acc[0] = mfma16<true>(wh_[st % PM], pixv, acc[0]);
                     acc[0] = mfma16<true>(wl_[st % PM], pixv, acc[0]);
                     if constexpr (RES) {
                         if (st == 8 || st == 9) {
-                            racc[0] = mfma16<true>(rh_[st & 1], pixv, racc[0]);
-                            racc[0] = mfma16<true>(rl_[st & 1], pixv, racc[0]);
+                            fence();                      // (behind the step's own products, as written: sub-step 1's fragments are two products old)
+                            racc[0] = mfma16<true>(rh_, pixv, racc[0]);
+                            racc[0] = mfma16<true>(rl_, pixv, racc[0]);
                         }
                     }
+                    fence();
                 }
             } else
 #pragma unroll
@@ -713,6 +739,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                 if (bank) __builtin_amdgcn_sched_barrier(0);        // (one round's fragment reads stay out of the other's: no registers for both)
 #pragma unroll
                 for (int st = 0; st < PD - 1; ++st) load_frags(st, af[st], bfr[st]);
+                fence();
 #pragma unroll
                 for (int st = 0; st < 18; ++st) {
                     if (st + PD - 1 < 18) load_frags(st + PD - 1, af[(st + PD - 1) % PD], bfr[(st + PD - 1) % PD]);
@@ -724,6 +751,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                                 for (int nt = 0; nt < NT; ++nt) rfr[sub][nt] = *(const u32x4*)(bb + 9 * kTapBytes + (sub * NT + nt) * 1024);
                         }
                     }
+                    fence();
                     const u32x4 pixv = af[st % PD];
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {     // weights are the A operand (rows = channels), pixels the B operand
@@ -732,11 +760,12 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                             if (st == 8 || st == 9) racc[nt] = mfma16<SPLIT>(rfr[st & 1][nt], pixv, racc[nt]);
                         }
                     }
+                    fence();
                 }
             }
         }
 
-        if constexpr (SPLIT && RP > RPH && PART == 1) proj_products(KH_{}, KR_{});      // (requested at the head of this stage)
+        if constexpr (SPLIT && RP > RPH && PART == 1) proj_products(KH_{}, KR_{}, std::bool_constant<kProjEarly>{});      // (pixels: requested at the head of this stage)
         if constexpr (RP > 0 && !SPLIT) {                 // + conv1x1(x): pixel fragments straight from memory, weights from LDS
 #pragma unroll
             for (int k = 0; k < RP; ++k) {

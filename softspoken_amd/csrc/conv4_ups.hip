@@ -213,7 +213,9 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             constexpr int PART = decltype(part_c)::value;
             const char* bb0 = sB + boff0 + (ci >> 1) * 2 * kBankR;
             const char* bb1 = bb0 + kBankR;
-            constexpr int PM = 3;
+            // slots: a step's reads lie PM - 1 steps -- two or three products -- ahead of its products, held there by the fences
+            // (mfma_util.h frag_fence).  One slot more (three to five products ahead) measured no faster and costs 7 registers
+            constexpr int PM = PART == 1 ? 2 : 3;
             u32x4 pf[PM], wh_[PM], wl_[PM];
             auto load3 = [&](int st, int slot) {
                 const int tap = st >> 1, sub = st & 1;
@@ -223,12 +225,15 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             };
 #pragma unroll
             for (int st = 0; st < PM - 1; ++st) load3(st, st);
+            frag_fence();
 #pragma unroll
             for (int st = 0; st < 18; ++st) {
                 if (st + PM - 1 < 18) load3(st + PM - 1, (st + PM - 1) % PM);
+                frag_fence();
                 const u32x4 pixv = pf[st % PM];
                 acc = mfma16<true>(wh_[st % PM], pixv, acc);
                 if constexpr (PART == 1) acc = mfma16<true>(wl_[st % PM], pixv, acc);
+                frag_fence();
             }
         };
         using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
@@ -248,12 +253,15 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                 wl_[slot] = *(const u32x4*)(bb1 + tap * 2048 + sub * 1024);
             };
             load4(0, 0);
+            frag_fence();
 #pragma unroll
             for (int st = 0; st < 8; ++st) {
                 if (st + 1 < 8) load4(st + 1, (st + 1) % PM);
+                frag_fence();
                 acc = mfma16<true>(wh_[st % PM], pl[st % PM], acc);
                 acc = mfma16<true>(wl_[st % PM], ph[st % PM], acc);
                 acc = mfma16<true>(wh_[st % PM], ph[st % PM], acc);
+                frag_fence();
             }
         }
         if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);
@@ -336,6 +344,9 @@ constexpr int kGL = (kEntU / 32 + NTHR - 1) / NTHR;       // LDS-DMA instruction
 __global__ __launch_bounds__(NTHR * NH) __attribute__((amdgpu_waves_per_eu(4)))
 void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // The multiply loops below are written as software prefetch (slots pf / wf / ph / pl), but WITHOUT the fences of the other f16x2
+    // kernels (mfma_util.h frag_fence): the scheduler sinks every ds_read to just in front of its v_mfma (tools/frag_distance.py:
+    // distance 0 for all 90 products).  Fenced, two products ahead, this kernel measured 1.3 - 2 % slower.
     // timing-only ablations (development build, SOFTSPOKEN_DBG bits 16..20: results are wrong): no matrix products / no operand reads from
     // the LDS / no patch loads from memory / no ring DMA / no epilogue stores -- what a beat is made of
 #ifdef SS_DEVBUILD
@@ -506,11 +517,14 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
             const int base = half == 1 ? 0 : h0, cnt = half == 1 ? h0 : total - h0;
             const char* src = (const char*)a.wpk + (size_t)rq_g * group_bytes + entry_off(rq) + base * 16;
             char* dst = sR + rq_slot * kSlot + base * 16 + wave * 1024;        // the wave's 1 KB of an instruction: base + 16 x lane by the hardware
+            // (the thread's byte offset is made opaque here: as a loop invariant the compiler held the kGL 64-bit offsets and the kGL
+            // piece indices in registers for the kernel's lifetime -- 14 of the 128 -- and spilled the patch geometry beside them)
+            uint32_t t16 = (uint32_t)tid * 16u;
+            asm volatile("" : "+v"(t16));
 #pragma unroll
             for (int it = 0; it < kGL; ++it) {
-                const int idx = tid + NTHR * it;
-                if (idx < cnt)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)idx * 16),
+                if (tid < cnt - NTHR * it)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(t16 + (uint32_t)(it * NTHR * 16))),
                                                      (__attribute__((address_space(3))) void*)(uintptr_t)(dst + it * NTHR * 16), 16, 0, 0);
             }
         }
@@ -630,17 +644,15 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
                 pf[slot] = *(const u32x4*)(sA + base_r + tap_r[tap] + sub * 32);
                 wf[slot] = *(const u32x4*)(bb + tap * 2048 + sub * 1024);
             };
-            u32x4 wr0, wr1;
+            u32x4 wr;                                     // the projection's fragments, one slot (in the source: two products ahead, then behind sub-step 0's product)
 #pragma unroll
             for (int st = 0; st < PM - 1; ++st) load2(st, st);
 #pragma unroll
             for (int st = 0; st < 18; ++st) {
                 if (st + PM - 1 < 18) load2(st + PM - 1, (st + PM - 1) % PM);
-                if (st == 6) wr0 = *(const u32x4*)(bb + 9 * 2048);             // the projection's fragments, two steps ahead of their products
-                if (st == 7) wr1 = *(const u32x4*)(bb + 9 * 2048 + 1024);
+                if ((st == 7 || st == 9) && !SS_ABL(17)) wr = *(const u32x4*)(bb + 9 * 2048 + (st == 9) * 1024);
                 acc = mm(wf[st % PM], pf[st % PM], acc);
-                if (st == 8) racc = mm(wr0, pf[st % PM], racc);
-                if (st == 9) racc = mm(wr1, pf[st % PM], racc);
+                if (st == 8 || st == 9) racc = mm(wr, pf[st % PM], racc);
             }
         } else if constexpr (KIND == 3) {
             // U1: the class's four pre-summed taps over both planes of the low-resolution patch against the high halves: wh xl + wh xh
@@ -654,19 +666,26 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
                 pl[slot] = *(const u32x4*)(sA + kLowPlane + base_u + tap_u[tap] + sub * 32);
                 wf[slot] = *(const u32x4*)(bb + tap * 2048 + sub * 1024);
             };
+            // the projection's two sub-steps ride behind the loop: the first is read in front of the loop's last products, the second
+            // in front of the first's, into the slot the loop has left (in the source: the scheduler's order in the binary, see the kernel's head)
+            auto load_r = [&](int sub, int slot) {
+                if (SS_ABL(17)) return;
+                wf[slot] = *(const u32x4*)(ent + boff0 + 16 * 2048 + sub * 1024);
+                ph[slot] = *(const u32x4*)(sA + base_u + kCentreU + sub * 32);
+                pl[slot] = *(const u32x4*)(sA + kLowPlane + base_u + kCentreU + sub * 32);
+            };
             load3(0, 0);
 #pragma unroll
             for (int st = 0; st < 8; ++st) {
-                if (st + 1 < 8) load3(st + 1, (st + 1) % PM);
+                if (st + 1 < 8) load3(st + 1, (st + 1) % PM); else load_r(0, (st + 1) % PM);
                 acc = mm(wf[st % PM], pl[st % PM], acc);
                 acc = mm(wf[st % PM], ph[st % PM], acc);
             }
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
-                const u32x4 w = *(const u32x4*)(ent + boff0 + 16 * 2048 + sub * 1024);
-                const u32x4 xh = *(const u32x4*)(sA + base_u + kCentreU + sub * 32), xl = *(const u32x4*)(sA + kLowPlane + base_u + kCentreU + sub * 32);
-                racc = mm(w, xl, racc);
-                racc = mm(w, xh, racc);
+                if (sub == 0) load_r(1, 1);
+                racc = mm(wf[sub], pl[sub], racc);
+                racc = mm(wf[sub], ph[sub], racc);
             }
         } else {
             // U2: the high plane against the low halves: wl xh
@@ -679,18 +698,20 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
                 ph[slot] = *(const u32x4*)(sA + base_u + tap_u[tap] + sub * 32);
                 wf[slot] = *(const u32x4*)(bb + tap * 2048 + sub * 1024);
             };
+            // the projection's two sub-steps are steps 8 and 9 of the same rotation (PM - 1 steps ahead in the source, like the taps')
+            auto load_any = [&](int st, int slot) {
+                if (st < 8) { load2(st, slot); return; }
+                if (SS_ABL(17)) return;
+                wf[slot] = *(const u32x4*)(ent + boff0 + 16 * 2048 + (st - 8) * 1024);
+                ph[slot] = *(const u32x4*)(sA + base_u + kCentreU + (st - 8) * 32);
+            };
 #pragma unroll
-            for (int st = 0; st < PM - 1; ++st) load2(st, st);
+            for (int st = 0; st < PM - 1; ++st) load_any(st, st);
 #pragma unroll
-            for (int st = 0; st < 8; ++st) {
-                if (st + PM - 1 < 8) load2(st + PM - 1, (st + PM - 1) % PM);
-                acc = mm(wf[st % PM], ph[st % PM], acc);
-            }
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                const u32x4 w = *(const u32x4*)(ent + boff0 + 16 * 2048 + sub * 1024);
-                const u32x4 xh = *(const u32x4*)(sA + base_u + kCentreU + sub * 32);
-                racc = mm(w, xh, racc);
+            for (int st = 0; st < 10; ++st) {
+                if (st + PM - 1 < 10) load_any(st + PM - 1, (st + PM - 1) % PM);
+                if (st < 8) acc = mm(wf[st % PM], ph[st % PM], acc);
+                else racc = mm(wf[st % PM], ph[st % PM], racc);
             }
         }
         if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);

@@ -64,6 +64,12 @@ __device__ __forceinline__ f32x16 mfma16(const u32x4& a, const u32x4& b, const f
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
+// The f16x2 multiply loops are written as software prefetch: the operand fragments of step st + depth - 1 are read from the LDS in front
+// of the products of step st.  Left to itself the scheduler sinks every ds_read to just in front of the v_mfma that consumes it and waits
+// there for the whole LDS round trip (~130 cycles loaded, a product is 32): the depth exists in the source only.  A fence behind a step's
+// reads and one behind its products keep the order as written; the compiler still counts lgkmcnt itself (tools/frag_distance.py
+// reports, per product, how many products lie between its operands' read and itself in the binary).
+__device__ __forceinline__ void frag_fence() { __builtin_amdgcn_sched_barrier(0); }
 // lanes 32..63 of x <-> lanes 0..31 of y
 __device__ __forceinline__ void half_swap(uint32_t& x, uint32_t& y) {
     const u32x2 r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
