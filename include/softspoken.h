@@ -523,7 +523,8 @@ int ss_debug_fail_workspace_alloc(ss_ctx* ctx, int nth);
 int ss_debug_set_separation_budget(ss_ctx* ctx, int64_t frames);
 /* Activation tensors of the context's last network pass, for per-launch tests.  name: a tensor of the activation workspace ("h1" ... "s9"),
  * "feat" (the pass's features) or "flat_part" (conv_flatten's row-group partial sums, fp32 [n][groups][4][256] read as H = groups,
- * W = 4, C = 256; exponents: the common power of two they carry).  Copies windows [first_window, first_window + n_windows) of one plane as stored, [n][H][W][C]: fp32,
+ * W = 4, C = 256; exponents: the common power of two they carry).  Copies windows [first_window, first_window + n_windows) of one plane as [n][H][W][C], whatever the stored
+ * byte order (the f16x2 tensors wider than 32 channels are stored [n][C / 32][H][W][32] and gathered on readback): fp32,
  * bf16, or under SS_FLAG_F16X2 the high (plane 0) or low (plane 1) f16 halves.  shape (if not NULL) receives H, W, C and the bytes of
  * one element; exponents (if not NULL, C entries) the power-of-two channel exponents of the tensor (the stored value of channel c is
  * 2^e[c] x its value; all zero outside SS_FLAG_F16X2).  out == NULL: shape and exponents only, for any tensor of the model (no pass

@@ -34,6 +34,8 @@ static constexpr int kMfmaPrio = 2;
 __device__ __forceinline__ uint32_t relu_pk(uint32_t v) {            // bf16 pair: negative <=> int16 negative
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), s16x2{0, 0}));
 }
+// a 16-channel K step of a projection operand: its chunk, and its half of the chunk (kernels.h: ActStride)
+__device__ __forceinline__ uint32_t step_off(ActStride s, int ch) { return (uint32_t)(ch >> 5) * s.chunk + (uint32_t)(ch & 16) * 2u; }
 __device__ __forceinline__ uint32_t max_pk(uint32_t a, uint32_t b) { // valid for non-negative bf16 (after ReLU)
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
 }
@@ -126,6 +128,11 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     float* sFlat = (float*)sBias + 32;                               // FLAT: [NW][2 rows][4][16] per-wave, per-row flatten sums of the current tile
 
     const int H = a.H, W = a.W, Cout = a.Cout;
+    // byte order of the tensors (kernels.h ActStride).  f16x2: the engine's choice per tensor; bf16 tensors are [window][H][W][C], which
+    // the compiler is told here: a chunk step is the constant 64 and a pixel step 2 C, the one scalar it was
+    const ActStride s_src0 = SPLIT ? a.s_src0 : act_stride(H, W, a.C0, false), s_src1 = SPLIT ? a.s_src1 : act_stride(H >> 1, W >> 1, a.C1, false);
+    const ActStride s_out = SPLIT ? a.s_out : act_stride(H, W, Cout, false), s_pool = SPLIT ? a.s_pool : act_stride(H >> 1, W >> 1, Cout, false);
+    const ActStride s_xp0 = SPLIT ? a.s_xp0 : act_stride(H, W, a.C0x, false), s_xp1 = SPLIT ? a.s_xp1 : act_stride(H >> 1, W >> 1, a.C1x, false);
     const int ngroups = Cout / (32 * NT);
     const int nch_r = (a.C0 + a.C1) / KC;                          // K chunks of 32 input channels
     const int nch = SPLIT ? 2 * nch_r : nch_r;                        // stages per tile
@@ -203,11 +210,11 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         const int64_t plane = (SPLIT && !(ci & 1)) ? a.lo_delta : 0;      // part 0 multiplies the low halves
         const char* base; uint32_t cs2, toff; bool up;
         if (kNoUp || ch < a.C0) {
-            base = (const char*)a.src0 - kHdr + plane; cs2 = 2u * a.C0; up = false;
-            toff = kHdr + ((((uint32_t)d.n * H + d.y0 - 1) * W + d.x0 - 1) * a.C0 + ch) * 2u;            // mod 2^32; valid pieces land >= kHdr
+            base = (const char*)a.src0 - kHdr + plane; cs2 = s_src0.pix; up = false;
+            toff = kHdr + act_offset(s_src0, H, W, a.C0, d.n, d.y0 - 1, d.x0 - 1, ch);                 // mod 2^32; valid pieces land >= kHdr
         } else {
-            base = (const char*)a.src1 - kHdr + plane; cs2 = 2u * a.C1; up = true;
-            toff = kHdr + ((((uint32_t)d.n * (H >> 1) + (d.y0 >> 1) - 1) * (W >> 1) + (d.x0 >> 1) - 1) * a.C1 + (ch - a.C0)) * 2u;
+            base = (const char*)a.src1 - kHdr + plane; cs2 = s_src1.pix; up = true;
+            toff = kHdr + act_offset(s_src1, H >> 1, W >> 1, a.C1, d.n, (d.y0 >> 1) - 1, (d.x0 >> 1) - 1, ch - a.C0);
         }
         // edge mask of the tile against the piece flags: a piece is outside the image when its halo side is an image border
         uint32_t tm = (d.y0 == 0 ? 1u : 0u) | (d.y0 + TH == H ? 2u : 0u) | (d.x0 == 0 ? 4u : 0u) | (d.x0 + 16 == W ? 8u : 0u) | 16u;
@@ -299,20 +306,20 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     auto issue_proj = [&](const Tile& d, int chunk, auto k0c, auto k1c) {
         constexpr int K0 = decltype(k0c)::value, K1 = decltype(k1c)::value;
         if constexpr (SPLIT && RP > 0 && K1 > K0) {
-            const uint32_t t_full = kHdr + ((((uint32_t)d.n * H + d.y0 + 2 * wave) * W + d.x0) * a.C0x) * 2u;
-            const uint32_t t_half = kHdr + ((((uint32_t)d.n * (H >> 1) + (d.y0 >> 1) + wave) * (W >> 1) + (d.x0 >> 1)) * a.C1x) * 2u;
+            const uint32_t t_full = kHdr + act_offset(s_xp0, H, W, a.C0x, d.n, d.y0 + 2 * wave, d.x0, 0);
+            const uint32_t t_half = kHdr + act_offset(s_xp1, H >> 1, W >> 1, a.C1x, d.n, (d.y0 >> 1) + wave, d.x0 >> 1, 0);
             // (an opaque zero per call: left to itself the compiler forms every lane address of this block once, ahead of the stage loop,
             // and pays for the 64-bit loop invariants with spills)
             uint32_t zl = 0;
             asm volatile("" : "+v"(zl));
-            const uint32_t xf_o = (uint32_t)((py * W + px) * a.C0x + hh * 8) * 2u + zl, xh_o = (uint32_t)((px >> 1) * a.C1x + hh * 8) * 2u + zl;
+            const uint32_t xf_o = (uint32_t)(py * W + px) * s_xp0.pix + hh * 16u + zl, xh_o = (uint32_t)(px >> 1) * s_xp1.pix + hh * 16u + zl;
 #pragma unroll
             for (int k = K0; k < K1; ++k) {
                 const int sidx = chunk * RP + k, ch = sidx * 16;                   // block-uniform
                 const char* base; uint32_t off;
                 if (sidx >= proj_steps) { base = (const char*)a.xp0 - kHdr; off = 0; }     // (a step past the end multiplies the zero header)
-                else if (ch < a.C0x) { base = (const char*)a.xp0 - kHdr; off = t_full + xf_o + ch * 2u; }
-                else { base = (const char*)a.xp1 - kHdr; off = t_half + xh_o + (ch - a.C0x) * 2u; }
+                else if (ch < a.C0x) { base = (const char*)a.xp0 - kHdr; off = t_full + xf_o + step_off(s_xp0, ch); }
+                else { base = (const char*)a.xp1 - kHdr; off = t_half + xh_o + step_off(s_xp1, ch - a.C0x); }
                 pxh[k - K0] = *(const u32x4*)(base + off);
                 pxl[k - K0] = *(const u32x4*)(base + a.lo_delta + off);
             }
@@ -489,18 +496,18 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     const int aoff0 = (2 * wave + py) * kRowPitch + px * kPixPitch + hh * 16;
     const int boff0 = lane * 16;
     // where this lane's 16-byte runs of its pixel go, relative to the wave's M-tile origin (row y0 + 2 wave, column x0)
-    const uint32_t st_off = (uint32_t)((py * W + px) * Cout + hh * 8) * 2u;
+    const uint32_t st_off = (uint32_t)(py * W + px) * s_out.pix + hh * 16u;
     // f16x2 r tensors: fp32 accumulator fragments, one 2 x 16-pixel x 32-channel M-tile after the other
     // ([n][H/2][W/16][Cout/32]); an M-tile's 4 KB sit half in each plane's slot of the tensor: [lane][registers 0..7] in the
     // plane of high halves, [lane][registers 8..15] in the other (each slot is 2 KB per M-tile, as for an activation tensor)
     auto r_mtile = [&](const Tile& t, uint32_t co) -> uint32_t {     // byte offset of this wave's M-tile (channel tile co / 32) in a slot
         return (((((uint32_t)t.n * (H >> 1) + (t.y0 >> 1) + wave) * (W >> 4) + (t.x0 >> 4)) * (uint32_t)(Cout >> 5)) + (co >> 5)) * 2048u;
     };
-    const uint32_t pl_off = (uint32_t)((m >> 2) * Cout + hh * 8) * 2u;     // pooled pixel (m >> 2) of the M-tile's 1x8 pooled row
+    const uint32_t pl_off = (uint32_t)(m >> 2) * s_pool.pix + hh * 16u;  // pooled pixel (m >> 2) of the M-tile's 1x8 pooled row
     // RP: this lane's pixel in the block input x (full-resolution source / nearest-upsampled half-resolution source), as byte
     // offsets from the wave's M-tile origin; + 32 s bytes for K step s, + 16 hh for the lane's half of the 16 channels
-    const uint32_t xf_off = (uint32_t)((py * W + px) * a.C0x + hh * 8) * 2u;
-    const uint32_t xh_off = (uint32_t)((px >> 1) * a.C1x + hh * 8) * 2u;
+    const uint32_t xf_off = (uint32_t)(py * W + px) * s_xp0.pix + hh * 16u;
+    const uint32_t xh_off = (uint32_t)(px >> 1) * s_xp1.pix + hh * 16u;
 
     // One stage.  Order: MFMAs of stage k | barrier | commit of stage k+1 (its loads were issued a whole stage or two ago),
     // loads of stage k+2 (PF2: k+3) into the registers just freed | barrier | epilogue of stage k.  The epilogue's stores are
@@ -550,7 +557,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         const bool last = ci == nch - 1;
         ++jit_n; jitter(0);
         const uint32_t co0 = cur.g * 32 * NT;
-        const uint32_t o_tile = ((((uint32_t)cur.n * H + cur.y0 + 2 * wave) * W + cur.x0) * Cout + co0) * 2u;   // wave-uniform
+        const uint32_t o_tile = act_offset(s_out, H, W, Cout, cur.n, cur.y0 + 2 * wave, cur.x0, co0);   // wave-uniform
+        const uint32_t o_nt = s_out.chunk;                 // from a 32-channel output tile to the next
 
         // B launches: the residual runs of this lane's pixel, requested now and used after the MFMAs
         u32x4 rlo[RADD ? NT : 1], rhi[RADD ? NT : 1];
@@ -577,7 +585,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             } else {
                 const char* rp = (const char*)a.res_in - kHdr + (last ? kHdr + o_tile + st_off : 0u);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) { rlo[nt] = *(const u32x4*)(rp + nt * 64); rhi[nt] = *(const u32x4*)(rp + nt * 64 + 32); }
+                for (int nt = 0; nt < NT; ++nt) { rlo[nt] = *(const u32x4*)(rp + nt * o_nt); rhi[nt] = *(const u32x4*)(rp + nt * o_nt + 32); }   // (bf16: o_nt = 64, inside the header)
             }
         }
         // FLAT: filter fragments of this wave's mel row pair x two channel steps: rows 0..3 of the fragment are the 4 flatten
@@ -596,15 +604,15 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
         // every stage issues the same loads and MFMAs: nothing is predicated, see the residual loads above)
         u32x4 xf[RP ? RP : 1];
         if constexpr (RP > 0 && !SPLIT) {
-            const uint32_t t_full = kHdr + ((((uint32_t)cur.n * H + cur.y0 + 2 * wave) * W + cur.x0) * a.C0x) * 2u;
-            const uint32_t t_half = kHdr + ((((uint32_t)cur.n * (H >> 1) + (cur.y0 >> 1) + wave) * (W >> 1) + (cur.x0 >> 1)) * a.C1x) * 2u;
+            const uint32_t t_full = kHdr + act_offset(s_xp0, H, W, a.C0x, cur.n, cur.y0 + 2 * wave, cur.x0, 0);
+            const uint32_t t_half = kHdr + act_offset(s_xp1, H >> 1, W >> 1, a.C1x, cur.n, (cur.y0 >> 1) + wave, cur.x0 >> 1, 0);
 #pragma unroll
             for (int k = 0; k < RP; ++k) {
                 const int sidx = ci * RP + k, ch = sidx * 16;                       // block-uniform
                 const char* base; uint32_t off;
                 if (sidx >= proj_steps) { base = (const char*)a.xp0 - kHdr; off = 0; }
-                else if (ch < a.C0x) { base = (const char*)a.xp0 - kHdr; off = t_full + xf_off + ch * 2u; }
-                else { base = (const char*)a.xp1 - kHdr; off = t_half + xh_off + (ch - a.C0x) * 2u; }
+                else if (ch < a.C0x) { base = (const char*)a.xp0 - kHdr; off = t_full + xf_off + step_off(s_xp0, ch); }
+                else { base = (const char*)a.xp1 - kHdr; off = t_half + xh_off + step_off(s_xp1, ch - a.C0x); }
                 xf[k] = *(const u32x4*)(base + off);
             }
         }
@@ -871,23 +879,23 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
 #endif
 #ifdef SS_DEVBUILD
                         if ((a.dbg & 256) && (!FLAT || a.store_out)) {   // timing-only: each store instruction covers whole 64-byte pixels of one row
-                            char* o1 = (char*)a.out + o_tile + (uint32_t)(px * Cout) * 2u + (hh + 2 * py) * 16;
-                            char* o2 = o1 + (uint32_t)(W * Cout) * 2u;
+                            char* o1 = (char*)a.out + o_tile + (uint32_t)px * s_out.pix + (hh + 2 * py) * 16;
+                            char* o2 = o1 + (uint32_t)W * s_out.pix;
                             to_runs(kh, lo, hi);
-                            *(u32x4*)(o1 + nt * 64) = lo;
-                            *(u32x4*)(o2 + nt * 64) = hi;
+                            *(u32x4*)(o1 + nt * o_nt) = lo;
+                            *(u32x4*)(o2 + nt * o_nt) = hi;
                             to_runs(kl, lo, hi);
-                            *(u32x4*)(o1 + a.lo_delta + nt * 64) = lo;
-                            *(u32x4*)(o2 + a.lo_delta + nt * 64) = hi;
+                            *(u32x4*)(o1 + a.lo_delta + nt * o_nt) = lo;
+                            *(u32x4*)(o2 + a.lo_delta + nt * o_nt) = hi;
                         } else
 #endif
                         if ((!FLAT || a.store_out) && st_ok) {
                             to_runs(kh, lo, hi);
-                            *(u32x4*)(op + nt * 64) = lo;
-                            *(u32x4*)(op + nt * 64 + 32) = hi;
+                            *(u32x4*)(op + nt * o_nt) = lo;
+                            *(u32x4*)(op + nt * o_nt + 32) = hi;
                             to_runs(kl, lo, hi);
-                            *(u32x4*)(op + a.lo_delta + nt * 64) = lo;
-                            *(u32x4*)(op + a.lo_delta + nt * 64 + 32) = hi;
+                            *(u32x4*)(op + a.lo_delta + nt * o_nt) = lo;
+                            *(u32x4*)(op + a.lo_delta + nt * o_nt + 32) = hi;
                         }
                         if constexpr (RES) {                      // the residual projection leaves un-activated (its bias came in through C)
                             // as fp32 accumulator fragments (r_mtile above): launch B adds them to its accumulator as they are
@@ -909,7 +917,7 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                                 x = max(x, __builtin_amdgcn_mov_dpp(x, 0x4E, 0xf, 0xf, true));
                                 pv[r] = __builtin_bit_cast(float, x);
                             }
-                            const uint32_t p_tile = ((((uint32_t)cur.n * (H >> 1) + (cur.y0 >> 1) + wave) * (W >> 1) + (cur.x0 >> 1)) * Cout + co0) * 2u;
+                            const uint32_t p_tile = act_offset(s_pool, H >> 1, W >> 1, Cout, cur.n, (cur.y0 >> 1) + wave, cur.x0 >> 1, co0);
                             char* pp = (char*)a.pool_out + (p_tile + pl_off);
 #ifdef SS_DEVBUILD
                             if (a.dbg & 128) pp = (char*)a.pool_out + ((p_tile + pl_off) & 0x3ffffu);
@@ -921,8 +929,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                             to_runs(pl, lo, hi);
                             const u32x4 pvl = (m & 1) ? hi : lo;
                             if ((m & 3) < 2 && st_ok) {
-                                *(u32x4*)(pp + nt * 64 + (m & 1) * 32) = pvh;
-                                *(u32x4*)(pp + a.lo_delta + nt * 64 + (m & 1) * 32) = pvl;
+                                *(u32x4*)(pp + nt * s_pool.chunk + (m & 1) * 32) = pvh;
+                                *(u32x4*)(pp + a.lo_delta + nt * s_pool.chunk + (m & 1) * 32) = pvl;
                             }
                         }
                     }
@@ -986,8 +994,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                     u32x4 lo, hi;
                     if (!FLAT || a.store_out) {               // c9 itself is only needed when the spec head runs
                         to_runs(k, lo, hi);
-                        *(u32x4*)(op + nt * 64) = lo;
-                        *(u32x4*)(op + nt * 64 + 32) = hi;
+                        *(u32x4*)(op + nt * o_nt) = lo;
+                        *(u32x4*)(op + nt * o_nt + 32) = hi;
                     }
                     if constexpr (RES) {                      // the residual projection leaves un-activated (its bias came in through C)
                         Packed kr;
@@ -997,8 +1005,8 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                             for (int h = 0; h < 2; ++h) kr.p[g][h] = pack_bf16(racc[nt][4 * g + 2 * h], racc[nt][4 * g + 2 * h + 1]);
                         to_runs(kr, lo, hi);
                         char* rp = (char*)a.res_out + (o_tile + st_off);
-                        *(u32x4*)(rp + nt * 64) = lo;
-                        *(u32x4*)(rp + nt * 64 + 32) = hi;
+                        *(u32x4*)(rp + nt * o_nt) = lo;
+                        *(u32x4*)(rp + nt * o_nt + 32) = hi;
                     }
                     if constexpr (POOL) {
                         to_runs(kp, lo, hi);
@@ -1006,9 +1014,9 @@ void conv3x3_v4_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                         // one instruction (both half-waves) stores whole 64-byte pixels
                         const u32x4 pv = (m & 1) ? hi : lo;
                         if ((m & 3) < 2) {
-                            const uint32_t p_tile = ((((uint32_t)cur.n * (H >> 1) + (cur.y0 >> 1) + wave) * (W >> 1) + (cur.x0 >> 1)) * Cout + co0) * 2u;
+                            const uint32_t p_tile = act_offset(s_pool, H >> 1, W >> 1, Cout, cur.n, (cur.y0 >> 1) + wave, cur.x0 >> 1, co0);
                             char* pp = (char*)a.pool_out + (p_tile + pl_off);
-                            *(u32x4*)(pp + nt * 64 + (m & 1) * 32) = pv;
+                            *(u32x4*)(pp + nt * s_pool.chunk + (m & 1) * 32) = pv;
                         }
                     }
                 }

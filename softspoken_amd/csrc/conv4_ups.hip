@@ -105,8 +105,8 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             const int chunk = ci >> 1;
             const int64_t plane = (ci & 1) ? 0 : a.lo_delta;
             const char* base = (const char*)a.src0 - kHdr + plane;
-            const uint32_t cs2 = 2u * a.C0;
-            const uint32_t tp = kHdr + ((((uint32_t)d.n * H + d.y0 - 1) * W + d.x0 - 1) * a.C0 + chunk * 32) * 2u + part16;   // mod 2^32
+            const uint32_t cs2 = a.s_src0.pix;
+            const uint32_t tp = kHdr + act_offset(a.s_src0, H, W, a.C0, d.n, d.y0 - 1, d.x0 - 1, chunk * 32) + part16;   // mod 2^32
 #pragma unroll
             for (int it = 0; it < AIT; ++it) {
                 uint32_t off = __umul24(pix_full[it], cs2) + tp;
@@ -115,8 +115,8 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
             }
         } else {
             const char* base = (const char*)a.src1 - kHdr;
-            const uint32_t cs2 = 2u * a.C1;
-            const uint32_t tp = kHdr + ((((uint32_t)d.n * (H >> 1) + (d.y0 >> 1) - 1) * (W >> 1) + (d.x0 >> 1) - 1) * a.C1 + (ci - 2 * nreg) * 32) * 2u + part16;
+            const uint32_t cs2 = a.s_src1.pix;
+            const uint32_t tp = kHdr + act_offset(a.s_src1, H >> 1, W >> 1, a.C1, d.n, (d.y0 >> 1) - 1, (d.x0 >> 1) - 1, (ci - 2 * nreg) * 32) + part16;
             uint32_t off = __umul24(pix_low, cs2) + tp;
             if (flags_low & tm) off = 0;
             ra[0] = *(const u32x4*)(base + off);                          // high halves
@@ -173,7 +173,7 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
     const int base_u = Y * kRowU + X * kPix + hh * 16;
     const int boff0 = lane * 16;
     // where this lane's runs of its pixel (2 Y + ca, 2 X + cb) go, relative to the tile's origin
-    const uint32_t st_off = (uint32_t)(((2 * Y + ca) * W + 2 * X + cb) * Cout + hh * 8) * 2u;
+    const uint32_t st_off = (uint32_t)((2 * Y + ca) * W + 2 * X + cb) * a.s_out.pix + hh * 16u;
     // per tap of the skip patch: (ca + dy) rows down, column cb + dx: its parity half and its place there
     int tap_r[9];
 #pragma unroll
@@ -288,7 +288,7 @@ void conv3x3_ups_kernel(ConvArgs a, int total_tiles, int lds_b_bytes) {
                     ovf = pk_max_u16(ovf, kh.p[g][h]);
                     kl.p[g][h] = split_lo(kh.p[g][h], x0, x1);
                 }
-            char* op = (char*)a.out + ((((uint32_t)cur.n * H + cur.y0) * W + cur.x0) * Cout) * 2u + st_off;
+            char* op = (char*)a.out + act_offset(a.s_out, H, W, Cout, cur.n, cur.y0, cur.x0, 0) + st_off;
             u32x4 lo, hi;
             to_runs(kh, lo, hi);
             *(u32x4*)(op) = lo;
@@ -442,8 +442,8 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
         if (p.sec == 0) {
             const int64_t plane = p.part ? 0 : a.lo_delta;                     // part 0: low halves; part 1: high halves
             const char* base = (const char*)a.src0 - kHdr + plane;
-            const uint32_t cs2 = 2u * a.C0;
-            const uint32_t tp = kHdr + ((((uint32_t)d.n * H + d.y0 - 1) * W + d.x0 - 1) * a.C0 + p.chunk * 32) * 2u + part16;   // mod 2^32
+            const uint32_t cs2 = a.s_src0.pix;
+            const uint32_t tp = kHdr + act_offset(a.s_src0, H, W, a.C0, d.n, d.y0 - 1, d.x0 - 1, p.chunk * 32) + part16;   // mod 2^32
 #pragma unroll
             for (int it = 0; it < AIT; ++it) {
                 uint32_t off = __umul24(pix_full[it], cs2) + tp;
@@ -452,8 +452,8 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
             }
         } else {
             const char* base = (const char*)a.src1 - kHdr;
-            const uint32_t cs2 = 2u * a.C1;
-            const uint32_t tp = kHdr + ((((uint32_t)d.n * (H >> 1) + (d.y0 >> 1) - 1) * (W >> 1) + (d.x0 >> 1) - 1) * a.C1 + p.chunk * 32) * 2u + part16;
+            const uint32_t cs2 = a.s_src1.pix;
+            const uint32_t tp = kHdr + act_offset(a.s_src1, H >> 1, W >> 1, a.C1, d.n, (d.y0 >> 1) - 1, (d.x0 >> 1) - 1, p.chunk * 32) + part16;
             uint32_t off = __umul24(pix_low, cs2) + tp;
             if (flags_low & tm) off = 0;
             ra[0] = *(const u32x4*)(base + off);                          // high halves
@@ -543,7 +543,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     const int base_r = 2 * Y * kRowR + X * kPix + hh * 16;
     const int base_u = Y * kRowU + X * kPix + hh * 16;
     const int boff0 = lane * 16;
-    const uint32_t st_off = (uint32_t)(((2 * Y + ca) * W + 2 * X + cb) * Cout + hh * 8) * 2u;
+    const uint32_t st_off = (uint32_t)((2 * Y + ca) * W + 2 * X + cb) * a.s_out.pix + hh * 16u;
     const uint32_t r_lane = (uint32_t)(32 * hh + 4 * X + 2 * ca + cb) * 32u;
     int tap_r[9];
 #pragma unroll
@@ -586,7 +586,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
     };
     // h of a finished position: ReLU, split, store (its r went out in the position's last off-phase)
     f32x16 acc_done;
-    uint32_t done_off = 0;                                // element offset of the finished position's tile origin and channel group
+    uint32_t done_off = 0;                                // byte offset of the finished position's tile origin and channel group
     bool have_done = false;
     auto store_h = [&]() {
         __builtin_amdgcn_sched_barrier(0);
@@ -602,7 +602,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
                 ovf = pk_max_u16(ovf, kh.p[g][h]);
                 kl.p[g][h] = split_lo(kh.p[g][h], x0, x1);
             }
-        char* op = (char*)a.out + done_off * 2u + st_off;
+        char* op = (char*)a.out + done_off + st_off;
         u32x4 lo, hi;
         to_runs(kh, lo, hi);
         *(u32x4*)(op) = lo;
@@ -739,7 +739,7 @@ void conv3x3_upsr_kernel(ConvArgs a, int total_tiles, int) {
             *(f32x4*)(rq_p + a.lo_delta) = f32x4{racc[8], racc[9], racc[10], racc[11]};
             *(f32x4*)(rq_p + a.lo_delta + 16) = f32x4{racc[12], racc[13], racc[14], racc[15]};
         }
-        if (last) { acc_done = acc; done_off = (((uint32_t)cur.n * H + cur.y0) * W + cur.x0) * Cout + cur.g * 32; have_done = true; }
+        if (last) { acc_done = acc; done_off = act_offset(a.s_out, H, W, Cout, cur.n, cur.y0, cur.x0, cur.g * 32); have_done = true; }
         if (KIND == 1 && c == 0 && have_done && !SS_ABL(20)) { store_h(); have_done = false; }
         if (KIND == 1 && c == 0) compute_next();          // (before the patch requests reach into the next position: the second chunk's R0 at the earliest)
         if (last && more) { cur = nxt; cur_i = nxt_i; }

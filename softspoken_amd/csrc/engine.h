@@ -96,6 +96,7 @@ struct Workspace {
     std::map<std::string, void*> act;                     // tensor name -> first byte (high plane in f16x2 mode) inside arena
     void* arena = nullptr;
     int64_t lo_delta = 0;                                 // f16x2: byte distance from a tensor's high plane to its low plane
+    std::map<const void*, ActStride> stride;              // 16-bit modes: a tensor's byte order (kernels.h ActStride), by its first byte
     float* feat = nullptr; float* flat = nullptr;         // front-end features; conv_flatten's row-group partial sums
     int flat_groups = 0;                                  // row groups the last FLAT launch wrote per window into `flat`
 };

@@ -65,9 +65,13 @@ void resolve_events(ss_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// activation workspace: NHWC tensors for `n` windows.  Every tensor is preceded by a 256-byte zero header (conv4.hip reads it
+// activation workspace: tensors for `n` windows.  Every tensor is preceded by a 256-byte zero header (conv4.hip reads it
 // for out-of-image patch pieces).  f16x2 mode keeps two planes per tensor (high and low halves of every value, both f16) in two
 // arenas of identical layout, so that one byte distance (Workspace::lo_delta) leads from any high plane to its low plane.
+// Byte order inside a tensor (kernels.h ActStride): [window][H][W][C] in fp32 and bf16; in f16x2 the tensors wider than 32 channels are
+// chunk-planar, [window][C / 32][H][W][32] (the r tensors are in MFMA fragment order in f16x2 and have no such order).  The order is
+// chosen per tensor here, when the workspace is built, and travels to the kernels as two strides per tensor; the window stride, the
+// headers and lo_delta are the same in both orders.  Development build: SOFTSPOKEN_LAYOUT=0 keeps every tensor [window][H][W][C].
 // ------------------------------------------------------------------------------------------------------
 static constexpr size_t kActHeader = 256;
 
@@ -122,7 +126,12 @@ static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, Workspace& w, s
             e = hipMemsetAsync((char*)w.arena + pl * total + off - kActHeader, 0, kActHeader, stream);
             if (e != hipSuccess) { what = "hipMemsetAsync"; free_ws(w); return e; }
         }
-    for (size_t i = 0; i < offs.size(); ++i) w.act[kWsTensors[i].n] = (char*)w.arena + offs[i];
+    const bool planar = c->prec == kF16x2 && dev_env("SOFTSPOKEN_LAYOUT", kActChunkPlanar ? 1 : 0) != 0;
+    for (size_t i = 0; i < offs.size(); ++i) {
+        const WsTensor& t = kWsTensors[i];
+        w.act[t.n] = (char*)w.arena + offs[i];
+        if (c->prec != kFp32) w.stride[w.act[t.n]] = act_stride(t.H, t.W, t.C, planar && t.n[0] != 'r');
+    }
     w.lo_delta = planes == 2 ? (int64_t)total : 0;
     w.bytes = (int64_t)(total * planes + feat_b + flat_b);
     w.chunk = n;
@@ -228,6 +237,16 @@ static void mark_written(ss_ctx* c, const Workspace& ws, const void* p) {
 #endif
 }
 
+// byte order of the workspace tensor at p for a 16-bit launch; false: a tensor the workspace does not know (never after ensure_workspace)
+static bool stride_of(const Workspace& ws, const void* p, ActStride& s) {
+    s = ActStride{0u, 0u};
+    if (!p) return true;
+    const auto it = ws.stride.find(p);
+    if (it == ws.stride.end()) return false;
+    s = it->second;
+    return true;
+}
+
 // One launch of a ResBlock half.  A launches (r_out) compute h and the residual projection r from the block input
 // (x0 [+ upsampled x1]); B launches (r_in) compute the block output from h and add r.
 static int run_conv2(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPlan& p, int n, const void* x0, const void* x1, void* out, void* pool,
@@ -242,6 +261,8 @@ static int run_conv2(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPla
     a.rank1_src = feat; a.rank1_w = p.d_rank1; a.out = out; a.pool_out = pool;
     a.N = n; a.H = p.H; a.W = p.W; a.Cout = p.Cout; a.relu = 1;
     a.lo_delta = ws.lo_delta; a.range_flag = c->d_range_flag;
+    if (c->prec != kFp32 && !(stride_of(ws, x0, a.s_src0) && stride_of(ws, x1, a.s_src1) && stride_of(ws, out, a.s_out) && stride_of(ws, pool, a.s_pool)))
+        return fail(c, SS_ERR_STATE, "no byte order for a tensor of " + p.name);
     if (isA) { a.C0 = p.C0; a.C1 = p.C1; } else { a.C0 = p.Cout; a.C1 = 0; }       // B's 3x3 input is h
     a.dbg = base_dbg();
     const double cin = a.C0 + a.C1;
@@ -308,6 +329,10 @@ static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const Co
     b.proj_w = pb.d_proj; b.xp0 = x0; b.xp1 = x1; b.C0x = pa.C0; b.C1x = pa.C1;
     b.flat_w4 = ex.flat_w4; b.flat_part = ex.flat_part; b.store_out = ex.store_out;
     a.dbg = b.dbg = base_dbg();
+    if (!(stride_of(ws, x0, a.s_src0) && stride_of(ws, x1, a.s_src1) && stride_of(ws, h, a.s_out) && stride_of(ws, h, b.s_src0) &&
+          stride_of(ws, out, b.s_out) && stride_of(ws, pool, b.s_pool)))
+        return fail(c, SS_ERR_STATE, "no byte order for a tensor of " + pa.name);
+    b.s_xp0 = a.s_src0; b.s_xp1 = a.s_src1;
     // f16x2: the A launch with the upsampled input half at low resolution (conv4_ups.hip: four pre-summed taps per output parity class
     // instead of nine on those channels) where that form exists -- conv9_1.A
     ConvArgs au = a;
@@ -419,7 +444,8 @@ static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const fl
 }
 
 #ifdef SS_DEVBUILD
-// ss_debug_activation: one plane of a tensor of the last pass, [n][H][W][C] as stored, and its channel exponents
+// ss_debug_activation: one plane of a tensor of the last pass as [n][H][W][C], whatever its stored order (a chunk-planar tensor is
+// gathered on the host), and its channel exponents
 int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int64_t n, void* out, int64_t out_bytes, int32_t* shape,
                      int32_t* exponents) {
     if (!c || !name) return fail(c, SS_ERR_ARG, "ss_debug_activation: null argument");
@@ -461,7 +487,18 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const char* src = (const char*)base + (plane ? w.lo_delta : 0) + first * per;
-        HIPCHK(c, hipMemcpy(out, src, (size_t)need, hipMemcpyDeviceToHost));
+        const auto st = w.stride.find(base);
+        if (st == w.stride.end() || st->second.pix == (uint32_t)(C * es)) {
+            HIPCHK(c, hipMemcpy(out, src, (size_t)need, hipMemcpyDeviceToHost));
+        } else {                                          // stored [n][C / 32][H][W][32]: 64-byte pieces to their pixels
+            std::vector<char> tmp((size_t)need);
+            HIPCHK(c, hipMemcpy(tmp.data(), src, (size_t)need, hipMemcpyDeviceToHost));
+            const ActStride s = st->second;
+            for (int64_t i = 0; i < n; ++i)
+                for (int k = 0; k < C / 32; ++k)
+                    for (int64_t px = 0; px < (int64_t)H * W; ++px)
+                        memcpy((char*)out + i * per + px * C * 2 + k * 64, tmp.data() + i * per + (int64_t)k * s.chunk + px * s.pix, 64);
+        }
     }
     return SS_OK;
 }

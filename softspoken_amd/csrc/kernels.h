@@ -30,8 +30,31 @@ inline hipError_t allow_full_lds(const void* kernel, std::atomic<uint64_t>& done
     return e;
 }
 
+// ---- byte order of a 16-bit activation tensor ---------------------------------------------------------------------------------
+// Every loader and storer of the 16-bit conv kernels works on (32-channel chunk x pixels), so a tensor's place of (n, y, x, c) is
+// given by two strides beside the window stride H W C 2:
+//   offset = n (H W C 2) + (c / 32) chunk + (y W + x) pix + (c % 32) 2
+//   pixel-major, [window][H][W][C]:               pix = 2 C, chunk = 64        (bf16; f16x2 tensors of 32 channels; SOFTSPOKEN_LAYOUT=0)
+//   chunk-planar, [window][C / 32][H][W][32]:     pix = 64,  chunk = H W 64    (f16x2 tensors wider than 32 channels)
+// Both fill the same H W C 2 bytes of a window, and for C = 32 they are the same order.  Chunk-planar, a chunk's patch row is 18
+// pixels x 64 B of contiguous memory: every 128-byte line a stage fetches is consumed by that stage, and a wave's 16-byte-per-lane
+// load or store covers 1 KB of whole lines (pixel-major it covers sixteen half-used lines, and the line's other half is fetched
+// again two stages later -- profiles/r05_fetch_order.md, profiles/r08_chunk_planar.md).
+// fp32 tensors (conv2*.hip) are [window][H][W][C] and do not use the rule.
+static constexpr bool kActChunkPlanar = true;       // the product's order for the f16x2 tensors wider than 32 channels
+struct ActStride { uint32_t pix, chunk; };          // bytes from a pixel to the next / from a 32-channel chunk to the next
+__host__ __device__ inline ActStride act_stride(int H, int W, int C, bool planar) {
+    return (planar && C > 32) ? ActStride{64u, (uint32_t)H * (uint32_t)W * 64u} : ActStride{2u * (uint32_t)C, 64u};
+}
+__host__ __device__ inline uint32_t act_window_bytes(int H, int W, int C) { return (uint32_t)H * (uint32_t)W * (uint32_t)C * 2u; }
+// byte offset of (n, y, x, c) from the tensor's first byte, mod 2^32 (the supports predicates hold a tensor below 4 GB).  y and x may
+// be -1 (a patch origin): the pieces that are read lie inside the picture, and their offsets come out right mod 2^32
+__host__ __device__ inline uint32_t act_offset(ActStride s, int H, int W, int C, int n, int y, int x, int c) {
+    return (uint32_t)n * act_window_bytes(H, W, C) + (uint32_t)(c >> 5) * s.chunk + (uint32_t)(y * W + x) * s.pix + (uint32_t)(c & 31) * 2u;
+}
+
 // ---- implicit-GEMM 3x3 (+ fused 1x1 residual) convolution on MFMA ---------------------------------
-// Activations are NHWC ([window][H][W][C]), element type float or bf16.  One launch computes
+// Element type float (conv2*.hip, [window][H][W][C]) or 16 bits (byte order: ActStride above).  One launch computes
 //   out = act( conv3x3(cat[src0, up2(src1)]) + conv1x1(cat[res0, up2(res1)]) + rank1 + bias )
 // where every term but the 3x3 is optional, and optionally also writes maxpool2x2(out).
 struct ConvArgs {
@@ -65,6 +88,8 @@ struct ConvArgs {
     int64_t lo_delta;
     int* range_flag;                              // f16x2: set to 1 when a value that is being split does not fit an f16 (overflow, NaN)
     void* stamps;                                 // dev build: [grid][waves][8] uint32 segment times of a stage (null otherwise)
+    // 16-bit kernels (conv4.hip, conv4_ups.hip): byte order of src0 / src1 / out / pool_out / xp0 / xp1 (res_in and a bf16 res_out: as out)
+    ActStride s_src0, s_src1, s_out, s_pool, s_xp0, s_xp1;
 };
 // ---- work order of the four-tile ring kernels (conv4.hip RING, conv4_ups.hip conv3x3_upsr_kernel) ----------------
 // A launch has total_pos positions (8 x 16-pixel tiles) x ngroups groups of 32 output channels.  XCD x owns the positions
