@@ -308,7 +308,7 @@ int ss_get_region_peaks(ss_ctx* ctx, int first_file, int n_channels, double* pea
 /* ---- streaming detection: one recording's PCM arriving in pieces, its final regions returned early -----------------------
  * A stream is one recording in one enum ss_pcm_format encoding, rate and channel count (the limits of ss_add_pcm), pushed in pieces
  * of any size down to one frame; its threshold, break and window step (the context's, ss_set_window_step) are fixed when it is opened.  Each step takes every stream of the context as
- * far as its pushed audio allows -- decode + mixdown + resample with carried state, every window that has become complete (in passes
+ * far as its pushed audio allows -- decode + mixdown (or, in each-channel mode below, one signal per channel) + resample with carried state, every window that has become complete (in passes
  * of up to ss_set_chunk_windows windows, mixed across streams), the averaging of the bins that became final, the regions -- and
  * returns what became final.  Equality: the concatenation of every region and every averaged bin a stream returned equals what
  * ss_add_pcm + ss_run(threshold, break_s) give for the same frames on a context of the same precision and window step (regions as ss_region values,
@@ -334,12 +334,13 @@ int ss_get_region_peaks(ss_ctx* ctx, int first_file, int n_channels, double* pea
 typedef struct ss_stream_info {
     int64_t frames_pushed;     /* frames pushed so far (stepped and staged) */
     int64_t frames_staged;     /* of them: waiting for the next step */
-    int64_t windows_run;       /* windows of the recording run so far */
-    int64_t windows_ready;     /* windows the next step would run (> 0: the stream takes part in it) */
+    int64_t windows_run;       /* windows of the recording run so far -- per channel: an each-channel stream of C channels ran C x as many */
+    int64_t windows_ready;     /* windows the next step would run, per channel likewise (> 0: the stream takes part in it) */
     double final_until_s;      /* audio time before which every bin is final (returned) */
     int32_t closed;            /* ss_stream_close was called */
     int32_t finished;          /* closed and the last step has run: every result is out */
-    int64_t state_bytes;       /* bytes the stream carries between steps (device samples, logits, host record), staging excluded */
+    int64_t state_bytes;       /* bytes the stream carries between steps (device samples, logits, host record), staging excluded; an
+                                  each-channel stream: every lane once, the raw PCM held for output once */
 } ss_stream_info;
 
 /* Open a stream; *stream_id names it on this context.  Needs a context with weights. */
@@ -428,6 +429,43 @@ int ss_stream_output(ss_ctx* ctx, int stream_id, int16_t* out, int64_t cap_frame
 int ss_stream_get_output_info(ss_ctx* ctx, int stream_id, ss_stream_output_info* out);
 /* Images: a stream with output exports "SSSTRM03" (the header, the step, the erase parameters, frames_out, the decided ranges still
  * ahead and the held PCM); ss_stream_import reads all three, and a stream without output writes the image it always wrote. */
+
+/* ---- each-channel streams: every channel detected alone, one merged table ------------------------------------------------------
+ * ss_stream_open_channels opens a stream of C channels that carries C lanes, one per channel, instead of the one lane of the channel
+ * mean: what ss_add_pcm_channels is to ss_add_pcm.  The lanes share the stream's plan (frame count, resampler positions, window and bin
+ * counts, the frontier of final bins) and every ss_stream_* call works on such a stream.  For any split into pieces, any cadence of
+ * steps, whichever other streams share the steps (mix streams included) and across ss_stream_export / ss_stream_import, on a context
+ * of precision P and window step s:
+ *   Per channel.    The concatenation of what ss_stream_avg_channel(stream, c) returned equals ss_get_avg(first_file + c) after
+ *                   ss_add_pcm_channels + ss_run(threshold, break_s) of the same frames on a context of P and s: averages as doubles, bit
+ *                   for bit, bin numbers exactly.
+ *   Merged table.   The concatenation of ss_stream_regions equals ss_get_regions_union(first_file, C) of that run, as ss_region values.
+ *   Merged series.  ss_stream_avg returns the series the table is found on: per covered bin the fmax over the channels' averages (a NaN
+ *                   on one channel is passed over; NaN only when every channel's is), so ss_find_regions(ss_stream_avg ...) gives the
+ *                   stream's regions, as for a mix stream.
+ *   Peaks.          ss_stream_region_peaks returns peaks[r * C + c] for the regions the last step returned: the values
+ *                   ss_get_region_peaks gives for the same regions of the whole-file run -- the fmax of channel c's averages over the
+ *                   covered bins from the region's first to its last bin, both and the below-threshold bins of the gaps that break_s
+ *                   merged included; -inf when all of them are NaN.  Bit for bit.
+ *   Output.         With output, the concatenation of ss_stream_output equals ss_silence_pcm(the whole recording, E(R)), byte for byte,
+ *                   R = the merged regions the stream returned: every channel is zeroed over the merged table.
+ *   Bounds.         B, D and the limit rule ss_stream_output_limit hold unchanged; the walk that feeds them runs over the merged flags.
+ *   One channel.    A one-channel recording opened here is a plain stream: the same path, results and image as ss_stream_open's (and
+ *                   ss_stream_region_peaks answers SS_ERR_STATE, as on a mix stream).
+ * erase == NULL and with_output == 0: detection only; otherwise a stream with output (erase == NULL: pad_s = min_len_s = 0), with
+ * ss_stream_open_output's rule for the threshold. */
+int ss_stream_open_channels(ss_ctx* ctx, int format, int sample_rate, int channels, double threshold, double break_s,
+                            const ss_stream_erase* erase, int with_output, int* stream_id);
+/* ss_stream_avg of one channel's lane (the same bins as ss_stream_avg's).  SS_ERR_ARG for a channel out of range; on a mix stream
+ * channel 0 is ss_stream_avg itself. */
+int ss_stream_avg_channel(ss_ctx* ctx, int stream_id, int channel, double* avg, int64_t* bin_idx, int64_t cap, int64_t* n_out);
+/* *n_out = the regions the last step returned; peaks (NULL to ask) takes *n_out x channels doubles; SS_ERR_CAPACITY when cap_regions
+ * is smaller; SS_ERR_STATE on a mix stream. */
+int ss_stream_region_peaks(ss_ctx* ctx, int stream_id, double* peaks, int64_t cap_regions, int64_t* n_out);
+/* Images: an each-channel stream of more than one channel exports "SSSTRM04" (the header, the step, the lane count, the peak state, the
+ * output block of "SSSTRM03" when it has output, every lane's carried data), so the mode survives the move to an fp32 context;
+ * ss_stream_import reads all four, and answers SS_ERR_ARG to an "SSSTRM04" image whose lane count is neither 1 nor its channel count
+ * or whose sizes do not add up to n. */
 
 /* ---- separation silencer: remove the speech part of the spectrum inside the erased intervals ---------------------------
  * The second silencing method.  ss_silence_pcm zeroes every reviewed interval (silencer_ui.py:974-998), and with it whatever

@@ -1333,6 +1333,30 @@ __global__ __launch_bounds__(256) void stream_decode_kernel(const unsigned char*
     }
 }
 
+// The frames pushed since the last step of the each-channel streams, every channel to a plane of its own: sample (i, c) is
+// decode_sample(base, format, i C + c) -- what decode_channels_batch_kernel stores for the whole file --, no mean.  A thread takes a
+// frame, reads it once and stores one float to each of the C planes, so a wave's stores to a plane are 256 contiguous bytes.  16-bit
+// stereo: the frame is one aligned 32-bit word (the host places every stream's pieces at a multiple of 16 bytes of the upload), its low
+// half channel 0 -- the same conversion, (float)(short) / 32768.  The planes of a 22 050 Hz stream are the lanes' signals themselves.
+__global__ __launch_bounds__(256) void stream_decode_channels_kernel(const unsigned char* __restrict__ pcm,
+                                                                     const StreamDecodeChannels* __restrict__ ds, int n) {
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamDecodeChannels d = ds[k];
+        const unsigned char* base = pcm + d.pcm_off;
+        if (d.format == 2 && d.channels == 2) {               // SS_PCM_S16, stereo
+            const uint32_t* fr = (const uint32_t*)base;
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.frames; i += (int64_t)gridDim.x * 256) {
+                const uint32_t w = fr[i];
+                d.dst[i] = (float)(short)(w & 0xffffu) / 32768.0f;
+                d.dst[d.stride + i] = (float)(short)(w >> 16) / 32768.0f;
+            }
+            continue;
+        }
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.frames; i += (int64_t)gridDim.x * 256)
+            for (int c = 0; c < d.channels; ++c) d.dst[(int64_t)c * d.stride + i] = decode_sample(base, d.format, i * d.channels + c);
+    }
+}
+
 // outputs [m0, m0 + n) of a stream from its decoded input history mono[idx - mono_base] (idx < frames; zeros past the end once the
 // stream is closed -- the host only asks for outputs whose taps lie inside the input before that): resample_batch_kernel's arithmetic,
 // tap order, float32 multiply then add, no contraction, so every output equals the whole-file resampler's bit for bit
@@ -1373,6 +1397,27 @@ __global__ __launch_bounds__(256) void stream_average_kernel(const StreamAvg* __
             const bool cov = c >= 1, abv = cov && v > a.threshold;
             avg[a.out_off + t] = v;
             flags[a.out_off + t] = (unsigned char)((cov ? 1 : 0) | (abv ? 2 : 0));
+        }
+    }
+}
+
+// "speech on any channel" of the bins an each-channel stream's lanes just made final: the OR of the lanes' flag bits (covered is the
+// same on every lane: they share one plan) and the fmax of their averages -- fmax, not a maximum that returns a NaN operand: a NaN on
+// one lane is passed over and the result is NaN only when every lane's is.  Written beside the lanes' own values; the host walks these
+// flags as it walks a mix stream's.
+__global__ __launch_bounds__(256) void stream_union_kernel(const StreamUnion* __restrict__ us, int n, double* __restrict__ avg,
+                                                           unsigned char* __restrict__ flags) {
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamUnion u = us[k];
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < u.nb; t += (int64_t)gridDim.x * 256) {
+            double m = avg[u.in_off + t];
+            unsigned f = flags[u.in_off + t];
+            for (int l = 1; l < u.lanes; ++l) {
+                m = fmax(m, avg[u.in_off + (int64_t)l * u.nb + t]);
+                f |= flags[u.in_off + (int64_t)l * u.nb + t];
+            }
+            avg[u.out_off + t] = m;
+            flags[u.out_off + t] = (unsigned char)f;
         }
     }
 }
@@ -1474,6 +1519,16 @@ hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n,
 hipError_t launch_stream_average(const StreamAvg* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s) {
     if (n <= 0 || max_bins <= 0) return hipSuccess;
     hipLaunchKernelGGL(stream_average_kernel, stream_grid(n, max_bins), dim3(256), 0, s, d, n, avg, flags);
+    return hipGetLastError();
+}
+hipError_t launch_stream_decode_channels(const void* pcm, const StreamDecodeChannels* d, int n, int64_t max_frames, hipStream_t s) {
+    if (n <= 0 || max_frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_decode_channels_kernel, stream_grid(n, max_frames), dim3(256), 0, s, (const unsigned char*)pcm, d, n);
+    return hipGetLastError();
+}
+hipError_t launch_stream_union(const StreamUnion* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s) {
+    if (n <= 0 || max_bins <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_union_kernel, stream_grid(n, max_bins), dim3(256), 0, s, d, n, avg, flags);
     return hipGetLastError();
 }
 hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s) {

@@ -293,11 +293,19 @@ struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, 
 struct StreamSilence { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, frame0, n, out_off;
                        int32_t n_ranges, format, channels, pad; };
 struct StreamCopyBytes { const unsigned char* src; unsigned char* dst; int64_t n; };   // n bytes, any alignment
+// each-channel streams (ss_stream_open_channels): the pushed frames of a stream of `channels` lanes -> channel c's samples at
+// dst[c stride ..), no mean; pcm_off is a multiple of 16 (the fast form reads a 16-bit stereo frame as one 32-bit word)
+struct StreamDecodeChannels { int64_t pcm_off; int64_t frames; float* dst; int64_t stride; int32_t format, channels; };
+// the merged series of such a stream: its `lanes` lanes' nb new bins lie at avg / flags [in_off + l nb ..); the OR of the flag bits and
+// the fmax of the averages (a NaN passed over) go to avg / flags [out_off ..)
+struct StreamUnion { int64_t in_off, nb, out_off; int32_t lanes, pad; };
 hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s);
 hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s);
 hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s);
 hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s);
 hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s);
 hipError_t launch_stream_average(const StreamAvg* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s);
+hipError_t launch_stream_decode_channels(const void* pcm, const StreamDecodeChannels* d, int n, int64_t max_frames, hipStream_t s);
+hipError_t launch_stream_union(const StreamUnion* d, int n, int64_t max_bins, double* avg, unsigned char* flags, hipStream_t s);
 
 }  // namespace ss

@@ -3,6 +3,10 @@
 // other half of a double-buffered arena:
 //   copy (carried samples / logits, padding zeros) -> decode + mixdown -> resample -> windows (forward_chunk, passes across streams)
 //   -> new logits behind the carried ones -> averaging of the bins that became final -> regions continued on the host.
+// A stream opened in each-channel mode (ss_stream_open_channels, more than one channel) carries one lane per channel instead of the one
+// mixdown lane: the lanes share the stream's plan and differ only in their arena segments; its pieces are decoded to one plane per
+// channel, every lane goes through the copies, the resampler, the passes and the averaging with a descriptor of its own, and the bins
+// that became final are merged (OR of the flags, fmax of the averages) into the series the host walks.
 // Nothing of the stream state changes before the step has completed without SS_ERR_RANGE: the arena half the streams live in is only
 // read, and the host records are updated at the end (commit), so a refused step leaves every stream as it was.
 // Streams opened with output (ss_stream_open_output) then get their decided frames back as 16-bit PCM with the detected speech zeroed
@@ -48,7 +52,16 @@ struct StreamRec {
     int64_t frames_out = 0, erased = 0, raw_off = 0;
     std::vector<int64_t> er_rng; std::vector<unsigned char> h_raw;
     int64_t o_first = 0, o_n = 0, o_off = 0;          // the last step's frames: o_n of them at the pinned output buffer + o_off (int16s)
+    // each-channel mode: `lanes` = ch lanes (1: a plain stream); lane l's carried segments lie l x mono_ls / sig_ls / lg_ls floats behind
+    // lane 0's (mono_off, sig_off, lg_off) in the current arena half, and back to back in h_mono / h_sig / h_lg after an import
+    int lanes = 1; int64_t mono_ls = 0, sig_ls = 0, lg_ls = 0;
+    // running per-channel peaks (fmax over covered bins; -inf: none yet) of the open run, of the pending merged region (mg.cur, the gaps it
+    // has merged included) and of the covered bins since the last run closed (the gap the next run may still merge)
+    std::vector<double> pk_run, pk_cur, pk_gap;
+    // the last step's results per lane: the lanes' averages of the bins in b_out (lane-major), peaks[r * lanes + c] of r_out
+    std::vector<double> la_out, p_out;
     int64_t frame_bytes() const { return (int64_t)ch * (int64_t)pcm_bytes_per_sample(format); }
+    void set_lanes(int n) { lanes = n; const double ninf = -HUGE_VAL; pk_run.assign(n > 1 ? n : 0, ninf); pk_cur = pk_run; pk_gap = pk_run; }
 };
 
 // what the next step does with a stream (host arithmetic only)
@@ -63,6 +76,7 @@ struct StreamPlan {
     int64_t lw0 = 0;                                  // logits in the step's arena: windows [lw0, i_end)
     // offsets in the next arena half
     int64_t mono_off = 0, sig_off = 0, lg_off = 0, up_off = 0, host_off = 0, raw_up_off = 0;
+    int64_t mono_ls = 0, sig_ls = 0, lg_ls = 0;       // floats from a lane's segment to the next lane's
     int64_t f0 = 0; bool was_host = false;            // frames decoded before the step; the carried state came from an image
     int64_t mono_len() const { return F - kb; }
     int64_t sig_len() const { return sig_keep + pre + (m_end - m_next_) + post; }
@@ -183,7 +197,7 @@ static StreamRec* find_stream(ss_ctx* c, int id) {
 }
 
 static int64_t state_bytes(const StreamRec& s) {
-    return (int64_t)sizeof(StreamRec) + 4 * (s.mono_n + s.sig_n + s.lg_n * 256) +
+    return (int64_t)sizeof(StreamRec) + 4 * s.lanes * (s.mono_n + s.sig_n + s.lg_n * 256) + 8 * (int64_t)(3 * s.pk_run.size()) +
            (s.out_on ? (s.frames_in - s.frames_out) * s.frame_bytes() + 8 * (int64_t)s.er_rng.size() : 0);
 }
 
@@ -192,7 +206,8 @@ static int init_rates(ss_ctx* c, StreamRec& s) {
     return get_taps(c, s.sr, s.L, s.M, s.half, &s.d_taps);
 }
 
-static int open_stream(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase, bool out_on, int* id) {
+static int open_stream(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase, bool out_on, int* id,
+                       bool each = false) {
     static const unsigned char one[8] = {0};
     int rc = check_pcm_args(c, one, format, sr, ch, 0);
     if (rc) return rc;
@@ -205,6 +220,7 @@ static int open_stream(ss_ctx* c, int format, int sr, int ch, double threshold, 
     s.format = format; s.sr = sr; s.ch = ch; s.thr = threshold; s.mg.brk = break_s;
     s.step = c->step; s.per_step = step_samples(c->step);
     s.out_on = out_on; if (erase) s.er = *erase;
+    s.set_lanes(each ? ch : 1);                          // (one channel in each-channel mode: a plain stream)
     if ((rc = init_rates(c, s))) return rc;
     StreamSet& S = streams_of(c);
     *id = S.next_id++;
@@ -219,6 +235,11 @@ extern "C" int ss_stream_open(ss_ctx* c, int format, int sr, int ch, double thre
 extern "C" int ss_stream_open_output(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
                                      int* id) {
     return open_stream(c, format, sr, ch, threshold, break_s, erase, true, id);
+}
+
+extern "C" int ss_stream_open_channels(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
+                                       int with_output, int* id) {
+    return open_stream(c, format, sr, ch, threshold, break_s, erase, erase != nullptr || with_output != 0, id, true);
 }
 
 extern "C" int ss_stream_push(ss_ctx* c, int id, const void* pcm, int64_t frames) {
@@ -282,6 +303,30 @@ extern "C" int ss_stream_avg(ss_ctx* c, int id, double* avg, int64_t* bin_idx, i
     return SS_OK;
 }
 
+extern "C" int ss_stream_avg_channel(ss_ctx* c, int id, int channel, double* avg, int64_t* bin_idx, int64_t cap, int64_t* n_out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_avg_channel: bad argument");
+    if (channel < 0 || channel >= s->lanes) return fail(c, SS_ERR_ARG, "ss_stream_avg_channel: no such channel (a mix stream has channel 0 only)");
+    if (s->lanes == 1) return ss_stream_avg(c, id, avg, bin_idx, cap, n_out);
+    *n_out = (int64_t)s->b_out.size();
+    if (!avg && !bin_idx) return SS_OK;
+    if (cap < *n_out) return fail(c, SS_ERR_CAPACITY, "ss_stream_avg_channel: capacity < " + std::to_string(*n_out));
+    if (*n_out && avg) memcpy(avg, s->la_out.data() + (size_t)channel * s->b_out.size(), s->b_out.size() * 8);
+    if (*n_out && bin_idx) memcpy(bin_idx, s->b_out.data(), s->b_out.size() * 8);
+    return SS_OK;
+}
+
+extern "C" int ss_stream_region_peaks(ss_ctx* c, int id, double* peaks, int64_t cap_regions, int64_t* n_out) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_region_peaks: bad argument");
+    if (s->lanes == 1) return fail(c, SS_ERR_STATE, "ss_stream_region_peaks: not an each-channel stream of several channels (ss_stream_open_channels)");
+    *n_out = (int64_t)s->r_out.size();
+    if (!peaks) return SS_OK;
+    if (cap_regions < *n_out) return fail(c, SS_ERR_CAPACITY, "ss_stream_region_peaks: capacity < " + std::to_string(*n_out) + " regions");
+    if (!s->p_out.empty()) memcpy(peaks, s->p_out.data(), s->p_out.size() * 8);
+    return SS_OK;
+}
+
 extern "C" int ss_stream_output(ss_ctx* c, int id, int16_t* out, int64_t cap_frames, int64_t* first_frame, int64_t* n_frames) {
     StreamRec* s = find_stream(c, id);
     if (!s || !first_frame || !n_frames) return fail(c, SS_ERR_ARG, "ss_stream_output: bad argument");
@@ -309,20 +354,46 @@ extern "C" int ss_stream_get_output_info(ss_ctx* c, int id, ss_stream_output_inf
 // the region walk over bins in order, one bin at a time: a run opens at a bin above the threshold and closes at the next covered bin
 // that is not; closed runs go through the stream's RunMerger.  A merged region is final once a covered bin lies more than brk after
 // its end (bin times never decrease, so no later run can merge into it).
-static void walk_bin(StreamRec& s, int64_t j, unsigned char f) {
+// An each-channel stream walks its merged flags, and beside them keeps every channel's peak (ss_stream_region_peaks): v[l vs] is lane l's
+// average of the bin (v == nullptr: a plain stream, which keeps none).  A region's peaks are the fmax over its covered bins from its first to its last one -- the runs, and the gaps
+// between them that the merger joined -- so the gap behind the last closed run is held apart until the next run decides whether it
+// belongs.  fmax of doubles is exact in any order: the values are ss_get_region_peaks' of the whole-file run.
+static void close_run(StreamRec& s) {
+    const bool had = s.mg.have;
+    const size_t n0 = s.r_out.size();
+    s.mg.add(s.run_first, s.run_last, s.r_out);
+    s.run_open = false;
+    if (s.lanes == 1) return;
+    const bool emitted = s.r_out.size() > n0;             // the run did not reach the pending region: that one is final
+    if (emitted) s.p_out.insert(s.p_out.end(), s.pk_cur.begin(), s.pk_cur.end());
+    for (int l = 0; l < s.lanes; ++l) {
+        s.pk_cur[l] = had && !emitted ? std::fmax(std::fmax(s.pk_cur[l], s.pk_gap[l]), s.pk_run[l]) : s.pk_run[l];
+        s.pk_run[l] = s.pk_gap[l] = -HUGE_VAL;
+    }
+}
+
+static void flush_merged(StreamRec& s) {
+    const size_t n0 = s.r_out.size();
+    s.mg.flush(s.r_out);
+    if (s.lanes > 1 && s.r_out.size() > n0) s.p_out.insert(s.p_out.end(), s.pk_cur.begin(), s.pk_cur.end());
+}
+
+static void walk_bin(StreamRec& s, int64_t j, unsigned char f, const double* v, int64_t vs) {
     if (!(f & 1)) return;                                 // not covered: absent from the reference's series
     if (f & 2) {
         if (!s.run_open) { s.run_open = true; s.run_first = j; }
         s.run_last = j;
+        if (v) for (int l = 0; l < s.lanes; ++l) s.pk_run[l] = std::fmax(s.pk_run[l], v[l * vs]);
         return;
     }
-    if (s.run_open) { s.mg.add(s.run_first, s.run_last, s.r_out); s.run_open = false; }
-    if (s.mg.have && bin_time(j) - s.mg.cur.end > s.mg.brk) s.mg.flush(s.r_out);
+    if (s.run_open) close_run(s);
+    if (v) for (int l = 0; l < s.lanes; ++l) s.pk_gap[l] = std::fmax(s.pk_gap[l], v[l * vs]);
+    if (s.mg.have && bin_time(j) - s.mg.cur.end > s.mg.brk) flush_merged(s);
 }
 
 static void finish_regions(StreamRec& s) {
-    if (s.run_open) { s.mg.add(s.run_first, s.run_last, s.r_out); s.run_open = false; }
-    s.mg.flush(s.r_out);
+    if (s.run_open) close_run(s);
+    flush_merged(s);
 }
 
 static int ensure_pinned(ss_ctx* c, unsigned char** p, size_t* cap, size_t need) {
@@ -482,34 +553,40 @@ extern "C" int ss_stream_step(ss_ctx* c) {
     const int nxt = S.cur ^ 1;
     float* cur_arena = S.arena[S.cur];
     auto al = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
-    int64_t arena_need = 0, up_bytes = 0, total_w = 0, total_b = 0;
+    int64_t arena_need = 0, up_bytes = 0, total_w = 0, total_b = 0, n_lanes = 0, n_each = 0;
     double avg_reads = 0;                                   // logits the averaging reads: 256 / s_b windows per bin
     for (auto& [sp, p] : act) {
         const StreamRec& s = *sp;
-        if (s.sr != SS_SAMPLE_RATE) { p.mono_off = arena_need; arena_need = al(arena_need + p.mono_len(), 64); }
-        p.sig_off = arena_need; arena_need = al(arena_need + p.sig_len() + 64, 64);    // (+ 64: slack behind the last window, as the file arena)
-        p.lg_off = arena_need; arena_need = al(arena_need + (p.i_end - p.lw0) * 256, 64);
+        // (arena_need stays a multiple of 64; a plain stream has one lane)
+        if (s.sr != SS_SAMPLE_RATE) { p.mono_off = arena_need; p.mono_ls = al(p.mono_len(), 64); arena_need += s.lanes * p.mono_ls; }
+        p.sig_off = arena_need; p.sig_ls = al(p.sig_len() + 64, 64); arena_need += s.lanes * p.sig_ls;    // (+ 64: slack behind the last window, as the file arena)
+        p.lg_off = arena_need; p.lg_ls = al((p.i_end - p.lw0) * 256, 64); arena_need += s.lanes * p.lg_ls;
         p.up_off = up_bytes; up_bytes = al(up_bytes + (int64_t)s.staged.size(), 16);
         p.host_off = up_bytes;
         if (s.on_host) up_bytes = al(up_bytes + 4 * (int64_t)(s.h_mono.size() + s.h_sig.size() + s.h_lg.size()), 16);
         p.raw_up_off = up_bytes;
         if (s.on_host && s.out_on) up_bytes = al(up_bytes + (int64_t)s.h_raw.size(), 16);
-        total_w += p.i_end - s.win_run;
-        total_b += p.b_end - s.bins_done;
+        total_w += s.lanes * (p.i_end - s.win_run);
+        total_b += (s.lanes > 1 ? s.lanes + 1 : 1) * (p.b_end - s.bins_done);      // every lane's bins, then the merged ones
+        n_lanes += s.lanes; n_each += s.lanes > 1;
     }
     std::vector<StreamCopy> pre, post;
     std::vector<StreamDecode> dec;
+    std::vector<StreamDecodeChannels> decc;                 // each-channel streams only: a step without one launches neither kernel
+    std::vector<StreamUnion> uni;
     std::vector<StreamResample> res;
     std::vector<StreamAvg> avg;
     std::vector<int64_t> winoff;
-    int64_t max_copy = 0, max_dec = 0, max_res = 0, max_bins = 0;
+    int64_t max_copy = 0, max_dec = 0, max_decc = 0, max_res = 0, max_bins = 0, max_uni = 0;
+    double decc_bytes = 0, uni_bytes = 0;
     if ((rc = ensure(c, &S.arena[nxt], &S.arena_cap[nxt], (size_t)std::max<int64_t>(arena_need, 64)))) return rc;
     float* A = S.arena[nxt];
     const size_t desc_off = (size_t)al(up_bytes, 64);
     // descriptors behind the data (they hold device addresses of the upload's copy, so its buffer is sized first): at most 5 copies
-    // before the passes, one after, one decode, one resample, one averaging per stream, the window offsets, 64-byte alignment of each
-    const size_t n_desc_bytes = act.size() * (6 * sizeof(StreamCopy) + sizeof(StreamDecode) + sizeof(StreamResample) + sizeof(StreamAvg)) +
-                                (size_t)total_w * 8 + 6 * 64;
+    // before the passes, one after, one resample, one averaging per lane, one decode (and one merge) per stream, the window offsets,
+    // 64-byte alignment of each
+    const size_t n_desc_bytes = (size_t)n_lanes * (6 * sizeof(StreamCopy) + sizeof(StreamResample) + sizeof(StreamAvg)) + act.size() * sizeof(StreamDecode) +
+                                (size_t)n_each * (sizeof(StreamDecodeChannels) + sizeof(StreamUnion)) + (size_t)total_w * 8 + 8 * 64;
     const size_t up_total = desc_off + n_desc_bytes;
     if ((rc = ensure(c, &S.d_up, &S.up_cap, up_total))) return rc;
     if ((rc = ensure_pinned(c, &S.h_up, &S.h_up_cap, up_total))) return rc;
@@ -534,41 +611,60 @@ extern "C" int ss_stream_step(ss_ctx* c) {
             hm = cur_arena + s.mono_off; hs = cur_arena + s.sig_off; hl = cur_arena + s.lg_off;
         }
         const bool direct = s.sr == SS_SAMPLE_RATE;
-        // carried mono history [kb, frames_in), then the new frames
-        if (!direct && p.mono_keep > 0) {
-            pre.push_back(StreamCopy{hm + (p.kb - s.mono_base), A + p.mono_off, p.mono_keep});
-            max_copy = std::max(max_copy, p.mono_keep);
+        // lane l's carried segments, and its segments in the next half
+        const int64_t src_mono_ls = s.on_host ? s.mono_n : s.mono_ls, src_sig_ls = s.on_host ? s.sig_n : s.sig_ls,
+                      src_lg_ls = s.on_host ? s.lg_n * 256 : s.lg_ls;
+        const int64_t n_new_out = p.m_end - s.m_next, nw = p.i_end - s.win_run, nb = p.b_end - s.bins_done;
+        for (int l = 0; l < s.lanes; ++l) {
+            const float* hm_l = hm + l * src_mono_ls; const float* hs_l = hs + l * src_sig_ls; const float* hl_l = hl + l * src_lg_ls;
+            float* Am = A + p.mono_off + l * p.mono_ls; float* As = A + p.sig_off + l * p.sig_ls; float* Al = A + p.lg_off + l * p.lg_ls;
+            // carried mono history [kb, frames_in), then the new frames
+            if (!direct && p.mono_keep > 0) {
+                pre.push_back(StreamCopy{hm_l + (p.kb - s.mono_base), Am, p.mono_keep});
+                max_copy = std::max(max_copy, p.mono_keep);
+            }
+            // signal: carried [base_new, sig_end), the leading zeros of a new stream, outputs, the trailing zeros at close
+            if (p.sig_keep > 0) { pre.push_back(StreamCopy{hs_l + (p.base_new - s.sig_base), As, p.sig_keep}); max_copy = std::max(max_copy, p.sig_keep); }
+            if (p.pre > 0) { pre.push_back(StreamCopy{nullptr, As + p.sig_keep, p.pre}); max_copy = std::max(max_copy, p.pre); }
+            float* out0 = As + p.sig_keep + p.pre;              // = padded index kPad + m_next
+            pre.push_back(StreamCopy{nullptr, out0 + n_new_out, p.post + 64});      // (+ 64: the slack behind the signal is zero, as in the file arena)
+            max_copy = std::max(max_copy, p.post + 64);
+            // logits carried [lw0, win_run)
+            if (s.lg_n > 0) { pre.push_back(StreamCopy{hl_l, Al, s.lg_n * 256}); max_copy = std::max(max_copy, s.lg_n * 256); }
+            if (s.staged_frames > 0 && l == 0) {
+                float* dst = direct ? out0 : Am + p.mono_keep;
+                if (s.lanes == 1) {
+                    dec.push_back(StreamDecode{(int64_t)p.up_off, s.staged_frames, dst, s.format, s.ch});
+                    max_dec = std::max(max_dec, s.staged_frames);
+                } else {                                         // every lane's plane from the one reading of the frames
+                    decc.push_back(StreamDecodeChannels{(int64_t)p.up_off, s.staged_frames, dst, direct ? p.sig_ls : p.mono_ls, s.format, s.ch});
+                    max_decc = std::max(max_decc, s.staged_frames);
+                    decc_bytes += (double)s.staged.size() + 4.0 * (double)(s.staged_frames * s.lanes);
+                }
+            }
+            if (!direct && n_new_out > 0) {
+                res.push_back(StreamResample{Am, p.kb, p.F, s.d_taps, out0, s.m_next, n_new_out, s.L, s.M, s.half, 0});
+                max_res = std::max(max_res, n_new_out);
+            }
+            // windows [win_run, i_end): arena offsets, their logits behind the carried ones
+            for (int64_t i = s.win_run; i < p.i_end; ++i) winoff.push_back(p.sig_off + l * p.sig_ls + (i * s.per_step - p.base_new));
+            if (nw > 0) post.push_back(StreamCopy{S.d_newlg + (size_t)w_at * 256, Al + (s.win_run - p.lw0) * 256, nw * 256});
+            w_at += nw;
+            if (nb > 0) {
+                avg.push_back(StreamAvg{Al, p.lw0, p.W_avg, 0, s.bins_done, nb, b_at, s.thr, s.step, step_bins(s.step)});
+                max_bins = std::max(max_bins, nb);
+                avg_reads += (double)nb * 256.0 / step_bins(s.step);
+            }
+            b_at += nb;
         }
-        // signal: carried [base_new, sig_end), the leading zeros of a new stream, outputs, the trailing zeros at close
-        if (p.sig_keep > 0) { pre.push_back(StreamCopy{hs + (p.base_new - s.sig_base), A + p.sig_off, p.sig_keep}); max_copy = std::max(max_copy, p.sig_keep); }
-        if (p.pre > 0) { pre.push_back(StreamCopy{nullptr, A + p.sig_off + p.sig_keep, p.pre}); max_copy = std::max(max_copy, p.pre); }
-        float* out0 = A + p.sig_off + p.sig_keep + p.pre;   // = padded index kPad + m_next
-        const int64_t n_new_out = p.m_end - s.m_next;
-        pre.push_back(StreamCopy{nullptr, out0 + n_new_out, p.post + 64});      // (+ 64: the slack behind the signal is zero, as in the file arena)
-        max_copy = std::max(max_copy, p.post + 64);
-        // logits carried [lw0, win_run)
-        if (s.lg_n > 0) { pre.push_back(StreamCopy{hl, A + p.lg_off, s.lg_n * 256}); max_copy = std::max(max_copy, s.lg_n * 256); }
-        if (s.staged_frames > 0) {
-            float* dst = direct ? out0 : A + p.mono_off + p.mono_keep;
-            dec.push_back(StreamDecode{(int64_t)p.up_off, s.staged_frames, dst, s.format, s.ch});
-            max_dec = std::max(max_dec, s.staged_frames);
+        if (s.lanes > 1) {                                       // the merged bins behind the lanes'
+            if (nb > 0) {
+                uni.push_back(StreamUnion{b_at - s.lanes * nb, nb, b_at, s.lanes, 0});
+                max_uni = std::max(max_uni, nb);
+                uni_bytes += 9.0 * (double)(nb * (s.lanes + 1));
+            }
+            b_at += nb;
         }
-        if (!direct && n_new_out > 0) {
-            res.push_back(StreamResample{A + p.mono_off, p.kb, p.F, s.d_taps, out0, s.m_next, n_new_out, s.L, s.M, s.half, 0});
-            max_res = std::max(max_res, n_new_out);
-        }
-        // windows [win_run, i_end): arena offsets, their logits behind the carried ones
-        const int64_t nw = p.i_end - s.win_run;
-        for (int64_t i = s.win_run; i < p.i_end; ++i) winoff.push_back(p.sig_off + (i * s.per_step - p.base_new));
-        if (nw > 0) post.push_back(StreamCopy{S.d_newlg + (size_t)w_at * 256, A + p.lg_off + (s.win_run - p.lw0) * 256, nw * 256});
-        w_at += nw;
-        const int64_t nb = p.b_end - s.bins_done;
-        if (nb > 0) {
-            avg.push_back(StreamAvg{A + p.lg_off, p.lw0, p.W_avg, 0, s.bins_done, nb, b_at, s.thr, s.step, step_bins(s.step)});
-            max_bins = std::max(max_bins, nb);
-            avg_reads += (double)nb * 256.0 / step_bins(s.step);
-        }
-        b_at += nb;
     }
     // pack the descriptors behind the data
     size_t at = desc_off;
@@ -579,6 +675,8 @@ extern "C" int ss_stream_step(ss_ctx* c) {
     const size_t o_res = put(res.data(), res.size() * sizeof(StreamResample));
     const size_t o_avg = put(avg.data(), avg.size() * sizeof(StreamAvg));
     const size_t o_win = put(winoff.data(), winoff.size() * 8);
+    const size_t o_decc = put(decc.data(), decc.size() * sizeof(StreamDecodeChannels));     // (nothing, and no bytes, without an each-channel stream)
+    const size_t o_uni = put(uni.data(), uni.size() * sizeof(StreamUnion));
     if (at > up_total) return fail(c, SS_ERR_STATE, "ss_stream_step: upload layout overflow");   // (cannot happen: sized above)
     // ---- device work ----
     HIPCHK(c, hipMemcpyAsync(S.d_up, S.h_up, at, hipMemcpyHostToDevice, c->stream));
@@ -589,6 +687,10 @@ extern "C" int ss_stream_step(ss_ctx* c) {
     {
         ScopedLaunch sl(c, c->stream, "stream_decode", 0.0, 0.0);
         HIPCHK(c, launch_stream_decode(S.d_up, (const StreamDecode*)(S.d_up + o_dec), (int)dec.size(), max_dec, c->stream));
+    }
+    if (!decc.empty()) {
+        ScopedLaunch sl(c, c->stream, "stream_decode_channels", 0.0, decc_bytes);
+        HIPCHK(c, launch_stream_decode_channels(S.d_up, (const StreamDecodeChannels*)(S.d_up + o_decc), (int)decc.size(), max_decc, c->stream));
     }
     {
         ScopedLaunch sl(c, c->stream, "stream_resample", 0.0, 0.0);
@@ -615,6 +717,10 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         ScopedLaunch sl(c, c->stream, "stream_average", 0.0, avg_reads * 4 + (double)total_b * 9);
         HIPCHK(c, launch_stream_average((const StreamAvg*)(S.d_up + o_avg), (int)avg.size(), max_bins, S.d_avg, S.d_flags, c->stream));
     }
+    if (!uni.empty()) {
+        ScopedLaunch sl(c, c->stream, "stream_union", 0.0, uni_bytes);
+        HIPCHK(c, launch_stream_union((const StreamUnion*)(S.d_up + o_uni), (int)uni.size(), max_uni, S.d_avg, S.d_flags, c->stream));
+    }
     S.h_avg.resize((size_t)total_b); S.h_flags.resize((size_t)total_b);
     if (total_b) {
         HIPCHK(c, hipMemcpyAsync(S.h_avg.data(), S.d_avg, (size_t)total_b * 8, hipMemcpyDeviceToHost, c->stream));
@@ -627,18 +733,29 @@ extern "C" int ss_stream_step(ss_ctx* c) {
         return fail(c, SS_ERR_RANGE, "f16x2: an activation left the f16 range (|x| > 65504) or was not finite; nothing of the step is committed: "
                                      "move the streams that had windows in it to an fp32 context (ss_stream_export / ss_stream_import)");
     // ---- commit ----
-    for (auto& kv : S.s) { kv.second.r_out.clear(); kv.second.a_out.clear(); kv.second.b_out.clear(); kv.second.o_first = kv.second.frames_out; kv.second.o_n = 0; }
+    for (auto& kv : S.s) {
+        StreamRec& s = kv.second;
+        s.r_out.clear(); s.a_out.clear(); s.b_out.clear(); s.la_out.clear(); s.p_out.clear(); s.o_first = s.frames_out; s.o_n = 0;
+    }
     b_at = 0;
     for (auto& [sp, p] : act) {
         StreamRec& s = *sp;
         const int64_t nb = p.b_end - s.bins_done;
+        // a plain stream's bins; an each-channel stream's lanes, then its merged bins: the series it returns and walks
+        const int64_t m_at = b_at + (s.lanes > 1 ? s.lanes * nb : 0);
+        const double* lane_avg = s.lanes > 1 ? S.h_avg.data() + b_at : nullptr;
         for (int64_t k = 0; k < nb; ++k) {
             const int64_t j = s.bins_done + k;
-            const unsigned char f = S.h_flags[(size_t)(b_at + k)];
-            if (f & 1) { s.a_out.push_back(S.h_avg[(size_t)(b_at + k)]); s.b_out.push_back(j); }
-            walk_bin(s, j, f);
+            const unsigned char f = S.h_flags[(size_t)(m_at + k)];
+            if (f & 1) { s.a_out.push_back(S.h_avg[(size_t)(m_at + k)]); s.b_out.push_back(j); }
+            walk_bin(s, j, f, lane_avg ? lane_avg + k : nullptr, nb);
         }
-        b_at += nb;
+        if (s.lanes > 1)
+            for (int l = 0; l < s.lanes; ++l)
+                for (int64_t k = 0; k < nb; ++k)
+                    if (S.h_flags[(size_t)(m_at + k)] & 1) s.la_out.push_back(S.h_avg[(size_t)(b_at + l * nb + k)]);
+        b_at = m_at + nb;
+        s.mono_ls = p.mono_ls; s.sig_ls = p.sig_ls; s.lg_ls = p.lg_ls;
         const bool direct = s.sr == SS_SAMPLE_RATE;
         const int64_t sig_end = p.base_new + p.sig_len();
         s.frames_in = p.F; s.m_next = p.m_end; s.win_run = p.i_end; s.bins_done = p.b_end;
@@ -681,20 +798,28 @@ constexpr char kMagicStep[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '2'};
 // the floats, then the held raw PCM (raw_bytes: frames [frames_out, frames_in) in the stream's encoding)
 constexpr char kMagicOut[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '3'};
 struct ImageOut { double pad_s, min_len_s; int64_t frames_out, erased, raw_bytes, n_er; };
+// "SSSTRM04": an each-channel stream of several channels -- the header, the step, ImageLanes, the peak state (3 x lanes doubles: open
+// run, pending region, gap), then with_out ? the output block of "SSSTRM03" (ImageOut, the ranges) : nothing, the staged bytes, the
+// floats (every lane's mono history, then every lane's signal, then every lane's logits), then the held raw PCM of a stream with output
+constexpr char kMagicLanes[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '4'};
+struct ImageLanes { int32_t lanes, with_out; };
 }  // namespace
 
 extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64_t* n_out) {
     StreamRec* s = find_stream(c, id);
     if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_export: bad argument");
-    const bool with_step = s->out_on || s->step != SS_STEP_DEFAULT;
+    const bool each = s->lanes > 1;
+    const bool with_step = each || s->out_on || s->step != SS_STEP_DEFAULT;
     const int64_t raw_bytes = s->out_on ? (s->frames_in - s->frames_out) * s->frame_bytes() : 0;
-    const int64_t need = (int64_t)sizeof(ImageHdr) + (with_step ? 8 : 0) + (int64_t)s->staged.size() + 4 * (s->mono_n + s->sig_n + s->lg_n * 256) +
+    const int64_t nl = s->lanes;
+    const int64_t need = (int64_t)sizeof(ImageHdr) + (with_step ? 8 : 0) + (each ? (int64_t)sizeof(ImageLanes) + 24 * nl : 0) + (int64_t)s->staged.size() +
+                         4 * nl * (s->mono_n + s->sig_n + s->lg_n * 256) +
                          (s->out_on ? (int64_t)sizeof(ImageOut) + 8 * (int64_t)s->er_rng.size() + raw_bytes : 0);
     *n_out = need;
     if (!buf) return SS_OK;
     if (cap < need) return fail(c, SS_ERR_CAPACITY, "ss_stream_export: capacity < " + std::to_string(need));
     ImageHdr h{};
-    memcpy(h.magic, s->out_on ? kMagicOut : with_step ? kMagicStep : kMagic, 8);
+    memcpy(h.magic, each ? kMagicLanes : s->out_on ? kMagicOut : with_step ? kMagicStep : kMagic, 8);
     h.format = s->format; h.sr = s->sr; h.ch = s->ch; h.closed = s->closed; h.finished = s->finished; h.have = s->mg.have; h.run_open = s->run_open;
     h.thr = s->thr; h.brk = s->mg.brk; h.cur_start = s->mg.cur.start; h.cur_end = s->mg.cur.end;
     h.frames_in = s->frames_in; h.staged_frames = s->staged_frames; h.staged_bytes = (int64_t)s->staged.size();
@@ -703,6 +828,11 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     unsigned char* o = (unsigned char*)buf;
     memcpy(o, &h, sizeof h); o += sizeof h;
     if (with_step) { memcpy(o, &s->step, 8); o += 8; }
+    if (each) {
+        const ImageLanes il{s->lanes, s->out_on ? 1 : 0};
+        memcpy(o, &il, sizeof il); o += sizeof il;
+        for (const std::vector<double>* v : {&s->pk_run, &s->pk_cur, &s->pk_gap}) { memcpy(o, v->data(), 8 * nl); o += 8 * nl; }
+    }
     if (s->out_on) {
         const ImageOut io{s->er.pad_s, s->er.min_len_s, s->frames_out, s->erased, raw_bytes, (int64_t)s->er_rng.size()};
         memcpy(o, &io, sizeof io); o += sizeof io;
@@ -712,19 +842,22 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     if (!s->staged.empty()) memcpy(o, s->staged.data(), s->staged.size());
     o += s->staged.size();
     float* f = (float*)o;                                 // (unaligned host memory is fine for memcpy / hipMemcpy)
-    unsigned char* raw = o + 4 * (s->mono_n + s->sig_n + s->lg_n * 256);
+    unsigned char* raw = o + 4 * nl * (s->mono_n + s->sig_n + s->lg_n * 256);
+    float* f_sig = f + nl * s->mono_n; float* f_lg = f_sig + nl * s->sig_n;       // the lanes back to back, as the host vectors hold them
     if (s->on_host) {
-        memcpy(f, s->h_mono.data(), s->mono_n * 4); memcpy(f + s->mono_n, s->h_sig.data(), s->sig_n * 4);
-        memcpy(f + s->mono_n + s->sig_n, s->h_lg.data(), s->lg_n * 1024);
+        memcpy(f, s->h_mono.data(), nl * s->mono_n * 4); memcpy(f_sig, s->h_sig.data(), nl * s->sig_n * 4);
+        memcpy(f_lg, s->h_lg.data(), nl * s->lg_n * 1024);
         if (raw_bytes) memcpy(raw, s->h_raw.data(), (size_t)raw_bytes);
         return SS_OK;
     }
     hipSetDevice(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const float* a = c->streams->arena[c->streams->cur];
-    if (s->mono_n) HIPCHK(c, hipMemcpy(f, a + s->mono_off, s->mono_n * 4, hipMemcpyDeviceToHost));
-    if (s->sig_n) HIPCHK(c, hipMemcpy(f + s->mono_n, a + s->sig_off, s->sig_n * 4, hipMemcpyDeviceToHost));
-    if (s->lg_n) HIPCHK(c, hipMemcpy(f + s->mono_n + s->sig_n, a + s->lg_off, s->lg_n * 1024, hipMemcpyDeviceToHost));
+    for (int64_t l = 0; l < nl; ++l) {
+        if (s->mono_n) HIPCHK(c, hipMemcpy(f + l * s->mono_n, a + s->mono_off + l * s->mono_ls, s->mono_n * 4, hipMemcpyDeviceToHost));
+        if (s->sig_n) HIPCHK(c, hipMemcpy(f_sig + l * s->sig_n, a + s->sig_off + l * s->sig_ls, s->sig_n * 4, hipMemcpyDeviceToHost));
+        if (s->lg_n) HIPCHK(c, hipMemcpy(f_lg + l * s->lg_n * 256, a + s->lg_off + l * s->lg_ls, s->lg_n * 1024, hipMemcpyDeviceToHost));
+    }
     if (raw_bytes) HIPCHK(c, hipMemcpy(raw, c->streams->barena[c->streams->bcur] + s->raw_off, (size_t)raw_bytes, hipMemcpyDeviceToHost));
     return SS_OK;
 }
@@ -735,11 +868,29 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
     ImageHdr h;
     memcpy(&h, buf, sizeof h);
     static const unsigned char one[8] = {0};
-    const bool with_out = memcmp(h.magic, kMagicOut, 8) == 0;
-    const bool with_step = with_out || memcmp(h.magic, kMagicStep, 8) == 0;
+    // an "SSSTRM04" image that does not hold together is an argument error (SS_ERR_ARG); the older images keep SS_ERR_FORMAT
+    const bool each = memcmp(h.magic, kMagicLanes, 8) == 0;
+    const int bad = each ? SS_ERR_ARG : SS_ERR_FORMAT;
+    bool with_out = memcmp(h.magic, kMagicOut, 8) == 0;
+    const bool with_step = each || with_out || memcmp(h.magic, kMagicStep, 8) == 0;
     int64_t hdr_bytes = (int64_t)sizeof h;
     double step = SS_STEP_DEFAULT;
     if (with_step && n >= hdr_bytes + 8) { memcpy(&step, (const unsigned char*)buf + hdr_bytes, 8); hdr_bytes += 8; }
+    ImageLanes il{1, 0};
+    int64_t pk_at = 0;                                    // the peak state's place in the image
+    if (each) {
+        bool ok = hdr_bytes == (int64_t)sizeof h + 8 && n >= hdr_bytes + (int64_t)sizeof il;
+        if (ok) {
+            memcpy(&il, (const unsigned char*)buf + hdr_bytes, sizeof il);
+            ok = il.lanes >= 1 && (il.lanes == 1 || il.lanes == h.ch) && il.lanes <= 64 && (il.with_out == 0 || il.with_out == 1) &&
+                 n >= hdr_bytes + (int64_t)sizeof il + 24 * (int64_t)il.lanes;
+        }
+        if (!ok) return fail(c, SS_ERR_ARG, "ss_stream_import: an each-channel image whose lane count is neither 1 nor its channel count, or cut short");
+        pk_at = hdr_bytes + (int64_t)sizeof il;
+        hdr_bytes = pk_at + 24 * (int64_t)il.lanes;
+        with_out = il.with_out != 0;
+    }
+    const int64_t nl = il.lanes;
     ImageOut io{0, 0, 0, 0, 0, 0};
     int64_t out_bytes = 0;                                // what an image with output holds beyond the others: ImageOut, the ranges, the raw PCM
     if (with_out) {
@@ -750,16 +901,16 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
             ok = erase_ok(&e) && io.n_er >= 0 && io.n_er <= ((int64_t)1 << 24) && io.n_er % 2 == 0 && io.frames_out >= 0 && io.frames_out <= h.frames_in &&
                  io.erased >= 0 && io.erased <= io.frames_out && h.ch > 0 && h.ch <= 64 && io.raw_bytes >= 0 && io.raw_bytes <= n;
         }
-        if (!ok) return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
+        if (!ok) return fail(c, bad, "ss_stream_import: not a stream image");
         hdr_bytes += (int64_t)sizeof io + 8 * io.n_er;
         out_bytes = io.raw_bytes;
     }
     if ((memcmp(h.magic, kMagic, 8) != 0 && !(with_step && hdr_bytes > (int64_t)sizeof h && step_ok(step))) || check_pcm_args(c, one, h.format, h.sr, h.ch, 0) != SS_OK || h.staged_bytes < 0 || h.mono_n < 0 ||
         h.sig_n < 0 || h.lg_n < 0 || h.lg_n > 64 || h.mono_n > ((int64_t)1 << 32) || h.sig_n > ((int64_t)1 << 32) ||
-        n != hdr_bytes + h.staged_bytes + 4 * (h.mono_n + h.sig_n + h.lg_n * 256) + out_bytes ||
+        n != hdr_bytes + h.staged_bytes + 4 * nl * (h.mono_n + h.sig_n + h.lg_n * 256) + out_bytes ||
         (with_out && io.raw_bytes != (h.frames_in - io.frames_out) * h.ch * (int64_t)pcm_bytes_per_sample(h.format)) ||
         h.staged_bytes != h.staged_frames * h.ch * (int64_t)pcm_bytes_per_sample(h.format))
-        return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
+        return fail(c, bad, "ss_stream_import: not a stream image");
     hipSetDevice(c->device);
     StreamRec s;
     s.format = h.format; s.sr = h.sr; s.ch = h.ch; s.closed = h.closed; s.finished = h.finished; s.mg.have = h.have; s.run_open = h.run_open;
@@ -772,10 +923,13 @@ extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) 
     if (rc) return rc;
     const unsigned char* p = (const unsigned char*)buf + hdr_bytes;
     s.staged.assign(p, p + h.staged_bytes); p += h.staged_bytes;
-    s.h_mono.resize(h.mono_n); s.h_sig.resize(h.sig_n); s.h_lg.resize(h.lg_n * 256);
-    memcpy(s.h_mono.data(), p, h.mono_n * 4); p += h.mono_n * 4;
-    memcpy(s.h_sig.data(), p, h.sig_n * 4); p += h.sig_n * 4;
-    memcpy(s.h_lg.data(), p, h.lg_n * 1024); p += h.lg_n * 1024;
+    s.set_lanes((int)nl);
+    if (nl > 1)
+        for (std::vector<double>* v : {&s.pk_run, &s.pk_cur, &s.pk_gap}) { memcpy(v->data(), (const unsigned char*)buf + pk_at, 8 * nl); pk_at += 8 * nl; }
+    s.h_mono.resize(nl * h.mono_n); s.h_sig.resize(nl * h.sig_n); s.h_lg.resize(nl * h.lg_n * 256);
+    memcpy(s.h_mono.data(), p, nl * h.mono_n * 4); p += nl * h.mono_n * 4;
+    memcpy(s.h_sig.data(), p, nl * h.sig_n * 4); p += nl * h.sig_n * 4;
+    memcpy(s.h_lg.data(), p, nl * h.lg_n * 1024); p += nl * h.lg_n * 1024;
     if (with_out) {
         s.out_on = true; s.er = ss_stream_erase{io.pad_s, io.min_len_s}; s.frames_out = io.frames_out; s.erased = io.erased;
         const unsigned char* q = (const unsigned char*)buf + hdr_bytes - 8 * io.n_er;

@@ -166,6 +166,9 @@ _SIGS = {
     "ss_stream_open_output": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.POINTER(C.c_int)]),
     "ss_stream_output": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ss_stream_get_output_info": (C.c_int, [_P, C.c_int, C.POINTER(StreamOutputInfo)]),
+    "ss_stream_open_channels": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.POINTER(C.c_int)]),
+    "ss_stream_avg_channel": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_region_peaks": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
@@ -744,6 +747,36 @@ class Context:
         e = _erase(erase)
         self._ck(lib().ss_stream_open_output(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s), C.byref(e), C.byref(sid)))
         return sid.value
+
+    def stream_open_channels(self, fmt: int, sr: int, channels: int, threshold: float = 0.1, break_s: float = 0.5, erase=None,
+                             with_output: bool = False) -> int:
+        """A stream whose channels are detected each alone (one lane per channel, one merged table: stream_regions / stream_avg give
+        "speech on any channel", stream_avg_channel a channel's own series, stream_region_peaks the channels' peaks per region).
+        erase None and with_output False: detection only; otherwise a stream with output, erase as stream_open_output's."""
+        sid = C.c_int(-1)
+        e = _erase(erase)
+        self._ck(lib().ss_stream_open_channels(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s),
+                                               C.byref(e) if erase is not None else None, int(bool(with_output)), C.byref(sid)))
+        return sid.value
+
+    def stream_avg_channel(self, sid: int, channel: int):
+        """stream_avg of one channel's lane of an each-channel stream (channel 0 of a mix stream: stream_avg)."""
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_avg_channel(self._h, int(sid), int(channel), None, None, 0, C.byref(n)))
+        a = np.empty(n.value, dtype=np.float64)
+        idx = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._ck(lib().ss_stream_avg_channel(self._h, int(sid), int(channel), _ptr(a), _ptr(idx), n.value, C.byref(n)))
+        return a, idx
+
+    def stream_region_peaks(self, sid: int, channels: int) -> np.ndarray:
+        """float64 [regions the last step returned, channels]: each channel's highest averaged score inside each of them."""
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_region_peaks(self._h, int(sid), None, 0, C.byref(n)))
+        out = np.empty((n.value, int(channels)), dtype=np.float64)
+        if n.value:
+            self._ck(lib().ss_stream_region_peaks(self._h, int(sid), _ptr(out), n.value, C.byref(n)))
+        return out
 
     def stream_output(self, sid: int, channels: int):
         """The frames the last step returned -> (first_frame, int16 array [n, channels])."""

@@ -14,6 +14,13 @@ A stream opened with erase= also returns its frames as final 16-bit PCM with the
     with StreamWavWriter("feed.wav", 48000, 2) as w:
         ...; s.push(samples); det.step(); w.write(s.output())      # (first_frame, int16 [n, channels]): contiguous from step to step
 
+A recording of several channels is detected on its channel mean by default; channel_mode="each" detects every channel alone (what
+native.Context.add_pcm_channels is to add_pcm) and the stream's table is "speech on any channel":
+
+    s = det.open(PCM_S16, 48000, 2, channel_mode="each")
+    ...; regions, merged, bin_idx = det.step()[s]       # merged: per bin the highest of the channels' scores
+    s.avg(1); s.peaks()                                 # channel 1's own series; [regions, channels] peaks of the step's regions
+
 The f16x2 mode reports SS_ERR_RANGE for a step whose passes met a value without an f16 representation (a NaN or Inf sample of a
 float stream), and commits nothing of it.  The rule of the drop-in (SpecUNet_2D.range_refused): the first such step says nothing about
 the checkpoint -- the streams that had windows in it move to an fp32 context of the same weights (ss_stream_export / import) and
@@ -31,10 +38,11 @@ from . import native as _native
 class Stream:
     """One recording of a StreamDetector.  Hashable: step() returns its results keyed by it."""
 
-    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None):
+    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None, channel_mode: str = "mix"):
         self._det, self._ctx, self._sid = det, ctx, sid
         self.format, self.sample_rate, self.channels = fmt, sr, channels
         self.erase = erase                                 # None: opened without output
+        self.channel_mode = channel_mode                   # "mix": the channel mean; "each": every channel alone, one merged table
 
     def push(self, pcm: np.ndarray):
         """Interleaved samples in the stream's encoding (int16 for PCM_S16, float32 for PCM_F32, raw bytes for 24-bit, ...)."""
@@ -47,6 +55,15 @@ class Stream:
 
     def info(self) -> dict:
         return self._ctx.stream_info(self._sid)
+
+    def avg(self, channel: int):
+        """(avg float64[n], bin_idx int64[n]) of one channel of an each-channel stream: what the last step made final on it."""
+        return self._ctx.stream_avg_channel(self._sid, channel)
+
+    def peaks(self) -> np.ndarray:
+        """float64 [regions the last step returned, channels]: each channel's highest score inside each region (each-channel streams of
+        more than one channel)."""
+        return self._ctx.stream_region_peaks(self._sid, self.channels)
 
     def output(self):
         """The frames the last step returned: (first_frame, int16 array [n, channels]) -- final, contiguous from step to step, the
@@ -91,16 +108,25 @@ class StreamDetector:
             self._fp32 = self._factory("fp32")
         return self._fp32
 
-    def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5, erase=None) -> Stream:
+    def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5, erase=None,
+             channel_mode: str = "mix") -> Stream:
         """erase: None -- detection only; dict(pad_s=, min_len_s=) (either may be left out: 0) -- the stream also returns its frames
-        as 16-bit PCM with the detected speech zeroed (Stream.output() after every step)."""
+        as 16-bit PCM with the detected speech zeroed (Stream.output() after every step).
+        channel_mode: "mix" -- detection on the channel mean; "each" -- on every channel alone: the regions and the series step()
+        returns are the merged ones ("speech on any channel"), every channel is zeroed over them, Stream.avg(c) / Stream.peaks() give
+        the channels' own."""
+        if channel_mode not in ("mix", "each"):
+            raise ValueError(f"channel_mode must be 'mix' or 'each', not {channel_mode!r}")
         ctx = self._fp32_ctx() if self._switched else self._main
-        if erase is None:
+        if erase is not None:
+            erase = dict(pad_s=float(erase.get("pad_s", 0.0)), min_len_s=float(erase.get("min_len_s", 0.0)))
+        if channel_mode == "each":
+            sid = ctx.stream_open_channels(fmt, sr, channels, threshold, break_s, erase)
+        elif erase is None:
             sid = ctx.stream_open(fmt, sr, channels, threshold, break_s)
         else:
-            erase = dict(pad_s=float(erase.get("pad_s", 0.0)), min_len_s=float(erase.get("min_len_s", 0.0)))
             sid = ctx.stream_open_output(fmt, sr, channels, threshold, break_s, erase)
-        s = Stream(self, ctx, sid, fmt, sr, channels, erase)
+        s = Stream(self, ctx, sid, fmt, sr, channels, erase, channel_mode)
         self._streams.append(s)
         return s
 
@@ -137,7 +163,8 @@ class StreamDetector:
                         self._move(s)
 
     def step(self) -> dict:
-        """One step over every stream -> {stream: (regions [(start, end)], avg float64[n], bin_idx int64[n])}: what became final."""
+        """One step over every stream -> {stream: (regions [(start, end)], avg float64[n], bin_idx int64[n])}: what became final (an
+        each-channel stream: its merged regions and merged series)."""
         if not self._switched:
             self._step_main()
         if self._fp32 is not None and self._fp32 is not self._main:
