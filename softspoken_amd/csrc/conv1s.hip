@@ -29,18 +29,14 @@
 // 512-thread block per CU (8 waves, 2 per SIMD, amdgpu_waves_per_eu(2, 2)), a wave takes units blockIdx * 8 + wave, + 8 * grid, ...;
 // TRACK = per-value f16 range test (false when weights.hip proved the range: ConvPlan::s1_range_proven); dynamic LDS 109 / 95 KB.
 #include "kernels.h"
-#include "mfma_util.h"
+#include "stream16.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace ss {
 
-static constexpr int kH = 128, kW = 256, kC = 32;
-static constexpr int kStrips = 9, kStripCols = 30;       // valid columns per strip: lanes 1 .. 30 of the 32-column tile
-static constexpr int kBank = 9 * 2 * 1024;               // one plane of the second conv's weights: [tap][K step][lane][16 B]
-static constexpr int kS1Waves = 8;                       // two waves per SIMD (twelve at 168 registers measured the same within the noise, and sat on the edge of spilling)
+// (the picture, the strips, the banks' size and the waves per block: stream16.h)
 static constexpr int kFPitch = 36;                       // floats per row of a wave's feature patch: columns x0 - 1 .. x0 + 32 (34) + 2 spare
-static constexpr int kMaxRows = 32;                      // most rows of a work unit (the patch holds rows y0 - 2 .. y0 + rows + 1)
 static constexpr int kFPatch = (kMaxRows + 5) * kFPitch; // floats per wave (+ one row that the last, unused look-ahead of a unit reads)
 
 // lane i <- lane i - 1 / lane i + 1 over the whole wavefront (lane 0 / 63: zero).  Lanes 0 and 32 (31 and 63) of the result belong to
@@ -393,17 +389,9 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 //     one on the same operand (its A is zero in the b_lo lanes).  8 products per row where the 32-column form issues 3 of twice the size.
 // Per row and wave: 8 + 4 + 108 products of 16 matrix cycles (1920; the other form 58 of 32 = 1856), about the same vector instructions
 // (operand building twice, no swaps, half the pooling).  Same numbers as the other form up to the summation order inside a product.
+// The second conv's core -- operand rows, the tap loop, the shifted combine, the split into 16-byte runs -- is stream16.h's, which
+// conv9s.hip runs as well.
 // =========================================================================================================
-struct S16Row { u32x4 f[2][2]; };                        // [pixel tile][plane: 0 = high halves, 1 = low halves]: the second conv's B operands
-
-__device__ __forceinline__ f32x4 s16_mfma(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ int s16_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true); }   // lane c <- lane c - 1 of its 16 (c = 0: 0)
-__device__ __forceinline__ int s16_shl1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x101, 0xf, 0xf, true); }   // lane c <- lane c + 1 (c = 15: 0)
-__device__ __forceinline__ float s16_shr1f(float v) { return __int_as_float(s16_shr1(__float_as_int(v))); }
-__device__ __forceinline__ float s16_shl1f(float v) { return __int_as_float(s16_shl1(__float_as_int(v))); }
-
 static constexpr int kFPatch16 = (kMaxRows + 6) * kFPitch;   // + a row of zeros (the odd lane groups' second feature row)
 
 template <bool TRACK>
@@ -568,17 +556,10 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             const float fc[2] = {fcen[0], fcen[1]};       // f(y, x) (requested with row y + 1's features)
             stamp(-1);
             // a group = one tap: both channel tiles' fragments (four 16-byte reads), requested one group ahead (a group's products: 192 cycles)
-            u32x4 wh[2][2], wl[2][2];                     // [ring slot][channel tile]
-            auto rd = [&](int tap) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    wh[tap & 1][u] = *(const u32x4*)(wl_base + (tap * 2 + u) * 1024);
-                    wl[tap & 1][u] = *(const u32x4*)(wl_base + kBank + (tap * 2 + u) * 1024);
-                }
-            };
+            S16Ring ring;
             const u32x4 kwl[2] = {*(const u32x4*)(sKl), *(const u32x4*)(sKl + 1024)};
             const u32x4 wrq[2] = {*(const u32x4*)(sKl + 2048), *(const u32x4*)(sKl + 3072)};
-            rd(0);
+            ring.rd(wl_base, 0);
             __builtin_amdgcn_sched_barrier(0);
             produce(y + 1, Hn, kwl);
             request(y + 2);
@@ -599,43 +580,19 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             }
             __builtin_amdgcn_sched_barrier(0);
             stamp(4);
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int dy = tap / 3, dx = tap % 3;
-                const S16Row& Hr = dy == 0 ? Ha : (dy == 1 ? Hb : Hn);
-                if (tap + 1 < 9) rd(tap + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                // the four result tiles (pixel tile x channel tile) take turns: a product's accumulator was last written four products earlier
-#pragma unroll
-                for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int t = 0; t < 2; ++t)
-                            P[dx][t][u] = s16_mfma(pr == 1 ? wl[tap & 1][u] : wh[tap & 1][u], Hr.f[t][pr == 0 ? 1 : 0], P[dx][t][u]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            s16_taps(ring, wl_base, Ha, Hb, Hn, P, [](int) {});
             stamp(0);
             // ---- out[x] = P_-1[x - 1] + P_0[x] + P_+1[x + 1], ReLU: tile 0's neighbours are tile 1's lanes c - 1 / c, tile 1's are tile 0's c / c + 1 ----
             float v[2][2][4];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[0][u][r] = relu_i(P[1][0][u][r] + s16_shr1f(P[0][1][u][r]) + P[2][1][u][r]);
-                    v[1][u][r] = relu_i(P[1][1][u][r] + P[0][0][u][r] + s16_shl1f(P[2][0][u][r]));
-                }
+            s16_combine(P, v);
             // a lane's eight values of a pixel tile are channels 8 g .. 8 g + 7 of its pixel: one 16-byte run per plane
             auto store_px = [&](const float (&val)[2][4], char* dst, bool on, auto track_c) {
                 constexpr bool track = TRACK && decltype(track_c)::value;
                 uint32_t kh[4], kl[4];
+                s16_split_px(val, kh, kl);
+                if (track) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float e0 = val[i >> 1][2 * (i & 1)], e1 = val[i >> 1][2 * (i & 1) + 1];
-                    kh[i] = pack_f16(e0, e1);
-                    if (track) ovf = pk_max_u16(ovf, kh[i]);
-                    kl[i] = split_lo(kh[i], e0, e1);
+                    for (int i = 0; i < 4; ++i) ovf = pk_max_u16(ovf, kh[i]);
                 }
                 if (on) {
                     *(u32x4*)(dst) = u32x4{kh[0], kh[1], kh[2], kh[3]};

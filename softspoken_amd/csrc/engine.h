@@ -64,7 +64,8 @@ struct ConvPlan {          // one launch of a ResBlock half
     bool s1_range_proven = false;                         // conv1s.hip: |h1| and |c1| bounded below the f16 limit by the weights alone (weights.hip)
     void* d_w_s1 = nullptr;                               // conv1s.hip: conv1_1's second conv, banks in the K order of the first conv's accumulator registers
     void* d_w_s16 = nullptr;                              // ... and for its 16-pixel form (v_mfma_f32_16x16x32_f16: natural K order, channel rows 8 g + 4 u + r)
-    void* d_w_upsr = nullptr;                             // conv4_ups.hip, ring form: the same for the A launch that also writes r (entries in walk order)
+    void* d_proj_s16 = nullptr;                           // conv9s.hip: conv9_1.B's projection as 16x16x32 A fragments (its 3 x 3 banks: d_w_s16)
+    void* d_w_upsr = nullptr;                           // conv4_ups.hip, ring form: the same for the A launch that also writes r (entries in walk order)
     void* d_w_ups32 = nullptr;                            // conv2_ups.hip (fp32): the A launch with the upsampled half at low resolution
     int ups32_nt = 1;                                     // ... packed for this many 32-channel tiles per block
     int Cout = 0, NT = 1, C0 = 0, C1 = 0, R0 = 0, R1 = 0, H = 0, W = 0;
@@ -136,6 +137,7 @@ struct ss_ctx {
     float2 *d_win2 = nullptr, *d_twt = nullptr, *d_wkt = nullptr; float* d_mel_wq = nullptr; int* d_mel_p0 = nullptr;   // second front-end kernel
     float *d_first_w = nullptr, *d_first_b = nullptr;
     float* d_flat_b = nullptr; void* d_flat_frag = nullptr; void* d_flat_frag4 = nullptr;
+    void* d_flat_rows = nullptr;                          // conv9s.hip: conv_flatten's filter per mel row as 16x16x32 A fragments (weights.hip pack_flat_rows)
     float *d_spec_w = nullptr, *d_spec_b = nullptr;
     ss::Head1dWeights head{};
     std::vector<ss::ConvPlan> convs;  // in launch order; pairs (A, B) per ResBlock, conv1_1 has only B

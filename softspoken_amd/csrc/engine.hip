@@ -169,7 +169,8 @@ static bool ensure_lane(ss_ctx* c, int n) {
 // ------------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------------
-struct ConvExtra { const float* first_w = nullptr; const float* first_b = nullptr; const void* flat_w = nullptr; const void* flat_w4 = nullptr; float* flat_part = nullptr; int store_out = 1; };
+struct ConvExtra { const float* first_w = nullptr; const float* first_b = nullptr; const void* flat_w = nullptr; const void* flat_w4 = nullptr; float* flat_part = nullptr; int store_out = 1;
+                   const void* flat_rows = nullptr; };
 
 static int base_dbg() {
     // product build: 32 (raised wave priority inside conv4.hip's MFMA loop: the measured default); dev build: + SOFTSPOKEN_DBG bits, and bit 9 =
@@ -356,6 +357,22 @@ static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const Co
     } else if ((rc = v4(pa, a, flops_a, bytes_a))) return rc;
     const double flops_b = 2.0 * px * pb.Cout * (9.0 * pb.Cout + cin) + (ex.flat_part ? 2.0 * px * 32 * 4 : 0.0);
     const double bytes_b = px * es * (pb.Cout + cinb + (ex.flat_part && !ex.store_out ? 0 : pb.Cout) + (pool ? pb.Cout / 4.0 : 0));
+    if (c->prec == kF16x2 && ex.flat_part && ex.flat_rows && pb.d_w_s16 && pb.d_proj_s16 && dev_env("SOFTSPOKEN_C9S", 1)) {
+        // conv9_1.B: the row-streaming form (conv9s.hip), in the mask-only pass and in the spec pass alike (store_out): the two passes'
+        // flatten sums are the same bits.  (Development build, SOFTSPOKEN_C9S=0: conv4.hip's form, below.)
+        ConvArgs bs = b;
+        bs.wpk = pb.d_w_s16; bs.proj_w = pb.d_proj_s16; bs.flat_w4 = ex.flat_rows;
+        const int rows = dev_env("SOFTSPOKEN_C9S_ROWS", 32);
+        if (conv9_stream_supports(bs) && conv9_stream_rows_ok(rows)) {
+            const int grid = dev_env("SOFTSPOKEN_C9S_GRID", 0);
+            // (FLOPs booked: the layer's algorithmic ones; issued: what the strips really multiply, their overlap columns included)
+            if ((rc = conv_launch(c, stream, conv9_stream_variant(), pb.name, bs, flops_b, bytes_b, conv9_stream_issued_macs(n),
+                                  [&](ConvArgs& y) { return launch_conv9_stream(y, rows, grid, cus, stream); })))
+                return rc;
+            ws.flat_groups = conv9_stream_flat_groups(rows);
+            return SS_OK;
+        }
+    }
     if ((rc = v4(pb, b, flops_b, bytes_b))) return rc;
     if (ex.flat_part) ws.flat_groups = conv_v4_flat_groups();
     return SS_OK;
@@ -421,6 +438,7 @@ static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const fl
     }
     {   // conv9_1 on cat[conv1, up(conv8)]; conv_flatten rides in B's epilogue (c9 itself only when the spec head runs)
         ConvExtra ex; ex.flat_w = c->d_flat_frag; ex.flat_w4 = c->d_flat_frag4; ex.flat_part = ws.flat; ex.store_out = d_spec ? 1 : 0;
+        ex.flat_rows = c->d_flat_rows;
         rc = 1;
         if (proj && (rc = run_block_proj(c, ws, stream, cv[i], cv[i + 1], n, A("c1"), A("c8"), A("h9"), A("c9"), nullptr, ex)) != 1) {
             if (rc) return rc;

@@ -204,6 +204,20 @@ size_t conv1_stream_weight_bytes();
 // v_mfma_f32_16x16x32_f16 (wpk: pack_conv_stream16; same size)
 hipError_t launch_conv1_stream(const ConvArgs& a, int form, int rows_per_unit, int num_cus, hipStream_t s);
 
+// conv9s.hip (f16x2): conv9_1.B as a row-streaming kernel on the same core (stream16.h) -- h9, c1 and c8 are read from memory as MFMA
+// operands, no patch image, no barrier after the prologue; conv_flatten in the epilogue, c9 written when store_out is set.  Fields as for
+// conv4.hip's projection-in-B FLAT launch, except: wpk = pack_conv_stream16's banks of the second conv, proj_w = pack_proj_stream16's
+// fragments (conv9_stream_proj_bytes), flat_w4 = pack_flat_rows' table (conv9_stream_flat_bytes).  flat_part receives
+// conv9_stream_flat_groups(rows_per_unit) row groups per window.  grid_override > 0: at most that many workgroups (development build).
+bool conv9_stream_supports(const ConvArgs& a);
+const char* conv9_stream_variant();
+size_t conv9_stream_proj_bytes();
+size_t conv9_stream_flat_bytes();
+bool conv9_stream_rows_ok(int rows_per_unit);        // even, divides 128, at most 32
+int conv9_stream_flat_groups(int rows_per_unit);
+double conv9_stream_issued_macs(int N);
+hipError_t launch_conv9_stream(const ConvArgs& a, int rows_per_unit, int grid_override, int num_cus, hipStream_t s);
+
 // heads.hip
 // ResBlock1D(4,4) + Conv1d(4,1,1) fed by the FLAT partial sums [N][n_parts][4][256]: sums them in order, adds conv_flatten's bias,
 // ReLU, then the 1-D head -> logits [N][256]

@@ -196,6 +196,42 @@ static void pack_conv_stream16(const Folded& w3, std::vector<char>& out, bool& r
                 }
 }
 
+// conv9s.hip: the block's 1 x 1 projection of cat[x0 (32 channels), up(x1) (32 channels)] for v_mfma_f32_16x16x32_f16, from the same
+// folded projection that d_proj is built from.  [source: x0, x1][channel tile u][plane: high, low halves][lane 64][8 values]: lane l is
+// output row i = l & 15 of tile u = channel 8 (i >> 2) + 4 u + (i & 3), value j is input channel 32 source + 8 (l >> 4) + j.
+static void pack_proj_stream16(const Folded& wr, std::vector<char>& out, bool& range_ok) {
+    out.assign((size_t)2 * 2 * 2 * 1024, 0);
+    for (int src = 0; src < 2; ++src)
+        for (int u = 0; u < 2; ++u)
+            for (int l = 0; l < 64; ++l)
+                for (int j = 0; j < 8; ++j) {
+                    const int i = l & 15, co = 8 * (i >> 2) + 4 * u + (i & 3), ci = 32 * src + 8 * (l >> 4) + j;
+                    const float v = wr.w[(size_t)co * wr.cin + ci];
+                    const uint16_t hi = f2h(v), lo = f2h(v - h2f(hi));
+                    if ((hi & 0x7c00u) == 0x7c00u) range_ok = false;
+                    const size_t off = ((size_t)((src * 2 + u) * 2) * 64 + l) * 16 + (size_t)j * 2;
+                    memcpy(&out[off], &hi, 2); memcpy(&out[off + 1024], &lo, 2);
+                }
+}
+
+// conv9s.hip: conv_flatten's filter of ONE mel row as a 16x16x32 A fragment -- rows 0 .. 3 are the four flatten channels, K = conv9_1's
+// channels in natural order (value j of lane l: channel 8 (l >> 4) + j), rows 4 .. 15 zero.  [row 128][plane: high, low halves][lane 64]
+// [8 values]; wf: [flatten channel][conv9_1 channel][row], already on conv9_1's normalised channels.
+static void pack_flat_rows(const float* wf, std::vector<char>& out, bool& range_ok) {
+    out.assign((size_t)128 * 2 * 1024, 0);
+    for (int h = 0; h < 128; ++h)
+        for (int l = 0; l < 64; ++l)
+            for (int j = 0; j < 8; ++j) {
+                const int row = l & 15, ch = 8 * (l >> 4) + j;
+                if (row >= 4) continue;
+                const float v = wf[((size_t)row * 32 + ch) * 128 + h];
+                const uint16_t hi = f2h(v), lo = f2h(v - h2f(hi));
+                if ((hi & 0x7c00u) == 0x7c00u) range_ok = false;
+                const size_t off = ((size_t)(h * 2) * 64 + l) * 16 + (size_t)j * 2;
+                memcpy(&out[off], &hi, 2); memcpy(&out[off + 1024], &lo, 2);
+            }
+}
+
 // conv4_ups.hip (round 3): the plain A launch of a decoder block, its upsampled input half at low resolution.  Skip chunks (input
 // channels [0, c0)) as pack_conv_split lays them out -- per 32-channel chunk a bank of high halves, then one of low halves, each [tap 9]
 // [sub-step 2][lane 64][8 values] --; then the upsampled chunks (input channels [c0, c0 + c1)): per chunk a bank of high halves and one
@@ -661,6 +697,14 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
         }
         if ((rc = dev_upload(c, (char**)&B.d_proj, (const char*)pj.data(), pj.size() * 2))) return rc;
         if ((rc = dev_upload(c, &B.d_bias3, b2r.data(), cout * 4))) return rc;
+        if (cin0 == 32 && cin1 == 32 && cout == 32 && H == 128 && W == 256) {      // conv9_1.B: the row-streaming form (conv9s.hip)
+            pack_conv_stream16(f2, pk, c->split_range_ok);
+            if (pk.size() != conv1_stream_weight_bytes()) return fail(c, SS_ERR_STATE, "pack_conv_stream16: size");
+            if ((rc = dev_upload(c, (char**)&B.d_w_s16, pk.data(), pk.size()))) return rc;
+            pack_proj_stream16(fr, pk, c->split_range_ok);
+            if (pk.size() != conv9_stream_proj_bytes()) return fail(c, SS_ERR_STATE, "pack_proj_stream16: size");
+            if ((rc = dev_upload(c, (char**)&B.d_proj_s16, pk.data(), pk.size()))) return rc;
+        }
     }
     if (c->prec == kF16x2) pack_conv_split(f2, nullptr, NTB, pk, c->split_range_ok); else pack_conv_v2(f2, nullptr, c->bf16, NT, pk);
     if ((rc = dev_upload(c, (char**)&B.d_w2, pk.data(), pk.size()))) return rc;
@@ -770,6 +814,10 @@ int build_model(ss_ctx* c, const Blob& bl) {
             t4[at] = hi; t4[bank + at] = f2h(v - h2f(hi));
         }
         if ((rc = dev_upload(c, (char**)&c->d_flat_frag4, (const char*)t4.data(), t4.size() * 2))) return rc;
+        std::vector<char> rows;                           // ... and per mel row for conv9s.hip
+        pack_flat_rows(wf, rows, c->split_range_ok);
+        if (rows.size() != conv9_stream_flat_bytes()) return fail(c, SS_ERR_STATE, "pack_flat_rows: size");
+        if ((rc = dev_upload(c, (char**)&c->d_flat_rows, rows.data(), rows.size()))) return rc;
     }
     if ((rc = dev_upload(c, &c->d_flat_b, bf, 16))) return rc;
     // spec_output_conv.1 (pytorch_neural_nets.py:128): Conv2d(32, 2, 1) with bias
