@@ -6,21 +6,21 @@
 // the arithmetic of conv1_1's second conv, which conv1s.hip runs without a patch image and without a barrier after the prologue; and
 // here the operands need not even be produced: h9 lies in memory in the order conv1s.hip's store_px writes -- lane (g, c) finds
 // channels 8 g .. 8 g + 7 of its pixel as one 16-byte run per plane -- so a strip row of h9 IS the 3 x 3's B operand, four 16-byte loads
-// per lane.  The core (tap loop, shifted combine, split) is stream16.h's, shared with conv1s.hip.
+// per lane.  The core is stream16.h's form without overlap columns (shifted operands with a halo lane, one accumulator set), shared with
+// conv9a.hip; the split is shared with conv1s.hip as well.
 //
-//   * Work unit = (window, band of `rows` rows, strip of 32 columns, 30 of them stored), strips fastest; a wave's units are independent.
+//   * Work unit = (window, band of `rows` rows, strip of 32 columns, all of them stored), strips fastest; a wave's units are independent.
 //   * The wave holds h9 of rows y - 1, y, y + 1 in three register sets that change roles.  Row y - 1 is last read by tap 2; behind it
 //     the loads of row y + 2 are issued INTO ITS REGISTERS and have the other six taps, the next row's projection and six more taps to
 //     arrive (about 1.3 row steps, ~4.8 us with two waves per SIMD): no set beyond the three.  c1 and c8 of row y + 1 are requested
 //     behind the projection's products of row y, a row step ahead, into the registers those products read.  In the mask-only pass
 //     the loop has no stores and no request behind a branch, so vmcnt counts loads alone and every wait is for the oldest request.
-//   * Rows outside the picture are zero operands; columns outside it have their addresses clamped and their h9 operands masked (the
-//     3 x 3's zero padding; what the projection computes there belongs to columns that are not stored).
-//   * P[1] starts from the summed biases b2 + br and takes the projection: c1 at (y, x) and c8 at (y >> 1, x >> 1), each a K = 32
+//   * Rows outside the picture are zero operands; so are the two halo pixels of a row (one more 16-byte load per plane, stream16.h)
+//     where they lie outside it: clamped addresses, wave-uniform masks (the 3 x 3's zero padding).
+//   * P starts from the summed biases b2 + br and takes the projection: c1 at (y, x) and c8 at (y >> 1, x >> 1), each a K = 32
 //     operand against fragments in 16x16x32 A-operand order (weights.hip pack_proj_stream16), three products per term.  Strip columns
-//     are x0 + 2 c + t with x0 odd, so tile 1's lane c and tile 0's lane c + 1 share a c8 pixel: c8 is loaded for tile 1 and reaches
-//     tile 0 through a DPP row shift.
-//   * out = P_0 + shifted P_- + shifted P_+, ReLU, split into f16 halves; the high halves are range-tested as in conv4.hip's form (the
+//     are 32 s + 2 c + t, so both tiles' lane c sit on c8 pixel 16 s + c: one load of c8 serves both.
+//   * The nine taps go into the same P; ReLU, split into f16 halves; the high halves are range-tested as in conv4.hip's form (the
 //     split values feed the flatten whether c9 is stored or not).  The split row is the B operand of conv_flatten: row y's filter is an
 //     A fragment whose rows 0 .. 3 are the four flatten channels (weights.hip pack_flat_rows, 256 KB, read from memory at the top of
 //     the row step); three products per tile accumulate in registers over the unit's rows, and at the unit's end lanes g = 0 write
@@ -63,42 +63,37 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
     uint32_t ovf = 0;                                     // the largest high halves of the stored columns (all exponent bits set = infinity / NaN)
 
     for (int unit = (int)blockIdx.x * kS1Waves + wave; unit < total_units; unit += (int)gridDim.x * kS1Waves) {
-        const int s = unit % kStrips, b = (unit / kStrips) % bands, n = unit / (kStrips * bands);
-        const int x0 = kStripCols * s - 1, y0 = b * rows_per_unit, ylast = y0 + rows_per_unit - 1;
-        uint32_t keep[2], voff[2]; bool st_lane[2];
-        int xt[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int mm = 2 * c + t;                     // this lane's strip column in pixel tile t
-            xt[t] = x0 + mm;
-            keep[t] = (unsigned)xt[t] < (unsigned)kW ? 0xffffffffu : 0u;
-            st_lane[t] = mm >= 1 && mm <= kStripCols && xt[t] < kW;
-            voff[t] = (uint32_t)min(max(xt[t], 0), kW - 1) * 64u + (uint32_t)g * 16u;       // this lane's run in a row of h9 / c1 / c9
-        }
-        const uint32_t voff8 = (uint32_t)(min(max(xt[1], 0), kW - 1) >> 1) * 64u + (uint32_t)g * 16u;   // ... in a row of c8, tile 1's pixel
+        const int s = unit % kStrips32, b = (unit / kStrips32) % bands, n = unit / (kStrips32 * bands);
+        const int x0 = 32 * s, y0 = b * rows_per_unit, ylast = y0 + rows_per_unit - 1;
+        const int xt[2] = {x0 + 2 * c, x0 + 2 * c + 1};   // this lane's picture column in pixel tile t
+        const uint32_t voff[2] = {(uint32_t)xt[0] * 64u + (uint32_t)g * 16u, (uint32_t)xt[1] * 64u + (uint32_t)g * 16u};   // its run in a row of h9 / c1 / c9
+        // ... its halo pixel's (lanes c < 8: the one left of the strip, the others the one right of it; outside the picture: the edge
+        // pixel, masked), and its run in a row of c8: both tiles' lane c sit on c8 pixel 16 s + c
+        const uint32_t hoff = (uint32_t)(c < 8 ? max(x0 - 1, 0) : min(x0 + 32, kW - 1)) * 64u + (uint32_t)g * 16u;
+        const uint32_t hkeep = (c < 8 ? s > 0 : s < kStrips32 - 1) ? 0xffffffffu : 0u;
+        const uint32_t voff8 = (uint32_t)(x0 / 2 + c) * 64u + (uint32_t)g * 16u;
         const char* hw = (const char*)a.src0 + (size_t)n * kH * kRowB;   // the window's h9, c1, c8 (high planes; the low ones lie `lo` behind)
         const char* c1w = (const char*)a.xp0 + (size_t)n * kH * kRowB;
         const char* c8w = (const char*)a.xp1 + (size_t)n * (kH / 2) * kRowB8;
         char* ow = (char*)a.out + (size_t)n * kH * kRowB;
 
         // h9 of picture row r (any r: outside the picture the nearest row is read and mask_row clears it)
-        auto load_row = [&](S16Row& H, int r) {
+        auto load_row = [&](S16RowH& H, int r) {
             const char* p = hw + (size_t)min(max(r, 0), kH - 1) * kRowB;
 #pragma unroll
             for (int t = 0; t < 2; ++t) { H.f[t][0] = *(const u32x4*)(p + voff[t]); H.f[t][1] = *(const u32x4*)(p + lo + voff[t]); }
+            H.h[0] = *(const u32x4*)(p + hoff); H.h[1] = *(const u32x4*)(p + lo + hoff);
         };
-        auto mask_row = [&](S16Row& H, int r) {
+        auto mask_row = [&](S16RowH& H, int r) {
             const uint32_t rk = (unsigned)r < (unsigned)kH ? 0xffffffffu : 0u;      // (wave-uniform)
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
+            for (int pq = 0; pq < 2; ++pq)
 #pragma unroll
-                for (int pq = 0; pq < 2; ++pq)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) H.f[t][pq][e] &= keep[t] & rk;
+                for (int e = 0; e < 4; ++e) { H.f[0][pq][e] &= rk; H.f[1][pq][e] &= rk; H.h[pq][e] &= hkeep & rk; }
         };
-        S16Row H0, H1, H2;                                // h9 of rows y - 1, y, y + 1 of the output row y, in rotating roles
+        S16RowH H0, H1, H2;                               // h9 of rows y - 1, y, y + 1 of the output row y, in rotating roles
         S16Row C1;                                        // c1 of row y
-        u32x4 C8[2];                                      // c8 of row y >> 1 at tile 1's pixels, [plane]
+        u32x4 C8[2];                                      // c8 of row y >> 1 at the lane's pixel, [plane]
         auto load_c1 = [&](int r) {
             const char* p = c1w + (size_t)r * kRowB;
 #pragma unroll
@@ -112,26 +107,21 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
         uint32_t ovt[2] = {0u, 0u};
 
         // one output row: Ha = h9 of row y - 1, Hb = row y, Hn = row y + 1 (requested a row step ago; masked in front of its taps)
-        auto row_step = [&](int y, S16Row& Ha, const S16Row& Hb, S16Row& Hn) {
-            S16Ring ring;
-            ring.rd(wl_base, 0);
+        auto row_step = [&](int y, S16RowH& Ha, const S16RowH& Hb, S16RowH& Hn) {
+            S16Ring3 ring;                                // (two of its slots: every set here serves twelve products)
+            ring.rd_tap(0, wl_base, 0);
             u32x4 pw[2][2][2];                            // the projection's fragments, [source][channel tile][plane]
 #pragma unroll
             for (int q = 0; q < 8; ++q) pw[q >> 2][(q >> 1) & 1][q & 1] = *(const u32x4*)(pl_base + q * 1024);
             // row y's flatten filter: rows 0 .. 3 of the A fragment, high and low halves
             const u32x4 fwh = *(const u32x4*)(fw_base + (size_t)(2 * y) * 1024), fwl = *(const u32x4*)(fw_base + (size_t)(2 * y + 1) * 1024);
             __builtin_amdgcn_sched_barrier(0);
-            // ---- P[dx = 0] = b2 + br + projection of cat[c1, up(c8)] at (y, x); the others start at 0 ----
-            f32x4 P[3][2][2];
+            // ---- P = b2 + br + projection of cat[c1, up(c8)] at (y, x) ----
+            f32x4 P[2][2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int u = 0; u < 2; ++u) { P[0][t][u] = f32x4{0.f, 0.f, 0.f, 0.f}; P[1][t][u] = bias[u]; P[2][t][u] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            u32x4 c8t0[2];                                // tile 0's lane c has the c8 pixel of tile 1's lane c - 1 (lane 0: strip column 0, not stored)
-#pragma unroll
-            for (int pq = 0; pq < 2; ++pq)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c8t0[pq][e] = (uint32_t)s16_shr1((int)C8[pq][e]);
+                for (int u = 0; u < 2; ++u) P[t][u] = bias[u];
 #pragma unroll
             for (int src = 0; src < 2; ++src)
 #pragma unroll
@@ -141,8 +131,8 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
                             const int pq = pr == 0 ? 1 : 0;
-                            const u32x4& x = src == 0 ? C1.f[t][pq] : (t ? C8[pq] : c8t0[pq]);
-                            P[1][t][u] = s16_mfma(pw[src][u][pr == 1 ? 1 : 0], x, P[1][t][u]);
+                            const u32x4& x = src == 0 ? C1.f[t][pq] : C8[pq];
+                            P[t][u] = s16_mfma(pw[src][u][pr == 1 ? 1 : 0], x, P[t][u]);
                         }
             __builtin_amdgcn_sched_barrier(0);
             // the next row's c1 and c8, into the registers just read: they arrive behind this row's taps.  Every request of the loop is
@@ -153,13 +143,19 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             load_c8(min(y + 1, ylast) >> 1);
             __builtin_amdgcn_sched_barrier(0);
             // ---- the 3 x 3 ----
-            s16_taps(ring, wl_base, Ha, Hb, Hn, P, [&](int tap) {
+            s16_taps_shifted(ring, wl_base, Ha, Hb, Hn, P, [] {}, [&](int tap) {
                 if (tap == 2) load_row(Ha, min(y + 2, ylast + 1));     // row y - 1 has been read: row y + 2 takes its registers
                 if (tap == 5) mask_row(Hn, y + 1);
             });
-            // ---- out, ReLU, split; the range test; conv_flatten's products on the split row ----
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- ReLU, split; the range test; conv_flatten's products on the split row ----
             float v[2][2][4];
-            s16_combine(P, v);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[t][u][r] = relu_i(P[t][u][r]);
             uint32_t kh[2][4], kl[2][4];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -177,11 +173,10 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             if (a.store_out) {                            // (wave-uniform) c9 itself: only when the spec head runs
                 char* p = ow + (size_t)y * kRowB;
 #pragma unroll
-                for (int t = 0; t < 2; ++t)
-                    if (st_lane[t]) {
-                        *(u32x4*)(p + voff[t]) = u32x4{kh[t][0], kh[t][1], kh[t][2], kh[t][3]};
-                        *(u32x4*)(p + lo + voff[t]) = u32x4{kl[t][0], kl[t][1], kl[t][2], kl[t][3]};
-                    }
+                for (int t = 0; t < 2; ++t) {
+                    *(u32x4*)(p + voff[t]) = u32x4{kh[t][0], kh[t][1], kh[t][2], kh[t][3]};
+                    *(u32x4*)(p + lo + voff[t]) = u32x4{kl[t][0], kl[t][1], kl[t][2], kl[t][3]};
+                }
             }
         };
 
@@ -201,12 +196,12 @@ void conv9_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
         // the unit's flatten sums: result rows 0 .. 3 (lanes g = 0) are the four flatten channels of the lane's pixel
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            if (g == 0 && st_lane[t]) {
+            if (g == 0) {
                 float* fp = a.flat_part + ((size_t)n * bands + b) * 4 * kW + xt[t];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) fp[r * kW] = F[t][r];
             }
-            if (st_lane[t]) ovf = pk_max_u16(ovf, ovt[t]);        // (columns that are not stored hold partial sums: not tested)
+            ovf = pk_max_u16(ovf, ovt[t]);
         }
     }
     if (((ovf & 0x7fff7fffu) + 0x04000400u) & 0x80008000u) atomicOr(a.range_flag, 1);       // (rare: the engine turns it into SS_ERR_RANGE)
@@ -223,13 +218,13 @@ size_t conv9_stream_proj_bytes() { return kProjFrag; }
 size_t conv9_stream_flat_bytes() { return (size_t)kH * 2 * 1024; }
 bool conv9_stream_rows_ok(int rows_per_unit) { return rows_per_unit >= 2 && !(rows_per_unit & 1) && kH % rows_per_unit == 0 && rows_per_unit <= kMaxRows; }
 int conv9_stream_flat_groups(int rows_per_unit) { return kH / rows_per_unit; }
-// multiply-adds per term that the launch issues, the strips' overlap columns included: a strip row is 24 + 108 + 6 products of 16 x 16 x 32,
+// multiply-adds per term that the launch issues: a strip row is 24 + 108 + 6 products of 16 x 16 x 32,
 // three products to a term (ScopedLaunch counts the three)
-double conv9_stream_issued_macs(int N) { return (double)N * kH * kStrips * ((24 + 108 + 6) / 3) * (16.0 * 16 * 32); }
+double conv9_stream_issued_macs(int N) { return (double)N * kH * kStrips32 * ((24 + 108 + 6) / 3) * (16.0 * 16 * 32); }
 
 hipError_t launch_conv9_stream(const ConvArgs& a, int rows_per_unit, int grid_override, int num_cus, hipStream_t s) {
     if (!conv9_stream_supports(a) || !conv9_stream_rows_ok(rows_per_unit)) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)a.N * (kH / rows_per_unit) * kStrips;
+    const int64_t total = (int64_t)a.N * (kH / rows_per_unit) * kStrips32;
     if (total >= (int64_t)1 << 30) return hipErrorInvalidValue;
     const int cus = num_cus > 0 ? num_cus : 256;
     int grid = (int)std::min<int64_t>(cus, (total + kS1Waves - 1) / kS1Waves);

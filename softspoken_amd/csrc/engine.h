@@ -65,6 +65,7 @@ struct ConvPlan {          // one launch of a ResBlock half
     void* d_w_s1 = nullptr;                               // conv1s.hip: conv1_1's second conv, banks in the K order of the first conv's accumulator registers
     void* d_w_s16 = nullptr;                              // ... and for its 16-pixel form (v_mfma_f32_16x16x32_f16: natural K order, channel rows 8 g + 4 u + r)
     void* d_proj_s16 = nullptr;                           // conv9s.hip: conv9_1.B's projection as 16x16x32 A fragments (its 3 x 3 banks: d_w_s16)
+    void* d_w_a16 = nullptr; void* d_w_ups16 = nullptr;   // conv9a.hip: conv9_1.A's skip half as pack_conv_stream16's banks, its upsampled half as pre-summed 16x16x32 sets
     void* d_w_upsr = nullptr;                           // conv4_ups.hip, ring form: the same for the A launch that also writes r (entries in walk order)
     void* d_w_ups32 = nullptr;                            // conv2_ups.hip (fp32): the A launch with the upsampled half at low resolution
     int ups32_nt = 1;                                     // ... packed for this many 32-channel tiles per block

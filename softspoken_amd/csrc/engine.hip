@@ -349,7 +349,18 @@ static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const Co
                            [&](ConvArgs& y) { return launch_conv3x3_v4(y, p.NT, cus, prec4, stream); });
     };
     int rc;
-    if (ups) {
+    // conv9_1.A: the row-streaming form (conv9a.hip) -- the same pre-summed taps on stream16.h's core, no patch images, no barriers.
+    // (Development build, SOFTSPOKEN_C9A=0: conv4_ups.hip's form, below; SOFTSPOKEN_UPS=0 switches both off.)
+    ConvArgs as = a;
+    as.wpk = pa.d_w_a16; as.wpk_b = pa.d_w_ups16;
+    const int rows_a = dev_env("SOFTSPOKEN_C9A_ROWS", 32);
+    if (ups && pa.d_w_a16 && pa.d_w_ups16 && dev_env("SOFTSPOKEN_C9A", 1) && conv9a_stream_supports(as) && conv9a_stream_rows_ok(rows_a)) {
+        const int grid = dev_env("SOFTSPOKEN_C9A_GRID", 0);
+        // (FLOPs booked: the layer's algorithmic ones; issued: 108 + 48 products per strip row, the tile form's count)
+        if ((rc = conv_launch(c, stream, conv9a_stream_variant(), pa.name, as, flops_a, bytes_a, conv9a_stream_issued_macs(n),
+                              [&](ConvArgs& y) { return launch_conv9a_stream(y, rows_a, grid, cus, stream); })))
+            return rc;
+    } else if (ups) {
         // FLOPs booked are the layer's algorithmic ones (2 x multiply-adds of the 3x3 as the reference computes it); this
         // form issues 9 C0 + 4 C1 multiply-adds per output value instead of 9 (C0 + C1).  (It takes no stage stamps.)
         ScopedLaunch sl(c, stream, std::string(conv_ups_variant()) + "/" + pa.name, flops_a, bytes_a, px * pa.Cout * (9.0 * pa.C0 + 4.0 * pa.C1));
@@ -365,7 +376,7 @@ static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const Co
         const int rows = dev_env("SOFTSPOKEN_C9S_ROWS", 32);
         if (conv9_stream_supports(bs) && conv9_stream_rows_ok(rows)) {
             const int grid = dev_env("SOFTSPOKEN_C9S_GRID", 0);
-            // (FLOPs booked: the layer's algorithmic ones; issued: what the strips really multiply, their overlap columns included)
+            // (FLOPs booked: the layer's algorithmic ones; issued: what the strips really multiply, the flatten's products included)
             if ((rc = conv_launch(c, stream, conv9_stream_variant(), pb.name, bs, flops_b, bytes_b, conv9_stream_issued_macs(n),
                                   [&](ConvArgs& y) { return launch_conv9_stream(y, rows, grid, cus, stream); })))
                 return rc;

@@ -218,6 +218,17 @@ int conv9_stream_flat_groups(int rows_per_unit);
 double conv9_stream_issued_macs(int N);
 hipError_t launch_conv9_stream(const ConvArgs& a, int rows_per_unit, int grid_override, int num_cus, hipStream_t s);
 
+// conv9a.hip (f16x2): conv9_1.A as a row-streaming kernel on stream16.h's core without overlap columns -- c1 and c8 are read from memory
+// as MFMA operands, the upsampled half at c8's resolution against pre-summed taps.  Fields as for conv4_ups.hip's plain A launch, except:
+// wpk = pack_conv_stream16's banks of the conv's first 32 input channels, wpk_b = pack_ups_stream16's sets (conv9a_stream_ups_bytes).
+// rows_per_unit, grid_override: as for conv9s.hip.
+bool conv9a_stream_supports(const ConvArgs& a);
+const char* conv9a_stream_variant();
+size_t conv9a_stream_ups_bytes();
+bool conv9a_stream_rows_ok(int rows_per_unit);       // even, divides 128, at most 32
+double conv9a_stream_issued_macs(int N);
+hipError_t launch_conv9a_stream(const ConvArgs& a, int rows_per_unit, int grid_override, int num_cus, hipStream_t s);
+
 // heads.hip
 // ResBlock1D(4,4) + Conv1d(4,1,1) fed by the FLAT partial sums [N][n_parts][4][256]: sums them in order, adds conv_flatten's bias,
 // ReLU, then the 1-D head -> logits [N][256]

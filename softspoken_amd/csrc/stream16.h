@@ -1,11 +1,12 @@
-// The row-streaming core on v_mfma_f32_16x16x32_f16, shared by conv1s.hip (conv1_1) and conv9s.hip (conv9_1.B): a 3 x 3, 32 -> 32 conv at
+// The row-streaming core on v_mfma_f32_16x16x32_f16, shared by conv1s.hip (conv1_1), conv9a.hip (conv9_1.A) and conv9s.hip (conv9_1.B): a 3 x 3, 32 -> 32 conv at
 // 128 x 256 whose operand rows a wave holds in registers while it walks down a strip of 32 columns (conv1s.hip's header tells the idea).
 //   * Lane (g, c) = (lane >> 4, lane & 15).  A strip's 32 columns are two pixel tiles, interleaved: tile t holds strip columns 2 c + t.
 //     A lane's B operand of a tile is channels 8 g .. 8 g + 7 of its pixel as one 16-byte run per plane (high halves, low halves);
 //     result row 4 g + r of channel tile u is channel 8 g + 4 u + r.
 //   * The taps of one dx accumulate into their own tile, P[dx][t][u] = sum over dy of W[dy][dx] x row[y + dy], three f16 products per
 //     term; out[x] = P_-1[x - 1] + P_0[x] + P_+1[x + 1]: tile 0's column neighbours are tile 1's lanes c - 1 / c, tile 1's are tile 0's
-//     lanes c / c + 1.  Strip columns 0 and 31 have no neighbour and are not stored: a strip yields 30 columns, nine strips a row.
+//     lanes c / c + 1.  Strip columns 0 and 31 have no neighbour and are not stored: a strip yields 30 columns, nine strips a row
+//     (conv1s.hip's form: its operand rows are made in registers and have no halo pixel to load; the form below shifts operands instead).
 //   * Weight banks: weights.hip pack_conv_stream16, [plane][tap][channel tile][lane][16 B], read from the LDS one tap ahead.
 #pragma once
 #include "mfma_util.h"
@@ -76,6 +77,83 @@ __device__ __forceinline__ void s16_combine(const f32x4 (&P)[3][2][2], float (&v
             v[0][u][r] = relu_i(P[1][0][u][r] + s16_shr1f(P[0][1][u][r]) + P[2][1][u][r]);
             v[1][u][r] = relu_i(P[1][1][u][r] + P[0][0][u][r] + s16_shl1f(P[2][0][u][r]));
         }
+}
+
+// ---- the core without overlap columns (conv9a.hip, conv9s.hip) -----------------------------------------------------------------------------
+// The same lanes and tiles, but the OPERANDS are shifted, not the outputs: strip s holds picture columns 32 s .. 32 s + 31, tile t's
+// lane c column 32 s + 2 c + t, and one accumulator set P[t][u] takes all nine taps.  For tap (dy, dx) tile t needs the pixel at column
+// x + dx: for dx = -1 tile 1 reads tile 0's registers as they are and tile 0 reads tile 1's row shifted by row_shr:1, its lane 0 taking
+// the pixel at column 32 s - 1; for dx = +1 tile 0 reads tile 1's registers and tile 1 reads tile 0's row shifted by row_shl:1, its
+// lane 15 taking column 32 s + 32.  The two halo pixels of a row come from one more 16-byte load per plane (lanes c < 8 ask for the left
+// one, the others for the right one; lanes 0 and 15 use them): a strip stores all 32 columns, eight strips cover a row exactly.
+static constexpr int kStrips32 = 8;
+
+struct S16RowH { u32x4 f[2][2]; u32x4 h[2]; };           // S16Row + the halo load, [plane]
+
+// DPP with bound_ctrl off leaves `old` in the lane that has no source: the shifted operand and its halo lane in one move per register
+__device__ __forceinline__ u32x4 s16_shr1_halo(const u32x4& v, const u32x4& halo) {      // lane c <- lane c - 1 (c = 0: its halo)
+    u32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = (uint32_t)__builtin_amdgcn_update_dpp((int)halo[e], (int)v[e], 0x111, 0xf, 0xf, false);
+    return r;
+}
+__device__ __forceinline__ u32x4 s16_shl1_halo(const u32x4& v, const u32x4& halo) {      // lane c <- lane c + 1 (c = 15: its halo)
+    u32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = (uint32_t)__builtin_amdgcn_update_dpp((int)halo[e], (int)v[e], 0x101, 0xf, 0xf, false);
+    return r;
+}
+
+// Fragment sets (both channel tiles, both planes: four 16-byte LDS reads) in a THREE-slot ring: a set of the 3 x 3 serves twelve
+// products and is read one set ahead, as in S16Ring; a kernel with sets of six products (conv9a.hip's upsampled half) reads those two
+// sets ahead, so that every read still lies twelve products in front of its first use.
+struct S16Ring3 {
+    u32x4 wh[3][2], wl[3][2];                             // [ring slot][channel tile]
+    // hi / lo: the lane's address of channel tile 0's fragment of either plane; tile 1's lies `step` bytes behind
+    __device__ __forceinline__ void rd(int slot, const char* hi, const char* lo, int step) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) { wh[slot][u] = *(const u32x4*)(hi + u * step); wl[slot][u] = *(const u32x4*)(lo + u * step); }
+    }
+    __device__ __forceinline__ void rd_tap(int slot, const char* wl_base, int tap) { rd(slot, wl_base + tap * 2048, wl_base + kBank + tap * 2048, 1024); }
+};
+
+// three products per term of one pixel tile and both channel tiles against the set in `slot`: B[plane]
+__device__ __forceinline__ void s16_products(const S16Ring3& ring, int slot, const u32x4 (&B)[2], f32x4 (&Pt)[2]) {
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) Pt[u] = s16_mfma(pr == 1 ? ring.wl[slot][u] : ring.wh[slot][u], B[pr == 0 ? 1 : 0], Pt[u]);
+}
+
+// The nine taps into P[t][u].  Tap k's set is in slot k & 1; the caller has requested tap 0's.  before_last() runs in front of the
+// products of tap 8, where no next tap is to be read (the caller's own next sets go there); after_tap(tap) behind the products of taps
+// 0 .. 8 (rows Ha / Hb / Hn are last read by taps 2 / 5 / 8).  The shifted operand is made at the point of use.
+template <typename Last, typename AfterTap>
+__device__ __forceinline__ void s16_taps_shifted(S16Ring3& ring, const char* wl_base, const S16RowH& Ha, const S16RowH& Hb, const S16RowH& Hn,
+                                                 f32x4 (&P)[2][2], Last&& before_last, AfterTap&& after_tap) {
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int dy = tap / 3, dx = tap % 3 - 1, slot = tap & 1;
+        const S16RowH& Hr = dy == 0 ? Ha : (dy == 1 ? Hb : Hn);
+        if (tap + 1 < 9) ring.rd_tap(slot ^ 1, wl_base, tap + 1); else before_last();
+        u32x4 B[2][2];                                    // [pixel tile][plane]
+#pragma unroll
+        for (int pq = 0; pq < 2; ++pq) {
+            B[0][pq] = dx == 0 ? Hr.f[0][pq] : (dx < 0 ? s16_shr1_halo(Hr.f[1][pq], Hr.h[pq]) : Hr.f[1][pq]);
+            B[1][pq] = dx == 0 ? Hr.f[1][pq] : (dx < 0 ? Hr.f[0][pq] : s16_shl1_halo(Hr.f[0][pq], Hr.h[pq]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the four result tiles (pixel tile x channel tile) take turns: a product's accumulator was last written four products earlier
+#pragma unroll
+        for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+                    P[t][u] = s16_mfma(pr == 1 ? ring.wl[slot][u] : ring.wh[slot][u], B[t][pr == 0 ? 1 : 0], P[t][u]);
+        __builtin_amdgcn_sched_barrier(0);
+        after_tap(tap);
+    }
 }
 
 // a lane's eight values of a pixel tile are channels 8 g .. 8 g + 7 of its pixel: one 16-byte run per plane (high halves kh, low halves kl)

@@ -274,6 +274,31 @@ static void pack_conv_split_ups(const Folded& w3, int c0, int c1, std::vector<ch
                         }
 }
 
+// conv9a.hip: the upsampled input half (input channels [c0, c0 + 32)) of a 32-channel A launch for v_mfma_f32_16x16x32_f16, at the low
+// resolution: [row parity a][row tap ty][column form f = 2 b + tx][channel tile u][plane: high, low halves][lane 64][8 values], the sets
+// of rows and columns as in pack_conv_split_ups (b: the column parity), summed in float64, rounded to fp32, split.  Lane l is output row
+// i = l & 15 of tile u = channel 8 (i >> 2) + 4 u + (i & 3), value j is input channel c0 + 8 (l >> 4) + j (natural K).
+static void pack_ups_stream16(const Folded& w3, int c0, std::vector<char>& out, bool& range_ok) {
+    out.assign((size_t)2 * 2 * 4 * 2 * 2 * 1024, 0);
+    static const int lo_of[2][2] = {{0, 1}, {0, 2}}, hi_of[2][2] = {{0, 2}, {1, 2}};
+    for (int a = 0; a < 2; ++a)
+        for (int ty = 0; ty < 2; ++ty)
+            for (int f = 0; f < 4; ++f)
+                for (int u = 0; u < 2; ++u)
+                    for (int l = 0; l < 64; ++l)
+                        for (int j = 0; j < 8; ++j) {
+                            const int b = f >> 1, tx = f & 1, i = l & 15, co = 8 * (i >> 2) + 4 * u + (i & 3), ci = c0 + 8 * (l >> 4) + j;
+                            double sum = 0.0;
+                            for (int dy = lo_of[a][ty]; dy <= hi_of[a][ty]; ++dy)
+                                for (int dx = lo_of[b][tx]; dx <= hi_of[b][tx]; ++dx) sum += (double)w3.w[((size_t)co * w3.cin + ci) * 9 + dy * 3 + dx];
+                            const float v = (float)sum;
+                            const uint16_t hi = f2h(v), lo = f2h(v - h2f(hi));
+                            if ((hi & 0x7c00u) == 0x7c00u) range_ok = false;
+                            const size_t off = ((size_t)((((a * 2 + ty) * 4 + f) * 2 + u) * 2) * 64 + l) * 16 + (size_t)j * 2;
+                            memcpy(&out[off], &hi, 2); memcpy(&out[off + 1024], &lo, 2);
+                        }
+}
+
 // conv4_ups.hip, ring form (the A launch that also writes r = conv1x1(x) + br): per 32-channel output group the ring entries in the
 // order the kernel walks them -- per skip chunk WH = [tap 9 + the projection's][sub-step 2][lane 64][8] high halves, then [32] bias and
 // [32] projection bias of the group (fp32), WL = the same taps' low halves; per upsampled chunk UH = [class 4][tap 4] pre-summed as
@@ -668,6 +693,15 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
             if (pk.size() != conv_ups_weight_bytes(cin0, cin1)) return fail(c, SS_ERR_STATE, "pack_conv_split_ups: size");
             if ((rc = dev_upload(c, (char**)&A.d_w_ups, pk.data(), pk.size()))) return rc;
             c->convs.back().d_w_ups = A.d_w_ups;
+            if (cin0 == 32 && cin1 == 32 && H == 128 && W == 256) {      // conv9_1.A: the row-streaming form (conv9a.hip)
+                pack_conv_stream16(f1, pk, c->split_range_ok);           // (its input channels 0 .. 31: c1)
+                if (pk.size() != conv1_stream_weight_bytes()) return fail(c, SS_ERR_STATE, "pack_conv_stream16: size");
+                if ((rc = dev_upload(c, (char**)&A.d_w_a16, pk.data(), pk.size()))) return rc;
+                pack_ups_stream16(f1, cin0, pk, c->split_range_ok);
+                if (pk.size() != conv9a_stream_ups_bytes()) return fail(c, SS_ERR_STATE, "pack_ups_stream16: size");
+                if ((rc = dev_upload(c, (char**)&A.d_w_ups16, pk.data(), pk.size()))) return rc;
+                c->convs.back().d_w_a16 = A.d_w_a16; c->convs.back().d_w_ups16 = A.d_w_ups16;
+            }
         }
     }
     // f16x2, B launch of the 96-channel blocks: three 32-channel groups over the four tiles' shared ring as well (SOFTSPOKEN_NTB1=0 in the
