@@ -22,7 +22,7 @@
  *   ss_get_regions / ss_find_regions       NNDetector.py:103-143 find_speech_regions + worker.py:100
  *   ss_format_csv_rows                     worker.py:103-125 + root/code/frontend/silencer_ui.py:816-817 (DataFrame.to_csv text)
  *   ss_separation_plan / _maps /           silencer_ui.py:974-998 (SilenceWorker.run) with the spec head the reference computes and drops:
- *   ss_separate_pcm                        pytorch_neural_nets.py:125-130,184-185 (spec_output_conv, "env / speech separation"),
+ *   ss_separate_pcm (_channels)            pytorch_neural_nets.py:125-130,184-185 (spec_output_conv, "env / speech separation"),
  *                                          NNDetector.py:84-101 (process_batch's speech_pred), worker.py:78-79; averaging NNDetector.py:168-186
  *
  * Conventions: every function returns an int status (SS_OK == 0) unless stated; the caller owns all
@@ -537,6 +537,24 @@ int ss_separation_maps(ss_ctx* ctx, int file_id, int64_t first_bin, int64_t n_bi
  * f16 range (run the file in an fp32 context), with `out` not to be used. */
 int ss_separate_pcm(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, const ss_region* regions,
                     int64_t n_regions, const ss_separation_params* params, int16_t* out);
+/* Per-channel separation: the separation silencer for a recording detected with ss_add_pcm_channels* -- each channel's gains come from
+ * its own network passes, not from the mono mix (which holds a voice that reached one microphone at half level, and cuts bands out of
+ * the channels that did not hear it).  The definition above with two sentences changed:
+ *  1. The signals are those of ss_add_pcm_channels (channel c alone, no mixdown).  The spec head runs on the plan's windows of every
+ *     channel -- the windows of all channels fill the passes of ss_set_chunk_windows together -- and each channel has its own averaged
+ *     maps: a float64 sum in ascending window order divided by the count, stored as float32, bit for bit what ss_separation_maps gives
+ *     for that channel's file.
+ *  3. STFT bin q of channel c gets channel c's gain.
+ * Everything else is unchanged: the plan (ss_separation_plan), the default-step windows, the band gains, the triangles, the time
+ * interpolation and its clamps, above_fmax, the fades, the encode, the transcode's bytes outside the intervals; all channels are
+ * processed over the same merged intervals.  It acts as ss_reset + ss_add_pcm_channels of this file -- ss_reset_generation counts one
+ * reset, afterwards files 0 .. channels - 1 are the channels; streams are untouched.  Arguments, output and refusals are
+ * ss_separate_pcm's (SS_ERR_STATE on an audio-only context or while a run is in flight, SS_ERR_ARG for bad parameters, SS_ERR_RANGE
+ * under SS_FLAG_F16X2 when any channel's passes leave the f16 range).  channels == 1 is ss_separate_pcm, byte for byte; so is a channel
+ * without a partner (the last of an odd count) against ss_separate_pcm of its samples as a mono file, and a recording whose channels
+ * hold the same samples against ss_separate_pcm of that recording. */
+int ss_separate_pcm_channels(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames,
+                             const ss_region* regions, int64_t n_regions, const ss_separation_params* params, int16_t* out);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */

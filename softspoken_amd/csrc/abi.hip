@@ -292,6 +292,18 @@ extern "C" int ss_separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, i
     return separate_pcm(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
+extern "C" int ss_separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                                        int64_t n_regions, const ss_separation_params* params, int16_t* out) {
+    int rc = check_model_idle(c);
+    if (rc) return rc;
+    if ((rc = check_pcm_args(c, pcm, format, sr, ch, frames))) return rc;
+    if ((!regions && n_regions > 0) || n_regions < 0 || (!out && frames > 0)) return fail(c, SS_ERR_ARG, "ss_separate_pcm_channels: bad argument");
+    std::string err;
+    if ((rc = check_separation_params(params, err))) return fail(c, rc, "ss_separate_pcm_channels: " + err);
+    hipSetDevice(c->device);
+    return separate_pcm_channels(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
 // ------------------------------------------------------------------------------------------------------
 // review-screen spectrogram: voice_activity.py:148-154
 // ------------------------------------------------------------------------------------------------------

@@ -284,6 +284,8 @@ void separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n
 int separation_maps(ss_ctx* c, int file_id, int64_t first_bin, int64_t n_bins, float* out);
 int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
                  const ss_separation_params* params, int16_t* out);
+int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                          int64_t n_regions, const ss_separation_params* params, int16_t* out);
 void free_separation(ss_ctx* c);
 // host.hip
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")

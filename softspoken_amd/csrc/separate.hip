@@ -11,6 +11,10 @@
 //   4      sep_blend_kernel: per output sample of an interval, the four overlapping frames gathered in ascending order, blended with
 //          the decoded sample over the fade ramps, encoded as ss_silence_pcm encodes
 // Everything else of the file is the transcode (silence_encode_kernel with no ranges), launched first.
+//
+// ss_separate_pcm_channels ("per-channel separation"): the signals of step 1 are the channels alone (ss_add_pcm_channels), their windows
+// in one run list; sums, maps and gains carry a signal dimension, and step 3 runs as sep_stft_each_kernel<N>, which gives the two
+// channels of a complex FFT their own gains.  Steps 2 and 4 and the plan are the mix's.
 #include "engine.h"
 #include "dsp.h"
 
@@ -47,22 +51,29 @@ struct SepState {
 // One pass of the spec head: spec [m][2][128][256] holds the windows whose run-list positions (win_slot) are slot_lo .. slot_lo + m - 1.
 // Thread = (compact bin cb, channel x band cm); it adds the pass's windows over bin cbin[cb] to its float64 sum in ascending window order
 // (average_bin's window walk), so that the sum over all passes is the whole-file average's sum, bit for bit.
+// Signals (blockIdx.z: the channels of ss_separate_pcm_channels, one for the mix) share the plan: signal z's windows sit `nw` run-list
+// positions behind signal z - 1's, its sums and counts one [256][ncb] / [ncb] block further on.
 __global__ __launch_bounds__(256) void sep_accumulate_kernel(const float* __restrict__ spec, int slot_lo, int m, const int32_t* __restrict__ win_slot,
-                                                             int W, const int32_t* __restrict__ cbin, int ncb, double* __restrict__ sum,
+                                                             int W, int nw, const int32_t* __restrict__ cbin, int ncb, double* __restrict__ sum,
                                                              int32_t* __restrict__ count) {
-    const int cb = blockIdx.x * 256 + threadIdx.x, cm = blockIdx.y;
+    const int cb = blockIdx.x * 256 + threadIdx.x, cm = blockIdx.y, sig = blockIdx.z;
     if (cb >= ncb) return;
     const int j = cbin[cb];
     int lo = (int)((double)(j - 255) / 51.2) - 1;
     if (lo < 0) lo = 0;
     int hi = (int)((double)j / 51.2) + 1;
     if (hi > W - 1) hi = W - 1;
+    sum += (size_t)sig * 256 * ncb;
+    count += (size_t)sig * ncb;
+    const int64_t first = (int64_t)sig * nw - slot_lo;                     // signal's first window in this pass's numbering
+    if (first >= m || first + nw <= 0) return;                             // none of its windows ran in this pass
     double s = sum[(size_t)cm * ncb + cb];
     int n = 0;
     for (int i = lo; i <= hi; ++i) {
         const int d = j - (int)(((int64_t)512 * i + 5) / 10);             // start(i) = round(51.2 i) (no ties: 512 i is even)
         if (d < 0 || d >= 256) continue;
-        const int slot = win_slot[i] - slot_lo;
+        if (win_slot[i] < 0) continue;
+        const int64_t slot = first + win_slot[i];
         if (slot < 0 || slot >= m) continue;
         s += (double)spec[((size_t)slot * 256 + cm) * 256 + d];
         ++n;
@@ -78,12 +89,17 @@ __device__ __forceinline__ double sep_log_power(double y) {
     return a > 30.0 ? a + log1p(-exp(-a)) : log(expm1(a));
 }
 
-// maps [2][ncb][128] = sum / count as float32; gain (nullable) [ncb][128] = max(P_env / (P_env + P_speech), min_gain)
+// maps [2][ncb][128] = sum / count as float32; gain (nullable) [ncb][128] = max(P_env / (P_env + P_speech), min_gain); one such block of
+// each per signal (blockIdx.y)
 __global__ __launch_bounds__(256) void sep_finalize_kernel(const double* __restrict__ sum, const int32_t* __restrict__ count, int ncb,
                                                            float* __restrict__ map, float* __restrict__ gain, int speech_ch, double min_gain) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)ncb * 128) return;
-    const int cb = (int)(idx >> 7), band = (int)(idx & 127);
+    const int cb = (int)(idx >> 7), band = (int)(idx & 127), sig = blockIdx.y;
+    sum += (size_t)sig * 256 * ncb;
+    count += (size_t)sig * ncb;
+    map += (size_t)sig * 256 * ncb;
+    if (gain) gain += (size_t)sig * 128 * ncb;
     const int n = count[cb];
     float y[2];
 #pragma unroll
@@ -165,23 +181,38 @@ __device__ __forceinline__ void sep_fft(float2* buf, int lt, const float2* __res
 
 // Block = ITEMS frames of one channel pair (blockIdx.y): channels 2p and 2p + 1 ride as the real and imaginary parts of one complex FFT
 // (the gain is real and even in q, so the two stay apart).  out[rec][pair][N] = synthesis-windowed frame / (1.5 N), ready to gather.
-template <int N>
-__global__ __launch_bounds__(256) void sep_stft_kernel(const unsigned char* __restrict__ pcm, int format, int channels, int64_t frames,
-                                                       const SepFrame* __restrict__ fr, int n_fr, int hop, const float* __restrict__ gain,
-                                                       const SepBand* __restrict__ band, const float2* __restrict__ tw,
-                                                       const float* __restrict__ win, float gain_hi, float2* __restrict__ out) {
+//
+// EACH (ss_separate_pcm_channels): the two channels have gains of their own, Ga and Gb, from the tables gain + c gain_cs; both are real and
+// even in q, so with A, B the channels' spectra, Z = A + iB and A[q] = (Z[q] + conj(Z[N - q])) / 2, iB[q] = (Z[q] - conj(Z[N - q])) / 2:
+//   Ga A + Gb iB = S Z[q] + D conj(Z[N - q]),  S = (Ga + Gb) / 2,  D = (Ga - Gb) / 2
+// -- one thread per pair (q, N - q), in place (q = 0 and N / 2 pair with themselves).  Ga == Gb: D = 0 adds an exact zero, S = Ga, the
+// frame is the mix form's.  An unpaired last channel takes Gb := Ga.  LDS: two rows of band gains per frame in place of one.
+// The two forms are launched (and recorded) as sep_stft_kernel<N> and sep_stft_each_kernel<N>; gain_cs is unused by the first.
+template <int N, bool EACH>
+__global__ __launch_bounds__(256) void sep_stft_form_kernel(const unsigned char* __restrict__ pcm, int format, int channels, int64_t frames,
+                                                            const SepFrame* __restrict__ fr, int n_fr, int hop, const float* __restrict__ gain,
+                                                            const SepBand* __restrict__ band, const float2* __restrict__ tw,
+                                                            const float* __restrict__ win, float gain_hi, float2* __restrict__ out,
+                                                            size_t gain_cs) {
     using G = SepGeomT<N>;
     extern __shared__ float2 sep_lds[];
+    constexpr int GROWS = EACH ? 2 : 1;
     const int item = threadIdx.x / G::T, lt = threadIdx.x % G::T;
     float2* buf = sep_lds + item * G::PITCH;
-    float* gt = (float*)(sep_lds + G::ITEMS * G::PITCH) + item * 128;
+    float* gt = (float*)(sep_lds + G::ITEMS * G::PITCH) + item * (128 * GROWS);
     const int64_t rec = (int64_t)blockIdx.x * G::ITEMS + item;
     const bool valid = rec < n_fr;
     const int pair = blockIdx.y, npairs = gridDim.y, c0 = 2 * pair, c1 = 2 * pair + 1;
     SepFrame f{0, 0, 0, 0.f, 0};
     if (valid) f = fr[rec];
+    if constexpr (EACH) gain += (size_t)c0 * gain_cs;
     for (int m = lt; m < 128; m += G::T)                         // band gains at this frame's time: linear between two bins
         gt[m] = valid ? (1.0f - f.alpha) * gain[(size_t)f.cb0 * 128 + m] + f.alpha * gain[(size_t)f.cb1 * 128 + m] : 0.f;
+    if constexpr (EACH) {
+        const float* gain1 = gain + (c1 < channels ? gain_cs : 0);
+        for (int m = lt; m < 128; m += G::T)
+            gt[128 + m] = valid ? (1.0f - f.alpha) * gain1[(size_t)f.cb0 * 128 + m] + f.alpha * gain1[(size_t)f.cb1 * 128 + m] : 0.f;
+    }
     const int64_t base = f.k * hop - N / 2;
     for (int n = lt; n < N; n += G::T) {
         const int64_t s = base + n;
@@ -195,11 +226,24 @@ __global__ __launch_bounds__(256) void sep_stft_kernel(const unsigned char* __re
     }
     __syncthreads();
     sep_fft<N>(buf, lt, tw);
-    for (int q = lt; q < N; q += G::T) {                         // X[q] g(q), conjugated: the inverse FFT is conj(FFT(conj(.))) / N
-        const SepBand bd = band[q <= N / 2 ? q : N - q];
-        const float g = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
-        const float2 X = buf[sep_pad(q)];
-        buf[sep_pad(q)] = make_float2(X.x * g, -X.y * g);
+    if constexpr (EACH) {
+        for (int q = lt; q <= N / 2; q += G::T) {                // the pair (q, N - q), conjugated as below
+            const SepBand bd = band[q];
+            const float ga = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
+            const float gb = bd.m0 < 0 ? gain_hi : bd.w0 * gt[128 + bd.m0] + bd.w1 * gt[128 + bd.m1];
+            const float S = 0.5f * (ga + gb), D = 0.5f * (ga - gb);
+            const int r = (N - q) & (N - 1);
+            const float2 Zq = buf[sep_pad(q)], Zr = buf[sep_pad(r)];
+            buf[sep_pad(q)] = make_float2(S * Zq.x + D * Zr.x, -(S * Zq.y - D * Zr.y));
+            if (r != q) buf[sep_pad(r)] = make_float2(S * Zr.x + D * Zq.x, -(S * Zr.y - D * Zq.y));
+        }
+    } else {
+        for (int q = lt; q < N; q += G::T) {                     // X[q] g(q), conjugated: the inverse FFT is conj(FFT(conj(.))) / N
+            const SepBand bd = band[q <= N / 2 ? q : N - q];
+            const float g = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
+            const float2 X = buf[sep_pad(q)];
+            buf[sep_pad(q)] = make_float2(X.x * g, -X.y * g);
+        }
     }
     __syncthreads();
     sep_fft<N>(buf, lt, tw);
@@ -390,51 +434,58 @@ static int sep_tables(ss_ctx* c, int sr, SepTables** out) {
 
 // Step 1 (+ 2): the spec head over the windows win_ranges (merged, ascending) of file fid, averaged over the bins bin_ranges (merged,
 // ascending) -> st.d_map [2][ncb][128]; with gains (params non-null): st.d_gain [ncb][128].  Returns SS_ERR_RANGE when an f16x2 pass
-// left the f16 range.
-static int sep_run_maps(ss_ctx* c, int fid, int64_t W, const std::vector<std::pair<int64_t, int64_t>>& bin_ranges,
+// left the f16 range.  nsig > 1 (ss_separate_pcm_channels): the same for each of the files fid .. fid + nsig - 1, whose windows follow
+// one another in one run list -- a pass ends where the chunk is full, not where a signal ends -- -> d_map [nsig][2][ncb][128],
+// d_gain [nsig][ncb][128].
+static int sep_run_maps(ss_ctx* c, int fid, int nsig, int64_t W, const std::vector<std::pair<int64_t, int64_t>>& bin_ranges,
                         const std::vector<std::pair<int64_t, int64_t>>& win_ranges, const ss_separation_params* params, int64_t& ncb_out) {
     SepState& st = sep_state(c);
     std::vector<int32_t> cbin, slot((size_t)W, -1);
     for (auto& r : bin_ranges) for (int64_t j = r.first; j <= r.second; ++j) cbin.push_back((int32_t)j);
     std::vector<int64_t> off;
-    const FileRec& f = c->files[fid];
-    for (auto& r : win_ranges)
-        for (int64_t i = r.first; i <= r.second; ++i) { slot[i] = (int32_t)off.size(); off.push_back(f.off + i * SS_STEP_SAMPLES); }
-    const int ncb = (int)cbin.size(), nw = (int)off.size();
+    for (int s = 0; s < nsig; ++s) {
+        const FileRec& f = c->files[fid + s];
+        int32_t t = 0;
+        for (auto& r : win_ranges)
+            for (int64_t i = r.first; i <= r.second; ++i) { slot[i] = t++; off.push_back(f.off + i * SS_STEP_SAMPLES); }
+    }
+    if (off.size() > (size_t)INT32_MAX) return fail(c, SS_ERR_ARG, "separation: too many windows");
+    const int ncb = (int)cbin.size(), nw_all = (int)off.size(), nw = nw_all / nsig;
     ncb_out = ncb;
     if (ncb == 0 || nw == 0) return SS_OK;
+    const size_t ns = (size_t)nsig;
     int rc;
     if ((rc = ensure(c, &st.d_cbin, &st.cbin_cap, (size_t)ncb))) return rc;
     if ((rc = ensure(c, &st.d_slot, &st.slot_cap, (size_t)W))) return rc;
-    if ((rc = ensure(c, &st.d_sum, &st.sum_cap, (size_t)ncb * 256))) return rc;
-    if ((rc = ensure(c, &st.d_count, &st.count_cap, (size_t)ncb))) return rc;
-    if ((rc = ensure(c, &st.d_map, &st.map_cap, (size_t)ncb * 256))) return rc;
-    if (params && (rc = ensure(c, &st.d_gain, &st.gain_cap, (size_t)ncb * 128))) return rc;
+    if ((rc = ensure(c, &st.d_sum, &st.sum_cap, ns * ncb * 256))) return rc;
+    if ((rc = ensure(c, &st.d_count, &st.count_cap, ns * ncb))) return rc;
+    if ((rc = ensure(c, &st.d_map, &st.map_cap, ns * ncb * 256))) return rc;
+    if (params && (rc = ensure(c, &st.d_gain, &st.gain_cap, ns * ncb * 128))) return rc;
     HIPCHK(c, hipMemcpyAsync(st.d_cbin, cbin.data(), (size_t)ncb * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(st.d_slot, slot.data(), (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(st.d_sum, 0, (size_t)ncb * 256 * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(st.d_count, 0, (size_t)ncb * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.d_sum, 0, ns * ncb * 256 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.d_count, 0, ns * ncb * 4, c->stream));
     if ((rc = upload_winoff(c, off))) return rc;                  // (synchronises: cbin, slot and off are free again)
-    const int ch = std::min(nw, c->chunk);
+    const int ch = std::min(nw_all, c->chunk);
     if ((rc = ensure_workspace(c, ch))) return rc;
     if ((rc = ensure(c, &c->d_logits, &c->logits_cap, (size_t)ch * 256))) return rc;
     if ((rc = ensure(c, &c->d_spec, &c->spec_cap, (size_t)ch * 2 * 32768))) return rc;
     c->logits_valid = false;
     if ((rc = range_clear(c, c->stream))) return rc;
-    for (int p0 = 0; p0 < nw; p0 += ch) {
-        const int m = std::min(ch, nw - p0);
+    for (int p0 = 0; p0 < nw_all; p0 += ch) {
+        const int m = std::min(ch, nw_all - p0);
         if ((rc = forward_chunk(c, c->ws[0], c->stream, c->d_arena, c->d_winoff + p0, m, c->d_logits, c->d_spec))) return rc;
-        ScopedLaunch sl(c, c->stream, "sep_accumulate_kernel", 256.0 * ncb * 6, (double)ncb * 256 * 16);
-        hipLaunchKernelGGL(sep_accumulate_kernel, dim3((unsigned)((ncb + 255) / 256), 256), dim3(256), 0, c->stream, c->d_spec, p0, m, st.d_slot,
-                           (int)W, st.d_cbin, ncb, st.d_sum, st.d_count);
+        ScopedLaunch sl(c, c->stream, "sep_accumulate_kernel", 256.0 * ncb * 6 * nsig, (double)ncb * 256 * 16 * nsig);
+        hipLaunchKernelGGL(sep_accumulate_kernel, dim3((unsigned)((ncb + 255) / 256), 256, (unsigned)nsig), dim3(256), 0, c->stream, c->d_spec, p0, m,
+                           st.d_slot, (int)W, nw, st.d_cbin, ncb, st.d_sum, st.d_count);
         HIPCHK(c, hipGetLastError());
     }
     {
         const int sp = params ? params->speech_channel : 1;
         const double mg = params ? params->min_gain : 0.0;
-        ScopedLaunch sl(c, c->stream, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)));
-        hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256)), dim3(256), 0, c->stream, st.d_sum, st.d_count, ncb,
-                           st.d_map, params ? st.d_gain : nullptr, sp, mg);
+        ScopedLaunch sl(c, c->stream, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)) * nsig);
+        hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256), (unsigned)nsig), dim3(256), 0, c->stream, st.d_sum,
+                           st.d_count, ncb, st.d_map, params ? st.d_gain : nullptr, sp, mg);
         HIPCHK(c, hipGetLastError());
     }
     if (c->d_range_flag) {
@@ -455,49 +506,59 @@ int separation_maps(ss_ctx* c, int fid, int64_t first_bin, int64_t n_bins, float
                                        ") are not all covered by a window (covered: [0, " + std::to_string(nb) + "))");
     int64_t w0, w1, ncb;
     covering_windows(first_bin, first_bin + n_bins - 1, W, w0, w1);
-    int rc = sep_run_maps(c, fid, W, {{first_bin, first_bin + n_bins - 1}}, {{w0, w1}}, nullptr, ncb);
+    int rc = sep_run_maps(c, fid, 1, W, {{first_bin, first_bin + n_bins - 1}}, {{w0, w1}}, nullptr, ncb);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(out, sep_state(c).d_map, (size_t)n_bins * 256 * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
 
+// each: sep_stft_each_kernel<N> with the gain tables gain + c gain_cs; otherwise sep_stft_kernel<N> with the one table
 template <int N>
-static hipError_t launch_sep_stft(const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
-                                  const float* gain, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
+static hipError_t launch_sep_stft(bool each, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
+                                  const float* gain, size_t gain_cs, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
     using G = SepGeomT<N>;
-    const size_t lds = (size_t)G::ITEMS * (G::PITCH * sizeof(float2) + 128 * sizeof(float));
-    static std::atomic<uint64_t> attr_done{0};
-    if (hipError_t e = allow_full_lds((const void*)sep_stft_kernel<N>, attr_done)) return e;
+    const size_t lds = (size_t)G::ITEMS * (G::PITCH * sizeof(float2) + (each ? 256 : 128) * sizeof(float));
+    static std::atomic<uint64_t> attr_done{0}, attr_done_each{0};
     const dim3 grid((unsigned)((n_fr + G::ITEMS - 1) / G::ITEMS), (unsigned)((channels + 1) / 2));
-    hipLaunchKernelGGL(sep_stft_kernel<N>, grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr, hop, gain,
-                       tb.band, tb.tw, tb.win, gain_hi, out);
+    if (each) {
+        if (hipError_t e = allow_full_lds((const void*)sep_stft_form_kernel<N, true>, attr_done_each)) return e;
+        hipLaunchKernelGGL((sep_stft_form_kernel<N, true>), grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr,
+                           hop, gain, tb.band, tb.tw, tb.win, gain_hi, out, gain_cs);
+        return hipGetLastError();
+    }
+    if (hipError_t e = allow_full_lds((const void*)sep_stft_form_kernel<N, false>, attr_done)) return e;
+    hipLaunchKernelGGL((sep_stft_form_kernel<N, false>), grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr,
+                       hop, gain, tb.band, tb.tw, tb.win, gain_hi, out, (size_t)0);
     return hipGetLastError();
 }
 
-static hipError_t launch_sep_stft_n(int N, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
-                                    const float* gain, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
+static hipError_t launch_sep_stft_n(int N, bool each, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr,
+                                    int hop, const float* gain, size_t gain_cs, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
     switch (N) {
-        case 256: return launch_sep_stft<256>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
-        case 512: return launch_sep_stft<512>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
-        case 1024: return launch_sep_stft<1024>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
-        case 2048: return launch_sep_stft<2048>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
-        case 4096: return launch_sep_stft<4096>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
-        case 8192: return launch_sep_stft<8192>(pcm, format, channels, frames, fr, n_fr, hop, gain, tb, gain_hi, out, s);
+        case 256: return launch_sep_stft<256>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
+        case 512: return launch_sep_stft<512>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
+        case 1024: return launch_sep_stft<1024>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
+        case 2048: return launch_sep_stft<2048>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
+        case 4096: return launch_sep_stft<4096>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
+        case 8192: return launch_sep_stft<8192>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
         default: return hipErrorInvalidValue;
     }
 }
 
 static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes of resynthesised frames held at once (pieces / chunks)
 
-int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
-                 const ss_separation_params* params, int16_t* out) {
+// each (ss_separate_pcm_channels, ch > 1): the signals are the channels alone, every channel's STFT gets the gains of its own maps
+static int separate_run(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                        int64_t n_regions, const ss_separation_params* params, int16_t* out) {
     const ss_separation_params prm = params ? *params : separation_defaults();
     SepPlan pl;
     separation_plan(sr, frames, regions, n_regions, pl);
     int rc, fid = -1;
     if ((rc = ss_reset(c))) return rc;
-    if ((rc = ss_add_pcm(c, pcm, format, sr, ch, frames, &fid))) return rc;     // signal in the arena, samples in c->d_pcm
+    if (each) rc = ss_add_pcm_channels(c, pcm, format, sr, ch, frames, &fid);  // signals in the arena, samples in c->d_pcm
+    else rc = ss_add_pcm(c, pcm, format, sr, ch, frames, &fid);
+    if (rc) return rc;
     if (frames == 0) return SS_OK;
     SepState& st = sep_state(c);
     const size_t total = (size_t)frames * ch;
@@ -525,7 +586,7 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
             else wr.emplace_back(g.win_first, g.win_last);
         }
         int64_t ncb = 0;
-        if ((rc = sep_run_maps(c, fid, pl.W, br, wr, &prm, ncb))) return rc;
+        if ((rc = sep_run_maps(c, fid, each ? ch : 1, pl.W, br, wr, &prm, ncb))) return rc;
         // step 3 + 4: pieces of at most `piece` samples, chunks of at most `budget` frames
         SepTables* tb = nullptr;
         if ((rc = sep_tables(c, sr, &tb))) return rc;
@@ -566,14 +627,14 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
         HIPCHK(c, hipMemcpyAsync(st.d_segs, sg.data(), sg.size() * sizeof(SepSeg), hipMemcpyHostToDevice, c->stream));
         const float gain_hi = prm.above_fmax == SS_ABOVE_FMAX_KEEP ? 1.0f : (float)prm.min_gain;
         const int64_t F = (int64_t)std::nearbyint(prm.fade_s * sr);
-        const std::string stft_name = "sep_stft_kernel<" + std::to_string(N) + ">";
+        const std::string stft_name = (each ? "sep_stft_each_kernel<" : "sep_stft_kernel<") + std::to_string(N) + ">";
         for (const Chunk& ck : chunks) {
             {
                 const double lg = std::log2((double)N);
                 ScopedLaunch sl(c, c->stream, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
                                 (double)ck.nrec * npairs * N * (2.0 * pcm_bytes_per_sample(format) + 8.0));
-                HIPCHK(c, launch_sep_stft_n(N, c->d_pcm, format, ch, frames, st.d_frames + ck.rec0, (int)ck.nrec, hop, st.d_gain, *tb, gain_hi,
-                                            st.d_fout, c->stream));
+                HIPCHK(c, launch_sep_stft_n(N, each, c->d_pcm, format, ch, frames, st.d_frames + ck.rec0, (int)ck.nrec, hop, st.d_gain,
+                                            (size_t)ncb * 128, *tb, gain_hi, st.d_fout, c->stream));
             }
             const int64_t all = ck.total * ch;
             ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
@@ -586,6 +647,16 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
     HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // fr / sg and the caller's buffers are free again
     return SS_OK;
+}
+
+int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
+                 const ss_separation_params* params, int16_t* out) {
+    return separate_run(c, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
+int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                          int64_t n_regions, const ss_separation_params* params, int16_t* out) {
+    return separate_run(c, ch > 1, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 }  // namespace ss

@@ -172,6 +172,7 @@ _SIGS = {
     "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
+    "ss_separate_pcm_channels": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
 }
 EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
@@ -459,6 +460,18 @@ class Context:
         out = np.empty((frames, channels), dtype=np.int16)
         self._ck(lib().ss_separate_pcm(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions), C.byref(p),
                                        _ptr(out)))
+        return out
+
+    def separate_pcm_channels(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int, regions, fade_s: float = 0.01,
+                              min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> np.ndarray:
+        """Per-channel separation (ss_separate_pcm_channels): separate_pcm with every channel's gains from its own network passes
+        instead of the mono mix's.  Resets the context (ss_reset + ss_add_pcm_channels): files 0 .. channels - 1 are the channels."""
+        pcm = np.ascontiguousarray(pcm)
+        self._need_bytes(pcm, fmt, channels, frames)
+        p = separation_params(fade_s, min_gain, above_fmax, speech_channel)
+        out = np.empty((frames, channels), dtype=np.int16)
+        self._ck(lib().ss_separate_pcm_channels(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions),
+                                                C.byref(p), _ptr(out)))
         return out
 
     def separation_maps(self, fid: int, first_bin: int, n_bins: int) -> np.ndarray:

@@ -8,6 +8,10 @@ only groups the rows, maps the file and writes header + samples.
 method="separate" keeps the environmental sound of the erased intervals: `ss_separate_pcm` removes only the speech part of
 their spectrum, with the gains of the model's spec head (SpecUNet_2D's spec_output_conv, "env / speech separation"; the
 reference computes it and drops it).  Everything outside the intervals is what method="zero" writes.
+
+channel_mode "each" (settings.hip_channel_mode / SOFTSPOKEN_CHANNELS when not given) makes method="separate" follow per-channel
+detection: a recording of more than one channel goes through `ss_separate_pcm_channels`, every channel's gains from its own network
+passes instead of the mono mix's.
 """
 from __future__ import annotations
 
@@ -21,21 +25,27 @@ class SilenceJob:
     """Signals of the reference's worker (silencer_ui.py:908-916) as plain callbacks; `stop()` as there."""
 
     METHODS = ("zero", "separate")
+    CHANNEL_MODES = ("mix", "each")
 
     def __init__(self, review_df, output_dir, ctx=None, file_started=None, file_complete=None,
                  overall_progress=None, finished=None, method="zero", model=None, fade_s=0.01, min_gain=0.0,
-                 above_fmax="mute", speech_channel=1):
+                 above_fmax="mute", speech_channel=1, channel_mode=None):
         """method "zero": the reference's silencer (ctx: any context, default the shared audio context).  method "separate":
         ss_separate_pcm through `model` (a SpecUNet_2D, e.g. NNDetector(...).model) and its with_range_fallback, so that an input
         the f16x2 mode cannot represent runs in fp32; fade_s, min_gain, above_fmax ("mute" / "keep") and speech_channel are its
-        parameters (include/softspoken.h).  The model's device context must not be in use by another thread meanwhile."""
+        parameters (include/softspoken.h).  The model's device context must not be in use by another thread meanwhile.
+        channel_mode "mix" / "each" (None: voice_activity.channel_mode(), the detector's setting): with method "separate", "each"
+        sends a file of more than one channel through ss_separate_pcm_channels; method "zero" has no use for it."""
         if method not in self.METHODS:
             raise ValueError(f"method must be one of {self.METHODS}, not {method!r}")
+        if channel_mode is not None and channel_mode not in self.CHANNEL_MODES:
+            raise ValueError(f"channel_mode must be None or one of {self.CHANNEL_MODES}, not {channel_mode!r}")
         if method == "separate" and model is None:
             raise ValueError('method="separate" needs the model (a SpecUNet_2D) whose spec head gives the gains')
         self.review_df, self.output_dir = review_df, output_dir
         self.ctx = ctx
         self.method, self.model = method, model
+        self.channel_mode = channel_mode
         self.sep_params = dict(fade_s=fade_s, min_gain=min_gain, above_fmax=above_fmax, speech_channel=speech_channel)
         self.file_started, self.file_complete = file_started, file_complete
         self.overall_progress, self.finished = overall_progress, finished
@@ -56,6 +66,7 @@ class SilenceJob:
             self._emit(self.finished)
             return self.outputs
         ctx = (self.ctx or voice_activity.audio_context()) if self.method == "zero" else None
+        each = self.method == "separate" and (self.channel_mode or voice_activity.channel_mode()) == "each"
         groups = erase.groupby(['file_path', 'file_name'])
         total, done = len(groups), 0
         for (fpath, fname), rows in groups:
@@ -72,6 +83,10 @@ class SilenceJob:
                 if self.method == "zero":
                     with voice_activity._audio_lock:
                         out = ctx.silence_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames, regions)
+                elif each and info.channels > 1:
+                    out = self.model.with_range_fallback(
+                        lambda c: c.separate_pcm_channels(pcm, info.format, info.sample_rate, info.channels, info.frames, regions,
+                                                          **self.sep_params), key=("separate", src))
                 else:
                     out = self.model.with_range_fallback(
                         lambda c: c.separate_pcm(pcm, info.format, info.sample_rate, info.channels, info.frames, regions,
@@ -91,7 +106,7 @@ class SilenceJob:
 
 
 def silence_files(review_df, output_dir, ctx=None, method="zero", model=None, fade_s=0.01, min_gain=0.0, above_fmax="mute",
-                  speech_channel=1):
+                  speech_channel=1, channel_mode=None):
     """-> list of written paths."""
     return SilenceJob(review_df, output_dir, ctx=ctx, method=method, model=model, fade_s=fade_s, min_gain=min_gain,
-                      above_fmax=above_fmax, speech_channel=speech_channel).run()
+                      above_fmax=above_fmax, speech_channel=speech_channel, channel_mode=channel_mode).run()
