@@ -2,15 +2,16 @@
 //   weights.hip   weights blob -> folded BatchNorm -> MFMA fragment packing, front-end tables      (ss_create's work)
 //   engine.hip    activation workspaces (ss::Workspace), launch sequence of one pass of the U-Net on a workspace and a stream, job halves
 //                 (plan + enqueue / wait), the region scans of an ended run
+//   net.h         the network's graph, stated once: workspace tensors (ss::Act, kActs) and ResBlocks (kBlocks); the arrays below are indexed by it
 //   host.hip      host-only pieces of the path: WAV header walk, window plan, run merger (ss::RunMerger) and regions, CSV text
 //   abi.hip       the C ABI (include/softspoken.h): argument checks, arena, getters, measurement
 // Not part of the C ABI.
 #pragma once
 #include "../../include/softspoken.h"
 #include "kernels.h"
+#include "net.h"
 
 #include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -72,6 +73,8 @@ struct ConvPlan {          // one launch of a ResBlock half
     int Cout = 0, NT = 1, C0 = 0, C1 = 0, R0 = 0, R1 = 0, H = 0, W = 0;
 };
 
+struct BlockPlan { ConvPlan A, B; };    // the two launches of a ResBlock
+
 struct FileRec {
     int64_t off = 0;        // arena offset of the padded signal
     int64_t n = 0;          // samples at 22 050 Hz (unpadded)
@@ -93,12 +96,12 @@ struct SepPlan {
 
 // An activation workspace for `chunk` windows (engine.hip alloc_ws): what one pass of the network writes.  A context has two -- the main
 // one, and the second lane's of a run with several passes.
+struct ActTensor { void* p = nullptr; ActStride s{0u, 0u}; };   // first byte (high plane in f16x2 mode) inside the arena; 16-bit modes: byte order
 struct Workspace {
     int chunk = 0; int64_t bytes = 0;
-    std::map<std::string, void*> act;                     // tensor name -> first byte (high plane in f16x2 mode) inside arena
+    ActTensor t[kActCount];                               // the tensors of net.h, by Act
     void* arena = nullptr;
     int64_t lo_delta = 0;                                 // f16x2: byte distance from a tensor's high plane to its low plane
-    std::map<const void*, ActStride> stride;              // 16-bit modes: a tensor's byte order (kernels.h ActStride), by its first byte
     float* feat = nullptr; float* flat = nullptr;         // front-end features; conv_flatten's row-group partial sums
     int flat_groups = 0;                                  // row groups the last FLAT launch wrote per window into `flat`
 };
@@ -141,7 +144,7 @@ struct ss_ctx {
     void* d_flat_rows = nullptr;                          // conv9s.hip: conv_flatten's filter per mel row as 16x16x32 A fragments (weights.hip pack_flat_rows)
     float *d_spec_w = nullptr, *d_spec_b = nullptr;
     ss::Head1dWeights head{};
-    std::vector<ss::ConvPlan> convs;  // in launch order; pairs (A, B) per ResBlock, conv1_1 has only B
+    ss::BlockPlan convs[ss::kBlockCount];   // by block of net.h's kBlocks (conv1_1 has only B)
     std::vector<void*> owned;        // device allocations to free
     std::vector<void*> user_dev, user_host;   // ss_device_alloc / ss_host_alloc memory the caller has not freed: released with the context
 
@@ -170,12 +173,12 @@ struct ss_ctx {
     int fail_alloc_after = -1;                            // dev build's test hook (ss_debug_fail_workspace_alloc): the n-th workspace allocation from now fails
     int64_t sep_budget = 0;                               // dev build's test hook (ss_debug_set_separation_budget): frames per chunk of ss_separate_pcm; 0: from kSepFrameBytes
     bool split_range_ok = true;                           // f16x2: cleared while packing when a folded weight has no f16 representation
-    // f16x2: power-of-two channel exponents of every activation tensor, by tensor name (weights.hip; all zero in the other modes and under
-    // SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c
-    std::map<std::string, std::vector<int>> act_exp;
+    // f16x2: power-of-two channel exponents of every activation tensor, by Act, then of the features and of conv_flatten's partial sums
+    // (weights.hip; all zero in the other modes and under SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c
+    std::vector<int> act_exp[ss::kDbgCount];
     // the last network pass, for the dev build's ss_debug_activation (kept in both builds: the units shared by the two libraries must see
-    // one layout of this struct): its windows, the index of the workspace it ran on, the tensors it wrote
-    int dbg_n = 0, dbg_ws = 0; std::set<std::string> dbg_written;
+    // one layout of this struct): its windows, the index of the workspace it ran on, the tensors it wrote (bit Act; kDbgFeat, kDbgFlatPart)
+    int dbg_n = 0, dbg_ws = 0; uint64_t dbg_written = 0;
 
     // arena
     float* d_arena = nullptr; size_t arena_cap = 0, arena_used = 0;

@@ -84,7 +84,7 @@ static void free_ws(Workspace& w) {
 }
 
 void free_workspace(ss_ctx* c) {
-    c->dbg_n = 0; c->dbg_ws = 0; c->dbg_written.clear();
+    c->dbg_n = 0; c->dbg_ws = 0; c->dbg_written = 0;
     for (Workspace& w : c->ws) free_ws(w);
 }
 
@@ -93,24 +93,14 @@ static hipError_t ws_malloc(ss_ctx* c, void** p, size_t bytes) {
     return hipMalloc(p, bytes);
 }
 
-// one workspace for n windows, filled in place: arena (+ the tensor table), feature and flatten-partial buffers; the zero headers are
-// written on `stream`.  On failure everything it allocated is freed again (w is empty) and *what names the step.
-struct WsTensor { const char* n; int H, W, C; };
-static const WsTensor kWsTensors[] = {{"h1", 128, 256, 32}, {"c1", 128, 256, 32}, {"p1", 64, 128, 32}, {"h2", 64, 128, 64}, {"c2", 64, 128, 64},
-                                      {"p2", 32, 64, 64},   {"h3", 32, 64, 96},   {"c3", 32, 64, 96},  {"p3", 16, 32, 96},  {"h4", 16, 32, 128},
-                                      {"c4", 16, 32, 128},  {"p4", 8, 16, 128},   {"hb", 8, 16, 128},  {"bott", 8, 16, 128}, {"he", 8, 16, 128},
-                                      {"enc", 8, 16, 128},  {"h6", 16, 32, 96},   {"c6", 16, 32, 96},  {"h7", 32, 64, 64},  {"c7", 32, 64, 64},
-                                      {"h8", 64, 128, 32},  {"c8", 64, 128, 32},  {"h9", 128, 256, 32}, {"c9", 128, 256, 32},
-                                      {"hs", 128, 256, 32}, {"s9", 128, 256, 32},
-                                      // r = residual projection written by A launches that keep it (conv6, conv8, the spec head; every block in fp32 / f16x2)
-                                      {"r2", 64, 128, 64},  {"r3", 32, 64, 96},   {"r4", 16, 32, 128}, {"rb", 8, 16, 128},  {"re", 8, 16, 128},
-                                      {"r6", 16, 32, 96},   {"r7", 32, 64, 64},   {"r8", 64, 128, 32}, {"r9", 128, 256, 32}, {"rs", 128, 256, 32}};
+// one workspace for n windows, filled in place: arena (+ its tensors, net.h's kActs), feature and flatten-partial buffers; the zero headers
+// are written on `stream`.  On failure everything it allocated is freed again (w is empty) and *what names the step.
 static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, Workspace& w, std::string& what) {
     const size_t es = c->prec == kFp32 ? 4 : 2;
     // one arena, one size (the spec head's tensors included): the workspace is sized once per context and chunk
     size_t total = 0;
     std::vector<size_t> offs;
-    for (const WsTensor& t : kWsTensors) {
+    for (const ActInfo& t : kActs) {
         offs.push_back(total + kActHeader);
         total += kActHeader + (((size_t)n * t.H * t.W * t.C * es + 255) & ~(size_t)255);
     }
@@ -127,10 +117,10 @@ static hipError_t alloc_ws(ss_ctx* c, int n, hipStream_t stream, Workspace& w, s
             if (e != hipSuccess) { what = "hipMemsetAsync"; free_ws(w); return e; }
         }
     const bool planar = c->prec == kF16x2 && dev_env("SOFTSPOKEN_LAYOUT", kActChunkPlanar ? 1 : 0) != 0;
-    for (size_t i = 0; i < offs.size(); ++i) {
-        const WsTensor& t = kWsTensors[i];
-        w.act[t.n] = (char*)w.arena + offs[i];
-        if (c->prec != kFp32) w.stride[w.act[t.n]] = act_stride(t.H, t.W, t.C, planar && t.n[0] != 'r');
+    for (int i = 0; i < kActCount; ++i) {
+        const ActInfo& t = kActs[i];
+        w.t[i].p = (char*)w.arena + offs[i];
+        if (c->prec != kFp32) w.t[i].s = act_stride(t.H, t.W, t.C, planar && !t.frag_order);     // (fp32: no byte order, {0, 0})
     }
     w.lo_delta = planes == 2 ? (int64_t)total : 0;
     w.bytes = (int64_t)(total * planes + feat_b + flat_b);
@@ -169,9 +159,6 @@ static bool ensure_lane(ss_ctx* c, int n) {
 // ------------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------------
-struct ConvExtra { const float* first_w = nullptr; const float* first_b = nullptr; const void* flat_w = nullptr; const void* flat_w4 = nullptr; float* flat_part = nullptr; int store_out = 1;
-                   const void* flat_rows = nullptr; };
-
 static int base_dbg() {
     // product build: 32 (raised wave priority inside conv4.hip's MFMA loop: the measured default); dev build: + SOFTSPOKEN_DBG bits, and bit 9 =
     // the ring kernels' side-by-side work order (kernels.h; SOFTSPOKEN_ORDER=0: the sequential one; the product's order is compiled in)
@@ -214,12 +201,12 @@ struct StageStamps {
 #endif
 
 // One conv launch with its bookkeeping: the stat entry "<instantiation as rocprofv3 prints it>/<layer>", the dev build's stage stamps
-// when this layer's are asked for, the launch on `stream`, its error.  issued: as ScopedLaunch's issued_macs.
-template <typename Launch>
+// when this layer's are asked for (stamped: the form takes them), the launch on `stream`, its error.  issued: as ScopedLaunch's issued_macs.
+template <typename LaunchFn>
 static int conv_launch(ss_ctx* c, hipStream_t stream, const char* variant, const std::string& layer, ConvArgs& a, double flops, double bytes,
-                       double issued, Launch&& launch) {
+                       double issued, bool stamped, LaunchFn&& launch) {
     StageStamps stamps;
-    if (int rc = stamps.begin(c, stream, layer, a)) return rc;
+    if (stamped) if (int rc = stamps.begin(c, stream, layer, a)) return rc;
     {
         ScopedLaunch sl(c, stream, std::string(variant) + "/" + layer, flops, bytes, issued);
         HIPCHK(c, launch(a));
@@ -227,249 +214,248 @@ static int conv_launch(ss_ctx* c, hipStream_t stream, const char* variant, const
     return stamps.end(c, stream, layer, a.N);
 }
 
-// the tensors a pass writes, by name (dev build: ss_debug_activation refuses the others)
-static void mark_written(ss_ctx* c, const Workspace& ws, const void* p) {
-#ifdef SS_DEVBUILD
-    if (!p) return;
-    for (const auto& kv : ws.act)
-        if (kv.second == p) { c->dbg_written.insert(kv.first); return; }
-#else
-    (void)c; (void)ws; (void)p;
-#endif
+// The kernel forms that can serve a launch of a ResBlock half
+enum Form {
+    kNoForm,            // no launch
+    kConv2,             // conv2.hip: fp32, and bf16 under SOFTSPOKEN_CONV4=0
+    kConv4,             // conv4.hip: bf16 / f16x2
+    kConv4UpsPlain,     // conv4_ups.hip, plain A launch: the upsampled input half at low resolution, four pre-summed taps per parity class
+    kConv4UpsRing,      // conv4_ups.hip, ring form: the same for the A launch that also writes r
+    kConv2Ups,          // conv2_ups.hip: the same idea on the fp32 matrix instruction
+    kConv1Stream16,     // conv1s.hip: conv1_1 as a row-streaming kernel, 16-pixel form
+    kConv1Stream32,     // ... its 32-column form (development build, SOFTSPOKEN_C1S_FORM=32)
+    kConv9aStream,      // conv9a.hip: conv9_1.A row-streaming
+    kConv9Stream        // conv9s.hip: conv9_1.B row-streaming, conv_flatten in its epilogue
+};
+struct Launch { Form form = kNoForm; ConvArgs a{}; };
+// How one block runs.  proj: "projection in B" (conv4.hip RP) -- A writes h alone, B reads h and the centre pixels of the block input;
+// otherwise A + r / B -- A computes h and the residual projection r, B computes the block output from h and adds r.  conv1_1 has no A.
+// B2: development build, SOFTSPOKEN_C1S=2: conv4.hip's form of conv1_1 runs as well, behind the stream form -- an A/B aid.
+struct BlockRun { bool proj = false; Launch A, B, B2; };
+
+static int prec4(const ss_ctx* c) { return c->prec == kF16x2 ? 2 : 1; }
+static int ups32_mtw(const ConvPlan& p) { return dev_env("SOFTSPOKEN_UPS32_MTW", 2) == 2 && p.ups32_nt < 3 ? 2 : 1; }
+
+// The ConvArgs of block bi's two launches for n windows, in either way of running it -- the one place where tensors become ConvArgs fields.
+// (The form chosen below may still swap in its own weight banks.)
+static void fill_args(const ss_ctx* c, const Workspace& ws, int bi, int n, bool with_spec, BlockRun& r) {
+    const Block& k = kBlocks[bi];
+    const BlockPlan& p = c->convs[bi];
+    auto T = [&](Act t) { return t == kNoAct ? ActTensor() : ws.t[t]; };
+    // (conv1_1's B reads the fp32 features, not an h1 tensor: h1 only exists on chip)
+    const ActTensor x0 = T(k.x0), x1 = T(k.x1), h = T(k.first_in_loader ? kNoAct : k.h), rr = T(k.r), y = T(k.y), pool = T(k.pool);
+    ConvArgs& a = r.A.a; ConvArgs& b = r.B.a;
+    a = b = ConvArgs{};
+    a.N = b.N = n; a.H = b.H = k.H; a.W = b.W = k.W; a.Cout = b.Cout = k.cout; a.relu = b.relu = 1; a.store_out = b.store_out = 1;
+    a.lo_delta = b.lo_delta = ws.lo_delta; a.range_flag = b.range_flag = c->d_range_flag; a.dbg = b.dbg = base_dbg();
+    a.src0 = x0.p; a.s_src0 = x0.s; a.src1 = x1.p; a.s_src1 = x1.s; a.C0 = k.c0; a.C1 = k.c1; a.out = h.p; a.s_out = h.s; a.bias = p.A.d_bias2;
+    b.src0 = h.p; b.s_src0 = h.s; b.C0 = k.cout; b.out = y.p; b.s_out = y.s; b.pool_out = pool.p; b.s_pool = pool.s; b.wpk = p.B.d_w2;   // B's 3x3 input is h
+    if (r.proj) {
+        a.wpk = p.A.d_w3; a.plain = 1;
+        b.bias = p.B.d_bias3; b.proj_w = p.B.d_proj; b.xp0 = x0.p; b.s_xp0 = x0.s; b.xp1 = x1.p; b.s_xp1 = x1.s; b.C0x = k.c0; b.C1x = k.c1;
+    } else {
+        a.wpk = p.A.d_w2; a.res_out = rr.p; a.res_bias = p.A.d_res_bias;
+        b.bias = p.B.d_bias2; b.res_in = rr.p; b.rank1_w = p.B.d_rank1;
+    }
+    if (k.first_in_loader) { b.first_w = c->d_first_w; b.first_b = c->d_first_b; b.rank1_src = ws.feat; }
+    if (k.flat_in_b) { b.flat_w = r.proj ? nullptr : c->d_flat_frag; b.flat_w4 = c->d_flat_frag4; b.flat_part = ws.flat; b.store_out = with_spec ? 1 : 0; }
 }
 
-// byte order of the workspace tensor at p for a 16-bit launch; false: a tensor the workspace does not know (never after ensure_workspace)
-static bool stride_of(const Workspace& ws, const void* p, ActStride& s) {
-    s = ActStride{0u, 0u};
-    if (!p) return true;
-    const auto it = ws.stride.find(p);
-    if (it == ws.stride.end()) return false;
-    s = it->second;
+// the tile forms every launch can end on; false: none (f16x2 has only conv4.hip)
+static bool choose_tile(const ss_ctx* c, const ConvPlan& p, Launch& l) {
+    if (c->prec != kFp32 && dev_env("SOFTSPOKEN_CONV4", 1) && conv_v4_supports(l.a, p.NT, c->num_cus, prec4(c))) l.form = kConv4;
+    else if (c->prec != kF16x2) l.form = kConv2;
+    return l.form != kNoForm;
+}
+
+// an A launch that also writes r: the decoder forms with the upsampled input half at low resolution first
+static bool choose_A(const ss_ctx* c, const ConvPlan& p, Launch& l) {
+    Launch u = l;
+    if (c->prec == kF16x2 && p.d_w_upsr) {
+        u.form = kConv4UpsRing; u.a.wpk = p.d_w_upsr;
+        if (conv_upsr_supports(u.a, c->num_cus)) { l = u; return true; }
+    }
+    if (c->prec == kFp32 && p.d_w_ups32 && l.a.src1) {
+        u.form = kConv2Ups; u.a.wpk = p.d_w_ups32;
+        if (conv_ups32_supports(u.a, p.ups32_nt, ups32_mtw(p), c->num_cus)) { l = u; return true; }
+    }
+    return choose_tile(c, p, l);
+}
+
+// a B launch that adds r (conv1_1: the rank-1 term): conv1_1 has its row-streaming form, the others the tile forms alone
+static bool choose_B(const ss_ctx* c, const Block& k, const ConvPlan& p, BlockRun& r) {
+    if (c->prec == kF16x2 && k.first_in_loader && p.d_w_s16 && dev_env("SOFTSPOKEN_C1S", 1)) {
+        Launch s = r.B;
+        s.form = dev_env("SOFTSPOKEN_C1S_FORM", 16) == 32 && p.d_w_s1 ? kConv1Stream32 : kConv1Stream16;
+        s.a.wpk = s.form == kConv1Stream16 ? p.d_w_s16 : p.d_w_s1;
+        s.a.relu = 1 | (dev_env("SOFTSPOKEN_C1S_ABLATE", 0) << 4);    // (dev build, timing only: 1 no stores, 2 no second-conv products, 4 no pooled rows)
+        s.a.plain = p.s1_range_proven && dev_env("SOFTSPOKEN_C1S_TRACK", 0) == 0;
+        if (conv1_stream_supports(s.a)) {
+            if (dev_env("SOFTSPOKEN_C1S", 1) == 2) { r.B2 = r.B; if (!choose_tile(c, p, r.B2)) return false; }
+            r.B = s;
+            return true;
+        }
+    }
+    return choose_tile(c, p, r.B);
+}
+
+// "projection in B" (bf16, and f16x2 for the blocks conv4.hip has the form for); false: conv4.hip has no instantiation for this block, it
+// runs as A + r / B.  (It gives up when conv4.hip cannot serve B even where conv9s.hip could.)
+static bool choose_proj(const ss_ctx* c, const Block& k, const BlockPlan& p, BlockRun& r) {
+    if (!p.A.d_w3 || !p.B.d_proj) return false;
+    const int cus = c->num_cus;
+    // f16x2: the A launch with the upsampled input half at low resolution where that form exists -- conv9_1.A
+    Launch ups = r.A;
+    ups.form = kConv4UpsPlain; ups.a.wpk = p.A.d_w_ups;
+    const bool has_ups = c->prec == kF16x2 && p.A.d_w_ups && ups.a.src1 && conv_ups_supports(ups.a, cus);
+    if ((!has_ups && !conv_v4_supports(r.A.a, p.A.NT, cus, prec4(c))) || !conv_v4_supports(r.B.a, p.B.NT, cus, prec4(c))) return false;
+    r.A.form = r.B.form = kConv4;
+    if (has_ups) {
+        // conv9_1.A: the row-streaming form (conv9a.hip) -- the same pre-summed taps on stream16.h's core, no patch images, no barriers.
+        // (Development build, SOFTSPOKEN_C9A=0: conv4_ups.hip's form; SOFTSPOKEN_UPS=0 switches both off.)
+        Launch s = r.A;
+        s.form = kConv9aStream; s.a.wpk = p.A.d_w_a16; s.a.wpk_b = p.A.d_w_ups16;
+        const bool stream = p.A.d_w_a16 && p.A.d_w_ups16 && dev_env("SOFTSPOKEN_C9A", 1) && conv9a_stream_supports(s.a) &&
+                            conv9a_stream_rows_ok(dev_env("SOFTSPOKEN_C9A_ROWS", 32));
+        r.A = stream ? s : ups;
+    }
+    if (c->prec == kF16x2 && k.flat_in_b && c->d_flat_rows && p.B.d_w_s16 && p.B.d_proj_s16 && dev_env("SOFTSPOKEN_C9S", 1)) {
+        // conv9_1.B: the row-streaming form (conv9s.hip), in the mask-only pass and in the spec pass alike (store_out): the two passes'
+        // flatten sums are the same bits.  (Development build, SOFTSPOKEN_C9S=0: conv4.hip's form.)
+        Launch s = r.B;
+        s.form = kConv9Stream; s.a.wpk = p.B.d_w_s16; s.a.proj_w = p.B.d_proj_s16; s.a.flat_w4 = c->d_flat_rows;
+        if (conv9_stream_supports(s.a) && conv9_stream_rows_ok(dev_env("SOFTSPOKEN_C9S_ROWS", 32))) r.B = s;
+    }
     return true;
 }
 
-// One launch of a ResBlock half.  A launches (r_out) compute h and the residual projection r from the block input
-// (x0 [+ upsampled x1]); B launches (r_in) compute the block output from h and add r.
-static int run_conv2(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPlan& p, int n, const void* x0, const void* x1, void* out, void* pool,
-                     void* r_out, const void* r_in, const float* feat, const ConvExtra& ex = ConvExtra()) {
-    const bool isA = r_out != nullptr;
-    if (ex.store_out) mark_written(c, ws, out);
-    mark_written(c, ws, pool); mark_written(c, ws, r_out);
-    ConvArgs a{};
-    a.first_w = ex.first_w; a.first_b = ex.first_b; a.flat_w = ex.flat_w; a.flat_w4 = ex.flat_w4; a.flat_part = ex.flat_part; a.store_out = ex.store_out;
-    a.src0 = x0; a.src1 = x1; a.wpk = p.d_w2; a.bias = p.d_bias2;
-    a.res_out = r_out; a.res_bias = p.d_res_bias; a.res_in = r_in;
-    a.rank1_src = feat; a.rank1_w = p.d_rank1; a.out = out; a.pool_out = pool;
-    a.N = n; a.H = p.H; a.W = p.W; a.Cout = p.Cout; a.relu = 1;
-    a.lo_delta = ws.lo_delta; a.range_flag = c->d_range_flag;
-    if (c->prec != kFp32 && !(stride_of(ws, x0, a.s_src0) && stride_of(ws, x1, a.s_src1) && stride_of(ws, out, a.s_out) && stride_of(ws, pool, a.s_pool)))
-        return fail(c, SS_ERR_STATE, "no byte order for a tensor of " + p.name);
-    if (isA) { a.C0 = p.C0; a.C1 = p.C1; } else { a.C0 = p.Cout; a.C1 = 0; }       // B's 3x3 input is h
-    a.dbg = base_dbg();
-    const double cin = a.C0 + a.C1;
-    const double macs = (double)n * p.H * p.W * p.Cout * (9.0 * cin + (isA ? cin : 0.0) + (feat ? 1 : 0)) +
-                        (ex.first_w ? (double)n * p.H * p.W * 32 * 9 : 0.0) + (ex.flat_part ? (double)n * p.H * p.W * 32 * 4 : 0.0);
-    const double es = c->prec == kBf16 ? 2 : 4;           // bytes per stored activation value (f16x2: two f16 planes)
-    // (the fused conv1_1 launch reads the fp32 features, not an h1 tensor: h1 only exists in LDS)
-    const double bytes = (double)n * p.H * p.W * es * ((ex.first_w ? 4.0 / es : a.C0) + a.C1 / 4.0 + (ex.flat_part && !ex.store_out ? 0 : p.Cout) + (isA || r_in ? p.Cout : 0) + (pool ? p.Cout / 4.0 : 0));
-    const int prec4 = c->prec == kF16x2 ? 2 : 1;
-    const int cus = c->num_cus;
-    // (FLOPs booked: the layer's algorithmic ones, as for every launch; issued < 0: the same multiply-adds are issued)
-    auto go = [&](const char* variant, ConvArgs& x, double issued, auto&& launch) { return conv_launch(c, stream, variant, p.name, x, 2.0 * macs, bytes, issued, launch); };
-    // the decoder forms with the upsampled input half at low resolution issue 9 C0 + 4 C1 multiply-adds per output value (+ cin: the 1x1 projection)
-    const double issued_ups = (double)n * p.H * p.W * p.Cout * (9.0 * p.C0 + 4.0 * p.C1 + cin);
-    if (isA && c->prec == kF16x2 && p.d_w_upsr) {  // decoder A launches: conv4_ups.hip, ring form
-        ConvArgs au = a;
-        au.wpk = p.d_w_upsr;
-        if (conv_upsr_supports(au, cus)) return go(conv_upsr_variant(), au, issued_ups, [&](ConvArgs& x) { return launch_conv3x3_upsr(x, cus, stream); });
+// How block bi runs for n windows and which form serves each of its launches, with their arguments; nothing is launched.  false: a launch
+// has no form (its Launch is left at kNoForm).
+static bool choose_block(const ss_ctx* c, const Workspace& ws, int bi, int n, bool with_spec, BlockRun& r) {
+    const Block& k = kBlocks[bi];
+    const BlockPlan& p = c->convs[bi];
+    // (running A and B over Infinity-Cache-sized sub-chunks of windows was measured twice: no gain)
+    // Blocks whose input is narrower than their output (encoder) move fewer bytes when B recomputes the 1x1 projection from
+    // the block input than when A writes r and B reads it back; conv4.hip has that form for the blocks where it pays.
+    if (c->prec != kFp32 && !k.spec_only && dev_env("SOFTSPOKEN_CONV4", 1) && dev_env("SOFTSPOKEN_RPROJ", 1)) {
+        r.proj = true;
+        fill_args(c, ws, bi, n, with_spec, r);
+        if (choose_proj(c, k, p, r)) return true;
+        r = BlockRun();
     }
-    if (isA && c->prec == kFp32 && p.d_w_ups32 && x1) {   // fp32 decoder A launches: the same idea on the fp32 matrix instruction (conv2_ups.hip)
-        ConvArgs au = a;
-        au.wpk = p.d_w_ups32;
-        const int nt = p.ups32_nt, mtw = dev_env("SOFTSPOKEN_UPS32_MTW", 2) == 2 && nt < 3 ? 2 : 1;
-        if (conv_ups32_supports(au, nt, mtw, cus))
-            return go(conv_ups32_variant(nt, mtw), au, issued_ups, [&](ConvArgs& x) { return launch_conv3x3_ups32(x, nt, mtw, cus, stream); });
-    }
-    if (c->prec == kF16x2 && ex.first_w && p.d_w_s16 && dev_env("SOFTSPOKEN_C1S", 1)) {   // conv1_1: the row-streaming form (conv1s.hip)
-        ConvArgs as = a;
-        const int form = dev_env("SOFTSPOKEN_C1S_FORM", 16) == 32 && p.d_w_s1 ? 32 : 16;     // (32: the development build's other form)
-        as.wpk = form == 16 ? p.d_w_s16 : p.d_w_s1;
-        as.relu = 1 | (dev_env("SOFTSPOKEN_C1S_ABLATE", 0) << 4);    // (dev build, timing only: 1 no stores, 2 no second-conv products, 4 no pooled rows)
-        as.plain = p.s1_range_proven && dev_env("SOFTSPOKEN_C1S_TRACK", 0) == 0;
-        if (conv1_stream_supports(as)) {
-            const int rows = dev_env("SOFTSPOKEN_C1S_ROWS", 32);
-            if (int rc = go(conv1_stream_variant(as, form), as, -1.0, [&](ConvArgs& x) { return launch_conv1_stream(x, form, rows, cus, stream); })) return rc;
-            if (dev_env("SOFTSPOKEN_C1S", 1) != 2) return SS_OK;     // (dev build, 2: conv4.hip's form runs as well, behind it -- an A/B aid)
-        }
-    }
-    if (c->prec != kFp32 && dev_env("SOFTSPOKEN_CONV4", 1) && conv_v4_supports(a, p.NT, cus, prec4)) {   // conv4.hip: bf16 / f16x2 launches
-        if (int rc = go(conv_v4_variant(a, p.NT, cus, prec4), a, -1.0, [&](ConvArgs& x) { return launch_conv3x3_v4(x, p.NT, cus, prec4, stream); })) return rc;
-        if (ex.flat_part) ws.flat_groups = conv_v4_flat_groups();
-        return SS_OK;
-    }
-    if (c->prec == kF16x2) return fail(c, SS_ERR_STATE, "f16x2: no kernel form for " + p.name);
-    if (ex.flat_part) ws.flat_groups = conv_v2_flat_groups(c->bf16);
-    return go(conv_v2_variant(a, c->bf16, p.NT, cus), a, -1.0, [&](ConvArgs& x) { return launch_conv3x3_v2(x, c->bf16, p.NT, cus, stream); });
+    fill_args(c, ws, bi, n, with_spec, r);
+    if (!k.first_in_loader && !choose_A(c, p.A, r.A)) return false;
+    return choose_B(c, k, p.B, r);
 }
 
-// A ResBlock in the "projection in B" form (conv4.hip RP; bf16, and f16x2 for the blocks conv4.hip has the form for): A writes h
-// alone, B reads h and the centre pixels of the block input.  Returns 1 when conv4.hip has no instantiation for this block (the
-// caller then uses A + r / B).
-static int run_block_proj(ss_ctx* c, Workspace& ws, hipStream_t stream, const ConvPlan& pa, const ConvPlan& pb, int n, const void* x0, const void* x1,
-                          void* h, void* out, void* pool, const ConvExtra& ex = ConvExtra()) {
-    if ((c->prec != kBf16 && c->prec != kF16x2) || !pa.d_w3 || !pb.d_proj) return 1;
-    const int prec4 = c->prec == kF16x2 ? 2 : 1;
+// ---- what a launch is booked with: functions of the block, the launch (A or B), the way the block runs, the form and n ----
+// multiply-adds of the layer as the reference computes it (FLOPs booked: twice these, whatever the form issues)
+static double launch_macs(const Block& k, bool isA, bool proj, int n) {
+    const double px = (double)n * k.H * k.W, cin = k.c0 + k.c1;
+    if (isA) return px * k.cout * (9.0 * cin + (proj ? 0.0 : cin));
+    return px * k.cout * (9.0 * k.cout + (proj ? cin : 0.0) + (k.first_in_loader ? 1 : 0)) + (k.first_in_loader ? px * 32 * 9 : 0.0) +
+           (k.flat_in_b ? px * 32 * 4 : 0.0);
+}
+// bytes moved; es: bytes per stored activation value (f16x2: two f16 planes).  A reads the block input (its upsampled half at a quarter of
+// the pixels) and writes h (+ r); B reads h (conv1_1: the fp32 features) and r or the block input, and writes y (store_y) and the pooled y.
+static double launch_bytes(const Block& k, bool isA, bool proj, int n, double es, bool store_y) {
+    const double px = (double)n * k.H * k.W, x = k.c0 + k.c1 / 4.0;
+    if (isA) return px * es * (x + k.cout + (proj ? 0 : k.cout));
+    return px * es * ((k.first_in_loader ? 4.0 / es : k.cout) + (proj ? x : k.r != kNoAct ? k.cout : 0) + (store_y ? k.cout : 0) + (k.pool != kNoAct ? k.cout / 4.0 : 0));
+}
+// multiply-adds the form issues when they are not the layer's (< 0: the same).  The decoder forms with the upsampled input half at low
+// resolution issue 9 C0 + 4 C1 per output value (+ cin: the 1x1 projection, where A computes it); the stream forms count their own.
+static double launch_issued(const Block& k, Form f, int n) {
+    const double px = (double)n * k.H * k.W;
+    switch (f) {
+        case kConv4UpsRing: case kConv2Ups: return px * k.cout * (9.0 * k.c0 + 4.0 * k.c1 + (k.c0 + k.c1));
+        case kConv4UpsPlain: return px * k.cout * (9.0 * k.c0 + 4.0 * k.c1);
+        case kConv9aStream: return conv9a_stream_issued_macs(n);
+        case kConv9Stream: return conv9_stream_issued_macs(n);
+        default: return -1.0;
+    }
+}
+// row groups per window that the form serving conv9_1.B writes into the flatten's partial sums
+static int flat_groups_of(const ss_ctx* c, Form f) {
+    return f == kConv9Stream ? conv9_stream_flat_groups(dev_env("SOFTSPOKEN_C9S_ROWS", 32)) : f == kConv4 ? conv_v4_flat_groups() : conv_v2_flat_groups(c->bf16);
+}
+
+// one chosen launch, under its stat name "<instantiation>/<layer>"
+static int launch_form(ss_ctx* c, hipStream_t stream, const ConvPlan& p, Launch& l, double flops, double bytes, double issued) {
     const int cus = c->num_cus;
+    // (conv4_ups.hip's plain form takes no stage stamps)
+    auto go = [&](const char* variant, auto&& launch) { return conv_launch(c, stream, variant, p.name, l.a, flops, bytes, issued, l.form != kConv4UpsPlain, launch); };
+    switch (l.form) {
+        case kConv2: return go(conv_v2_variant(l.a, c->bf16, p.NT, cus), [&](ConvArgs& x) { return launch_conv3x3_v2(x, c->bf16, p.NT, cus, stream); });
+        case kConv4: return go(conv_v4_variant(l.a, p.NT, cus, prec4(c)), [&](ConvArgs& x) { return launch_conv3x3_v4(x, p.NT, cus, prec4(c), stream); });
+        case kConv4UpsPlain: return go(conv_ups_variant(), [&](ConvArgs& x) { return launch_conv3x3_ups(x, cus, stream); });
+        case kConv4UpsRing: return go(conv_upsr_variant(), [&](ConvArgs& x) { return launch_conv3x3_upsr(x, cus, stream); });
+        case kConv2Ups: return go(conv_ups32_variant(p.ups32_nt, ups32_mtw(p)), [&](ConvArgs& x) { return launch_conv3x3_ups32(x, p.ups32_nt, ups32_mtw(p), cus, stream); });
+        case kConv1Stream16: case kConv1Stream32: {
+            const int form = l.form == kConv1Stream16 ? 16 : 32;
+            return go(conv1_stream_variant(l.a, form), [&](ConvArgs& x) { return launch_conv1_stream(x, form, dev_env("SOFTSPOKEN_C1S_ROWS", 32), cus, stream); });
+        }
+        case kConv9aStream:
+            return go(conv9a_stream_variant(), [&](ConvArgs& x) { return launch_conv9a_stream(x, dev_env("SOFTSPOKEN_C9A_ROWS", 32), dev_env("SOFTSPOKEN_C9A_GRID", 0), cus, stream); });
+        case kConv9Stream:
+            return go(conv9_stream_variant(), [&](ConvArgs& x) { return launch_conv9_stream(x, dev_env("SOFTSPOKEN_C9S_ROWS", 32), dev_env("SOFTSPOKEN_C9S_GRID", 0), cus, stream); });
+        case kNoForm: break;
+    }
+    return fail(c, SS_ERR_STATE, "no kernel form chosen for " + p.name);
+}
+
+// Block bi of net.h's kBlocks for n windows: choose, then launch.
+static int run_block(ss_ctx* c, Workspace& ws, hipStream_t stream, int bi, int n, bool with_spec) {
+    const Block& k = kBlocks[bi];
+    const BlockPlan& p = c->convs[bi];
+    BlockRun r;
+    if (!choose_block(c, ws, bi, n, with_spec, r))
+        return fail(c, SS_ERR_STATE, "f16x2: no kernel form for " + (k.first_in_loader || r.A.form != kNoForm ? p.B.name : p.A.name));
+    // the tensors the block writes (ss_debug_activation refuses the others)
+    const bool hasA = r.A.form != kNoForm, store_y = r.B.a.store_out != 0;
+    for (Act t : {hasA ? k.h : kNoAct, hasA && !r.proj ? k.r : kNoAct, store_y ? k.y : kNoAct, k.pool})
+        if (t != kNoAct) c->dbg_written |= (uint64_t)1 << t;
     const double es = c->prec == kBf16 ? 2 : 4;
-    ConvArgs a{}, b{};
-    a.lo_delta = b.lo_delta = ws.lo_delta; a.range_flag = b.range_flag = c->d_range_flag;
-    a.src0 = x0; a.src1 = x1; a.wpk = pa.d_w3; a.bias = pa.d_bias2; a.out = h; a.plain = 1;
-    a.N = n; a.H = pa.H; a.W = pa.W; a.Cout = pa.Cout; a.C0 = pa.C0; a.C1 = pa.C1; a.relu = 1;
-    b.src0 = h; b.wpk = pb.d_w2; b.bias = pb.d_bias3; b.out = out; b.pool_out = pool;
-    b.N = n; b.H = pb.H; b.W = pb.W; b.Cout = pb.Cout; b.C0 = pb.Cout; b.C1 = 0; b.relu = 1;
-    b.proj_w = pb.d_proj; b.xp0 = x0; b.xp1 = x1; b.C0x = pa.C0; b.C1x = pa.C1;
-    b.flat_w4 = ex.flat_w4; b.flat_part = ex.flat_part; b.store_out = ex.store_out;
-    a.dbg = b.dbg = base_dbg();
-    if (!(stride_of(ws, x0, a.s_src0) && stride_of(ws, x1, a.s_src1) && stride_of(ws, h, a.s_out) && stride_of(ws, h, b.s_src0) &&
-          stride_of(ws, out, b.s_out) && stride_of(ws, pool, b.s_pool)))
-        return fail(c, SS_ERR_STATE, "no byte order for a tensor of " + pa.name);
-    b.s_xp0 = a.s_src0; b.s_xp1 = a.s_src1;
-    // f16x2: the A launch with the upsampled input half at low resolution (conv4_ups.hip: four pre-summed taps per output parity class
-    // instead of nine on those channels) where that form exists -- conv9_1.A
-    ConvArgs au = a;
-    au.wpk = pa.d_w_ups;
-    const bool ups = c->prec == kF16x2 && pa.d_w_ups && x1 && conv_ups_supports(au, cus);
-    if ((!ups && !conv_v4_supports(a, pa.NT, cus, prec4)) || !conv_v4_supports(b, pb.NT, cus, prec4)) return 1;
-    mark_written(c, ws, h); mark_written(c, ws, pool);
-    if (ex.store_out) mark_written(c, ws, out);
-    const double px = (double)n * pa.H * pa.W, cin = pa.C0 + pa.C1, cinb = pa.C0 + pa.C1 / 4.0;
-    const double flops_a = 2.0 * px * pa.Cout * 9.0 * cin, bytes_a = px * es * (cinb + pa.Cout);
-    auto v4 = [&](const ConvPlan& p, ConvArgs& x, double flops, double bytes) {
-        return conv_launch(c, stream, conv_v4_variant(x, p.NT, cus, prec4), p.name, x, flops, bytes, -1.0,
-                           [&](ConvArgs& y) { return launch_conv3x3_v4(y, p.NT, cus, prec4, stream); });
-    };
-    int rc;
-    // conv9_1.A: the row-streaming form (conv9a.hip) -- the same pre-summed taps on stream16.h's core, no patch images, no barriers.
-    // (Development build, SOFTSPOKEN_C9A=0: conv4_ups.hip's form, below; SOFTSPOKEN_UPS=0 switches both off.)
-    ConvArgs as = a;
-    as.wpk = pa.d_w_a16; as.wpk_b = pa.d_w_ups16;
-    const int rows_a = dev_env("SOFTSPOKEN_C9A_ROWS", 32);
-    if (ups && pa.d_w_a16 && pa.d_w_ups16 && dev_env("SOFTSPOKEN_C9A", 1) && conv9a_stream_supports(as) && conv9a_stream_rows_ok(rows_a)) {
-        const int grid = dev_env("SOFTSPOKEN_C9A_GRID", 0);
-        // (FLOPs booked: the layer's algorithmic ones; issued: 108 + 48 products per strip row, the tile form's count)
-        if ((rc = conv_launch(c, stream, conv9a_stream_variant(), pa.name, as, flops_a, bytes_a, conv9a_stream_issued_macs(n),
-                              [&](ConvArgs& y) { return launch_conv9a_stream(y, rows_a, grid, cus, stream); })))
+    for (Launch* l : {&r.A, &r.B, &r.B2}) {
+        if (l->form == kNoForm) continue;
+        const bool isA = l == &r.A;
+        if (int rc = launch_form(c, stream, isA ? p.A : p.B, *l, 2.0 * launch_macs(k, isA, r.proj, n), launch_bytes(k, isA, r.proj, n, es, store_y),
+                                 launch_issued(k, l->form, n)))
             return rc;
-    } else if (ups) {
-        // FLOPs booked are the layer's algorithmic ones (2 x multiply-adds of the 3x3 as the reference computes it); this
-        // form issues 9 C0 + 4 C1 multiply-adds per output value instead of 9 (C0 + C1).  (It takes no stage stamps.)
-        ScopedLaunch sl(c, stream, std::string(conv_ups_variant()) + "/" + pa.name, flops_a, bytes_a, px * pa.Cout * (9.0 * pa.C0 + 4.0 * pa.C1));
-        HIPCHK(c, launch_conv3x3_ups(au, cus, stream));
-    } else if ((rc = v4(pa, a, flops_a, bytes_a))) return rc;
-    const double flops_b = 2.0 * px * pb.Cout * (9.0 * pb.Cout + cin) + (ex.flat_part ? 2.0 * px * 32 * 4 : 0.0);
-    const double bytes_b = px * es * (pb.Cout + cinb + (ex.flat_part && !ex.store_out ? 0 : pb.Cout) + (pool ? pb.Cout / 4.0 : 0));
-    if (c->prec == kF16x2 && ex.flat_part && ex.flat_rows && pb.d_w_s16 && pb.d_proj_s16 && dev_env("SOFTSPOKEN_C9S", 1)) {
-        // conv9_1.B: the row-streaming form (conv9s.hip), in the mask-only pass and in the spec pass alike (store_out): the two passes'
-        // flatten sums are the same bits.  (Development build, SOFTSPOKEN_C9S=0: conv4.hip's form, below.)
-        ConvArgs bs = b;
-        bs.wpk = pb.d_w_s16; bs.proj_w = pb.d_proj_s16; bs.flat_w4 = ex.flat_rows;
-        const int rows = dev_env("SOFTSPOKEN_C9S_ROWS", 32);
-        if (conv9_stream_supports(bs) && conv9_stream_rows_ok(rows)) {
-            const int grid = dev_env("SOFTSPOKEN_C9S_GRID", 0);
-            // (FLOPs booked: the layer's algorithmic ones; issued: what the strips really multiply, the flatten's products included)
-            if ((rc = conv_launch(c, stream, conv9_stream_variant(), pb.name, bs, flops_b, bytes_b, conv9_stream_issued_macs(n),
-                                  [&](ConvArgs& y) { return launch_conv9_stream(y, rows, grid, cus, stream); })))
-                return rc;
-            ws.flat_groups = conv9_stream_flat_groups(rows);
-            return SS_OK;
-        }
     }
-    if ((rc = v4(pb, b, flops_b, bytes_b))) return rc;
-    if (ex.flat_part) ws.flat_groups = conv_v4_flat_groups();
+    if (k.flat_in_b) ws.flat_groups = flat_groups_of(c, r.B.form);
     return SS_OK;
-}
-
-static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec);
-
-// SpecUNet_2D.forward (pytorch_neural_nets.py:142-197) for n <= ws.chunk windows that start at signal + d_winoff[0..n)
-int forward_chunk(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec) {
-#ifdef SS_DEVBUILD
-    // the pass's record for ss_debug_activation
-    c->dbg_written.clear(); c->dbg_n = n; c->dbg_ws = (int)(&ws - c->ws);
-    c->dbg_written.insert("feat");
-    if (d_logits) c->dbg_written.insert("flat_part");
-    const int rc = forward_chunk_(c, ws, stream, signal, d_winoff, n, d_logits, d_spec);
-    if (rc) { c->dbg_written.clear(); c->dbg_n = 0; }
-    return rc;
-#else
-    return forward_chunk_(c, ws, stream, signal, d_winoff, n, d_logits, d_spec);
-#endif
 }
 
 static int forward_chunk_(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec) {
     FrontendTables tb{c->d_pretw, c->d_w2048, c->d_mel_start, c->d_mel_count, c->d_mel_off, c->d_mel_w, c->mel_nw, c->d_mel_wp, dev_env("SOFTSPOKEN_FEDBG", 0),
                       c->d_win2, c->d_twt, c->d_wkt, c->d_mel_wq, c->d_mel_p0};
-    float* const feat = ws.feat;
     {
         ScopedLaunch sl(c, stream, "frontend", 0.0, (double)n * (66150.0 * 4 + 128.0 * 256 * 4));
-        HIPCHK(c, launch_frontend(signal, d_winoff, n, tb, feat, c->num_cus, stream));
+        HIPCHK(c, launch_frontend(signal, d_winoff, n, tb, ws.feat, c->num_cus, stream));
     }
     if (!d_logits) return SS_OK;
-    auto A = [&](const char* k) -> void* {
-        auto it = ws.act.find(k);
-        return it == ws.act.end() ? nullptr : it->second;      // (never null after ensure_workspace; a null would be refused by the launch checks)
-    };
-    const double es = c->prec == kBf16 ? 2 : 4;
-    const std::vector<ConvPlan>& cv = c->convs;
-    int rc, i = 0;
-#define RC2(x) if ((rc = (x))) return rc
-    {   // conv1_1: first conv produced in the loader (bf16: MFMA on bf16 features; f16x2: three MFMAs on f16 halves), 1 -> 32 residual
-        // from the features (bf16: one more MFMA on hi/lo halves; f16x2: a rank-1 fp32 term in the epilogue; fp32: conv2.hip's own form)
-        ConvExtra ex; ex.first_w = c->d_first_w; ex.first_b = c->d_first_b;
-        RC2(run_conv2(c, ws, stream, cv[i++], n, nullptr, nullptr, A("c1"), A("p1"), nullptr, nullptr, feat, ex));
-    }
-    struct Blk { const char *x0, *x1, *h, *r, *y, *pool; };
-    const Blk blks[] = {{"p1", nullptr, "h2", "r2", "c2", "p2"},   {"p2", nullptr, "h3", "r3", "c3", "p3"},
-                        {"p3", nullptr, "h4", "r4", "c4", "p4"},   {"p4", nullptr, "hb", "rb", "bott", nullptr},
-                        {"bott", nullptr, "he", "re", "enc", nullptr}, {"c4", "enc", "h6", "r6", "c6", nullptr},
-                        {"c3", "c6", "h7", "r7", "c7", nullptr},   {"c2", "c7", "h8", "r8", "c8", nullptr}};
-    const bool proj = c->prec != kFp32 && dev_env("SOFTSPOKEN_CONV4", 1) && dev_env("SOFTSPOKEN_RPROJ", 1);
-    for (const Blk& b : blks) {
-        // (running A and B over Infinity-Cache-sized sub-chunks of windows was measured twice: no gain)
-        // Blocks whose input is narrower than their output (encoder) move fewer bytes when B recomputes the 1x1 projection from
-        // the block input than when A writes r and B reads it back; conv4.hip has that form for the blocks where it pays.
-        if (proj) {
-            rc = run_block_proj(c, ws, stream, cv[i], cv[i + 1], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), A(b.y), b.pool ? A(b.pool) : nullptr);
-            if (rc == SS_OK) { i += 2; continue; }
-            if (rc != 1) return rc;
-        }
-        RC2(run_conv2(c, ws, stream, cv[i], n, A(b.x0), b.x1 ? A(b.x1) : nullptr, A(b.h), nullptr, A(b.r), nullptr, nullptr));
-        RC2(run_conv2(c, ws, stream, cv[i + 1], n, A(b.h), nullptr, A(b.y), b.pool ? A(b.pool) : nullptr, nullptr, A(b.r), nullptr));
-        i += 2;
-    }
-    {   // conv9_1 on cat[conv1, up(conv8)]; conv_flatten rides in B's epilogue (c9 itself only when the spec head runs)
-        ConvExtra ex; ex.flat_w = c->d_flat_frag; ex.flat_w4 = c->d_flat_frag4; ex.flat_part = ws.flat; ex.store_out = d_spec ? 1 : 0;
-        ex.flat_rows = c->d_flat_rows;
-        rc = 1;
-        if (proj && (rc = run_block_proj(c, ws, stream, cv[i], cv[i + 1], n, A("c1"), A("c8"), A("h9"), A("c9"), nullptr, ex)) != 1) {
-            if (rc) return rc;
-        } else {
-            RC2(run_conv2(c, ws, stream, cv[i], n, A("c1"), A("c8"), A("h9"), nullptr, A("r9"), nullptr, nullptr));
-            RC2(run_conv2(c, ws, stream, cv[i + 1], n, A("h9"), nullptr, A("c9"), nullptr, nullptr, A("r9"), nullptr, ex));
-        }
-        i += 2;
-    }
-    if (d_spec) {   // dead head of the reference (worker.py:78-79 drops it), on request
-        RC2(run_conv2(c, ws, stream, cv[i], n, A("c9"), nullptr, A("hs"), nullptr, A("rs"), nullptr, nullptr));
-        RC2(run_conv2(c, ws, stream, cv[i + 1], n, A("hs"), nullptr, A("s9"), nullptr, nullptr, A("rs"), nullptr));
+    for (int bi = 0; bi < kBlockCount && !(kBlocks[bi].spec_only && !d_spec); ++bi)
+        if (int rc = run_block(c, ws, stream, bi, n, d_spec != nullptr)) return rc;
+    if (d_spec) {   // the spec head's 1x1 (its ResBlock ran above)
+        const double es = c->prec == kBf16 ? 2 : 4;
         ScopedLaunch sl(c, stream, "spec_tail", 2.0 * n * 32768 * 64, (double)n * 32768 * (32 * es + 8));
-        HIPCHK(c, launch_spec_tail(A("s9"), ws.lo_delta, c->d_spec_w, c->d_spec_b, d_spec, n, (int)c->prec, stream));
+        HIPCHK(c, launch_spec_tail(ws.t[kS9].p, ws.lo_delta, c->d_spec_w, c->d_spec_b, d_spec, n, (int)c->prec, stream));
     }
-#undef RC2
     const int groups = ws.flat_groups;
     ScopedLaunch sl(c, stream, "mask_head_parts", 0.0, (double)n * (groups * 4 * 256 * 4 + 1024));
     HIPCHK(c, launch_mask_head_parts(ws.flat, groups, c->d_flat_b, c->head, d_logits, n, stream));
     return SS_OK;
+}
+
+// SpecUNet_2D.forward (pytorch_neural_nets.py:142-197) for n <= ws.chunk windows that start at signal + d_winoff[0..n)
+int forward_chunk(ss_ctx* c, Workspace& ws, hipStream_t stream, const float* signal, const int64_t* d_winoff, int n, float* d_logits, float* d_spec) {
+    // the pass's record for the dev build's ss_debug_activation
+    c->dbg_n = n; c->dbg_ws = (int)(&ws - c->ws);
+    c->dbg_written = (uint64_t)1 << kDbgFeat | (uint64_t)(d_logits ? 1 : 0) << kDbgFlatPart;
+    const int rc = forward_chunk_(c, ws, stream, signal, d_winoff, n, d_logits, d_spec);
+    if (rc) { c->dbg_written = 0; c->dbg_n = 0; }
+    return rc;
 }
 
 #ifdef SS_DEVBUILD
@@ -480,32 +466,27 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
     if (!c || !name) return fail(c, SS_ERR_ARG, "ss_debug_activation: null argument");
     const std::string k = name;
     const Workspace& w = c->ws[0];
-    int H = 128, W = 256, C = 1, es = 4;
-    const void* base = nullptr;
-    if (k == "feat") {
-        base = w.feat;
-    } else if (k == "flat_part") {                        // conv_flatten's row-group partial sums [n][groups][4][256] (heads.hip)
-        base = w.flat; H = std::max(w.flat_groups, 1); W = 4; C = 256;
-    } else {
-        const WsTensor* t = nullptr;
-        for (const WsTensor& e : kWsTensors) if (k == e.n) t = &e;
-        if (!t) return fail(c, SS_ERR_ARG, "ss_debug_activation: no tensor named '" + k + "'");
-        H = t->H; W = t->W; C = t->C; es = c->prec == kFp32 ? 4 : 2;
-    }
+    int id = k == "feat" ? kDbgFeat : k == "flat_part" ? kDbgFlatPart : -1;
+    for (int i = 0; i < kActCount && id < 0; ++i) if (k == kActs[i].name) id = i;
+    if (id < 0) return fail(c, SS_ERR_ARG, "ss_debug_activation: no tensor named '" + k + "'");
+    const bool act = id < kActCount;                      // a workspace tensor
+    int H = 128, W = 256, C = 1, es = 4;                  // (the features)
+    if (id == kDbgFlatPart) { H = std::max(w.flat_groups, 1); W = 4; C = 256; }      // conv_flatten's row-group partial sums [n][groups][4][256] (heads.hip)
+    if (act) { H = kActs[id].H; W = kActs[id].W; C = kActs[id].C; es = c->prec == kFp32 ? 4 : 2; }
     if (shape) { shape[0] = H; shape[1] = W; shape[2] = C; shape[3] = es; }
     if (exponents) {
-        const auto it = c->act_exp.find(k);
-        for (int i = 0; i < C; ++i) exponents[i] = it != c->act_exp.end() && i < (int)it->second.size() ? it->second[i] : 0;
+        const std::vector<int>& e = c->act_exp[id];
+        for (int i = 0; i < C; ++i) exponents[i] = i < (int)e.size() ? e[i] : 0;
     }
     if (!out) return SS_OK;                               // (shape and exponents are the model's: no pass needed)
     if (c->run_pending) return fail(c, SS_ERR_STATE, "ss_debug_activation: a run is in flight");
-    if (!w.chunk || w.act.empty()) return fail(c, SS_ERR_STATE, "ss_debug_activation: the context has no workspace");
+    if (!w.chunk || !w.arena) return fail(c, SS_ERR_STATE, "ss_debug_activation: the context has no workspace");
     if (c->dbg_ws != 0) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass ran on the second lane's workspace");
-    if (!c->dbg_written.count(k)) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass did not write " + k);
+    if (!(c->dbg_written >> id & 1)) return fail(c, SS_ERR_STATE, "ss_debug_activation: the last pass did not write " + k);
     // (after the staleness test: SS_ERR_ARG for an r tensor tells the caller that the pass ran the block as A + r / B)
-    if (k[0] == 'r') return fail(c, SS_ERR_ARG, "ss_debug_activation: " + k + " is stored in MFMA fragment order; check it through its B launch");
-    if (k != "feat" && k != "flat_part") base = w.act.at(k);
-    const bool two = k != "feat" && k != "flat_part" && c->prec == kF16x2;
+    if (act && kActs[id].frag_order) return fail(c, SS_ERR_ARG, "ss_debug_activation: " + k + " is stored in MFMA fragment order; check it through its B launch");
+    const void* base = act ? w.t[id].p : id == kDbgFeat ? (const void*)w.feat : w.flat;
+    const bool two = act && c->prec == kF16x2;
     if (plane < 0 || plane > (two ? 1 : 0)) return fail(c, SS_ERR_ARG, "ss_debug_activation: no plane " + std::to_string(plane) + " in " + k);
     if (first < 0 || n < 0 || first + n > c->dbg_n)
         return fail(c, SS_ERR_ARG, "ss_debug_activation: windows [" + std::to_string(first) + ", " + std::to_string(first + n) + ") are outside the last pass (" +
@@ -516,13 +497,12 @@ int debug_activation(ss_ctx* c, const char* name, int plane, int64_t first, int6
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const char* src = (const char*)base + (plane ? w.lo_delta : 0) + first * per;
-        const auto st = w.stride.find(base);
-        if (st == w.stride.end() || st->second.pix == (uint32_t)(C * es)) {
+        const ActStride s = act ? w.t[id].s : ActStride{0u, 0u};
+        if (s.pix == 0 || s.pix == (uint32_t)(C * es)) {     // (no byte order: fp32, the features, the partial sums)
             HIPCHK(c, hipMemcpy(out, src, (size_t)need, hipMemcpyDeviceToHost));
         } else {                                          // stored [n][C / 32][H][W][32]: 64-byte pieces to their pixels
             std::vector<char> tmp((size_t)need);
             HIPCHK(c, hipMemcpy(tmp.data(), src, (size_t)need, hipMemcpyDeviceToHost));
-            const ActStride s = st->second;
             for (int64_t i = 0; i < n; ++i)
                 for (int k = 0; k < C / 32; ++k)
                     for (int64_t px = 0; px < (int64_t)H * W; ++px)

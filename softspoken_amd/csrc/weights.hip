@@ -588,9 +588,9 @@ static int pick_nt(int cout, int H) { return H <= 8 ? 1 : (cout == 96 ? 3 : (cou
 
 // One ResBlock (pytorch_neural_nets.py:7-41) -> launch A (conv1+BN+ReLU) and launch B (conv2+BN + residual+BN, add, ReLU).
 // s_in: exponents of the block input's channels (cat[x0, x1]); s_out receives the block output's (all zero unless f16x2)
-// s_hid receives the exponents of the block's hidden tensor h (the A launch's output)
+// s_hid receives the exponents of the block's hidden tensor h (the A launch's output); out the block's two launches
 static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, int cin0, int cin1, int cout, int H, int W,
-                          const std::vector<int>& s_in, std::vector<int>& s_out, std::vector<int>& s_hid) {
+                          const std::vector<int>& s_in, std::vector<int>& s_out, std::vector<int>& s_hid, BlockPlan& out) {
     std::string err;
     const int cin = cin0 + cin1;
     Folded f1, f2, fr;
@@ -653,7 +653,7 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
             }
             B.s1_range_proven = std::isfinite(worst) && worst < 60000.0;
         }
-        c->convs.push_back(B);
+        out.B = B;
         return SS_OK;
     }
     // f16x2, A launch of the 96-channel blocks: three 32-channel groups through the shared two-slot bank ring (conv4.hip RING)
@@ -678,21 +678,17 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
         if (pk.size() != conv_ups32_weight_bytes(cin0, cin1, cout)) return fail(c, SS_ERR_STATE, "pack_conv_v2_ups: size");
         if ((rc = dev_upload(c, (char**)&A.d_w_ups32, pk.data(), pk.size()))) return rc;
     }
-    c->convs.push_back(A);
     if (c->bf16) {
         pack_conv_v2(f1, nullptr, true, NT, pk);
         if ((rc = dev_upload(c, (char**)&A.d_w3, pk.data(), pk.size()))) return rc;
-        c->convs.back().d_w3 = A.d_w3;
     }
     if (c->prec == kF16x2) {                              // "projection in B" form: the 3x3 banks alone (no 1x1 tap)
         pack_conv_split(f1, nullptr, NTA, pk, c->split_range_ok);
         if ((rc = dev_upload(c, (char**)&A.d_w3, pk.data(), pk.size()))) return rc;
-        c->convs.back().d_w3 = A.d_w3;
         if (cin1 >= 32 && cin0 >= 32 && cout == 32) {     // ... and the same with the upsampled half at low resolution (conv4_ups.hip)
             pack_conv_split_ups(f1, cin0, cin1, pk, c->split_range_ok);
             if (pk.size() != conv_ups_weight_bytes(cin0, cin1)) return fail(c, SS_ERR_STATE, "pack_conv_split_ups: size");
             if ((rc = dev_upload(c, (char**)&A.d_w_ups, pk.data(), pk.size()))) return rc;
-            c->convs.back().d_w_ups = A.d_w_ups;
             if (cin0 == 32 && cin1 == 32 && H == 128 && W == 256) {      // conv9_1.A: the row-streaming form (conv9a.hip)
                 pack_conv_stream16(f1, pk, c->split_range_ok);           // (its input channels 0 .. 31: c1)
                 if (pk.size() != conv1_stream_weight_bytes()) return fail(c, SS_ERR_STATE, "pack_conv_stream16: size");
@@ -700,7 +696,6 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
                 pack_ups_stream16(f1, cin0, pk, c->split_range_ok);
                 if (pk.size() != conv9a_stream_ups_bytes()) return fail(c, SS_ERR_STATE, "pack_ups_stream16: size");
                 if ((rc = dev_upload(c, (char**)&A.d_w_ups16, pk.data(), pk.size()))) return rc;
-                c->convs.back().d_w_a16 = A.d_w_a16; c->convs.back().d_w_ups16 = A.d_w_ups16;
             }
         }
     }
@@ -743,42 +738,26 @@ static int build_resblock(ss_ctx* c, const Blob& bl, const std::string& name, in
     if (c->prec == kF16x2) pack_conv_split(f2, nullptr, NTB, pk, c->split_range_ok); else pack_conv_v2(f2, nullptr, c->bf16, NT, pk);
     if ((rc = dev_upload(c, (char**)&B.d_w2, pk.data(), pk.size()))) return rc;
     if ((rc = dev_upload(c, &B.d_bias2, f2.b.data(), cout * 4))) return rc;
-    c->convs.push_back(B);
+    out.A = A; out.B = B;
     return SS_OK;
 }
 
 int build_model(ss_ctx* c, const Blob& bl) {
     int rc;
     c->split_range_ok = true;
-    // launch order == pytorch_neural_nets.py:156-181
-    // x0 / x1: the blocks whose outputs are concatenated into this block's input (pytorch_neural_nets.py:171-180: [skip, upsampled]);
-    // their channel exponents (f16x2 normalisation) travel with them
-    // (h, y, pool: the block's tensors in the activation workspace, engine.hip alloc_ws)
-    struct RB { const char* n; int c0, c1, co, H, W; const char *x0, *x1, *h, *y, *pool; };
-    const RB rbs[] = {{"conv1_1", 1, 0, 32, 128, 256, nullptr, nullptr, "h1", "c1", "p1"},
-                      {"conv2_1", 32, 0, 64, 64, 128, "conv1_1", nullptr, "h2", "c2", "p2"},
-                      {"conv3_1", 64, 0, 96, 32, 64, "conv2_1", nullptr, "h3", "c3", "p3"},
-                      {"conv4_1", 96, 0, 128, 16, 32, "conv3_1", nullptr, "h4", "c4", "p4"},
-                      {"conv_bottleneck", 128, 0, 128, 8, 16, "conv4_1", nullptr, "hb", "bott", nullptr},
-                      {"encoder_out", 128, 0, 128, 8, 16, "conv_bottleneck", nullptr, "he", "enc", nullptr},
-                      {"conv6", 128, 128, 96, 16, 32, "conv4_1", "encoder_out", "h6", "c6", nullptr},
-                      {"conv7", 96, 96, 64, 32, 64, "conv3_1", "conv6", "h7", "c7", nullptr},
-                      {"conv8", 64, 64, 32, 64, 128, "conv2_1", "conv7", "h8", "c8", nullptr},
-                      {"conv9_1", 32, 32, 32, 128, 256, "conv1_1", "conv8", "h9", "c9", nullptr},
-                      {"spec_output_conv.0", 32, 0, 32, 128, 256, "conv9_1", nullptr, "hs", "s9", nullptr}};
-    std::map<std::string, std::vector<int>> sc;           // block name -> exponents of its output channels
-    c->act_exp.clear();
-    for (const RB& r : rbs) {
-        std::vector<int> s_in, s_hid;
-        if (r.x0) s_in = sc[r.x0]; else s_in.assign(r.c0, 0);          // (conv1_1: the features, as they are)
-        if (r.x1) s_in.insert(s_in.end(), sc[r.x1].begin(), sc[r.x1].end());
-        if ((int)s_in.size() != r.c0 + r.c1) return fail(c, SS_ERR_STATE, "build_model: channel bookkeeping");
-        if ((rc = build_resblock(c, bl, r.n, r.c0, r.c1, r.co, r.H, r.W, s_in, sc[r.n], s_hid))) return rc;
-        c->act_exp[r.h] = s_hid;
-        c->act_exp[r.y] = sc[r.n];
-        if (r.pool) c->act_exp[r.pool] = sc[r.n];
+    // the blocks of net.h in launch order (== pytorch_neural_nets.py:156-181).  A block's input is cat[x0, up2(x1)] (:171-180: [skip,
+    // upsampled]); the tensors' channel exponents (f16x2 normalisation) travel with them
+    for (std::vector<int>& e : c->act_exp) e.clear();
+    c->act_exp[kDbgFeat].assign(1, 0);                    // (conv1_1 reads the features, as they are)
+    for (int i = 0; i < kBlockCount; ++i) {
+        const Block& k = kBlocks[i];
+        std::vector<int> s_in = c->act_exp[k.x0 == kNoAct ? kDbgFeat : k.x0];
+        if (k.x1 != kNoAct) s_in.insert(s_in.end(), c->act_exp[k.x1].begin(), c->act_exp[k.x1].end());
+        if ((int)s_in.size() != k.c0 + k.c1) return fail(c, SS_ERR_STATE, "build_model: channel bookkeeping");
+        c->convs[i] = BlockPlan();
+        if ((rc = build_resblock(c, bl, k.name, k.c0, k.c1, k.cout, k.H, k.W, s_in, c->act_exp[k.y], c->act_exp[k.h], c->convs[i]))) return rc;
+        if (k.pool != kNoAct) c->act_exp[k.pool] = c->act_exp[k.y];
     }
-    c->act_exp["feat"] = std::vector<int>(1, 0);
     std::string err;
     // conv_flatten (pytorch_neural_nets.py:133): weight (4, 32, 128, 1) -> [h][ci][c]
     const float* wf0 = bl.f32("conv_flatten.weight", 4 * 32 * 128, err);
@@ -794,7 +773,7 @@ int build_model(ss_ctx* c, const Blob& bl) {
     // scores 2.3e-5 from the float64 oracle where the same function otherwise gives 6e-6; a median of -10 would have left the bar.
     // With this rule spread6's exponent is -1 and its scores lie 4.8e-6 from the oracle (tests/test_gpu_checkpoints.py).
     std::vector<float> wfs(wf0, wf0 + 4 * 32 * 128);
-    std::vector<int> s9 = sc["conv9_1"];
+    const std::vector<int>& s9 = c->act_exp[kC9];
     int s_common = 0;
     if (c->prec == kF16x2 && dev_env("SOFTSPOKEN_NORM", 1)) {
         double q = 0;
@@ -808,7 +787,7 @@ int build_model(ss_ctx* c, const Blob& bl) {
     for (int co = 0; co < 4; ++co) for (int ci = 0; ci < 32; ++ci) for (int h = 0; h < 128; ++h)
         wfs[((size_t)co * 32 + ci) * 128 + h] = std::ldexp(wfs[((size_t)co * 32 + ci) * 128 + h], s_common - s9[ci]);
     c->head.fscale = std::ldexp(1.0f, -s_common);
-    c->act_exp["flat_part"] = std::vector<int>(256, s_common);          // (the partial sums carry 2^s_common)
+    c->act_exp[kDbgFlatPart].assign(256, s_common);          // (the partial sums carry 2^s_common)
     const float* wf = wfs.data();
     {   // fused flatten (conv2.hip FLAT): per mel row PAIR a 32 -> 8 (padded to 32) 1x1 "conv" in MFMA fragment order -- columns 0..3 are
         // the four flatten channels with the weights of row 2 p, columns 4..7 the same with those of row 2 p + 1: one product per pair of
@@ -859,7 +838,7 @@ int build_model(ss_ctx* c, const Blob& bl) {
     const float* bs = bl.f32("spec_output_conv.1.bias", 2, err);
     if (!ws || !bs) return fail(c, SS_ERR_FORMAT, err);
     float wss[64];
-    for (int co = 0; co < 2; ++co) for (int ci = 0; ci < 32; ++ci) wss[co * 32 + ci] = std::ldexp(ws[co * 32 + ci], -sc["spec_output_conv.0"][ci]);
+    for (int co = 0; co < 2; ++co) for (int ci = 0; ci < 32; ++ci) wss[co * 32 + ci] = std::ldexp(ws[co * 32 + ci], -c->act_exp[kS9][ci]);
     if ((rc = dev_upload(c, &c->d_spec_w, wss, 256))) return rc;
     if ((rc = dev_upload(c, &c->d_spec_b, bs, 8))) return rc;
     // mask_output_conv (pytorch_neural_nets.py:137-140): ResBlock1D(4,4) + Conv1d(4,1,1)

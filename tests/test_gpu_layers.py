@@ -8,7 +8,16 @@ A child prints one line per launch,
 and one COVER line for every plan name of kernel_stats() that has no check; the parent asserts on them.  An f16x2 child also prints
     EXPONENTS <config> <channels whose exponent is not the host emulation's> <channels excused as rounding ties> <the first few>
 for the exponents ss_debug_activation reports for h1 ... hs, c1 ... s9 and the flatten's partial sums (tests/checkpoint_zoo.py
-exponent_chain)."""
+exponent_chain).  Every child also prints, per pass,
+    PLAN <config> <pass> <JSON: [name, launches, flops, bytes, issued] of every kernel_stats() entry, in order>
+and the parent holds these to tests/golden/launch_plan.json: which kernel form served which launch, how often, and what the engine
+booked for it (names and counts equal, the three doubles to 1e-9 relative: reassociated double arithmetic moves them by about 1e-15,
+a dropped term by far more).
+
+The golden was recorded on an MI355X from the commit BEFORE the engine's block table and runner (0df854f), with only this file's PLAN
+print applied there, not from the code under test: it pins the launch order, the form chosen for every launch under every switch set
+below and the roofline bookkeeping across that rewrite."""
+import json
 import os
 import subprocess
 import sys
@@ -22,8 +31,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL_SPEC = 1e-4          # the fp32 parity bar (BASELINE.json north_star), on every value of the spec head
 TOL_SPEC_BF16 = 0.15     # bf16: the throughput mode's stated score tolerance (test_bf16_mode)
 
+# the ResBlocks behind conv1_1 in launch order: block, x0, x1, h, r, y, pool (tests/test_net_table.py holds them to csrc/net.h)
+BLOCKS = [("conv2_1", "p1", None, "h2", "r2", "c2", "p2"), ("conv3_1", "p2", None, "h3", "r3", "c3", "p3"),
+          ("conv4_1", "p3", None, "h4", "r4", "c4", "p4"), ("conv_bottleneck", "p4", None, "hb", "rb", "bott", None),
+          ("encoder_out", "bott", None, "he", "re", "enc", None), ("conv6", "c4", "enc", "h6", "r6", "c6", None),
+          ("conv7", "c3", "c6", "h7", "r7", "c7", None), ("conv8", "c2", "c7", "h8", "r8", "c8", None),
+          ("conv9_1", "c1", "c8", "h9", "r9", "c9", None), ("spec_output_conv.0", "c9", None, "hs", "rs", "s9", None)]
+
 _CHILD = r"""
-import sys, numpy as np, torch
+import json, sys, numpy as np, torch
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 torch.set_grad_enabled(False)
 from softspoken_amd import synth, native, checkpoint
@@ -39,11 +55,7 @@ ctx = native.Context(checkpoint.pack_state_dict(sd), 0, precision=mode, chunk=5)
 fid = ctx.add_f32_22k(sig)
 sel = {sel!r}[:n_sel] if n_sel == 5 else [{sel!r}[0], {sel!r}[3]]
 S = starts[sel]
-BLOCKS = [("conv2_1", "p1", None, "h2", "r2", "c2", "p2"), ("conv3_1", "p2", None, "h3", "r3", "c3", "p3"),
-          ("conv4_1", "p3", None, "h4", "r4", "c4", "p4"), ("conv_bottleneck", "p4", None, "hb", "rb", "bott", None),
-          ("encoder_out", "bott", None, "he", "re", "enc", None), ("conv6", "c4", "enc", "h6", "r6", "c6", None),
-          ("conv7", "c3", "c6", "h7", "r7", "c7", None), ("conv8", "c2", "c7", "h8", "r8", "c8", None),
-          ("conv9_1", "c1", "c8", "h9", "r9", "c9", None), ("spec_output_conv.0", "c9", None, "hs", "rs", "s9", None)]
+BLOCKS = {blocks!r}
 W = {{b[0]: R.block_weights(sd, b[0]) for b in BLOCKS}}
 W["conv1_1"] = R.block_weights(sd, "conv1_1")
 L = native.lib()
@@ -141,6 +153,7 @@ def run(pname, with_spec, chunk):
     for s in ctx.kernel_stats():
         if s["name"].split("/")[-1] not in checked:
             print("COVER", tag, pname, s["name"], flush=True)
+    print("PLAN", tag, pname, json.dumps([[s["name"], s["launches"], s["flops"], s["bytes"], s["issued_flops"]] for s in ctx.kernel_stats()]), flush=True)
     checked.clear()
     return mask
 
@@ -190,17 +203,34 @@ def layer_signal(tmp_path_factory):
     return dict(dir=str(d), sig=str(d / "sig.npy"), sel=sel, starts=starts)
 
 
-def _child(tag, mode, env, layer_signal, n_sel=5, hostile=False, ckpt=None):
-    """ckpt: a checkpoint of tests/checkpoint_zoo.py by name; without one, `hostile` picks between the two the suite had before it."""
+PLAN_GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_plan.json")
+PLAN_RTOL = 1e-9
+
+
+def _check_plan(key, plans):
+    """plans: {pass: [[name, launches, flops, bytes, issued], ...]} of one child against the golden's entry `key`."""
+    with open(PLAN_GOLDEN) as f:
+        want = json.load(f)[key]
+    assert sorted(plans) == sorted(want), (key, sorted(plans), sorted(want))
+    for pname, got in plans.items():
+        w = want[pname]
+        assert [g[:2] for g in got] == [x[:2] for x in w], "%s %s: launches differ\n  got  %s\n  want %s" % (key, pname, [g[:2] for g in got], [x[:2] for x in w])
+        bad = [(g, x) for g, x in zip(got, w) if any(abs(a - b) > PLAN_RTOL * abs(b) for a, b in zip(g[2:], x[2:]))]
+        assert not bad, "%s %s: booked flops / bytes / issued differ, first: got %s want %s" % ((key, pname) + bad[0])
+
+
+def _child(tag, mode, env, layer_signal, n_sel=5, hostile=False, ckpt=None, plan_key=None):
+    """ckpt: a checkpoint of tests/checkpoint_zoo.py by name; without one, `hostile` picks between the two the suite had before it.
+    plan_key: the child's entry in tests/golden/launch_plan.json (default: tag)."""
     from softspoken_amd import build as hip_build
     ckpt = ckpt or ("hostile" if hostile else "seed0")
     out_npy = os.path.join(layer_signal["dir"], tag + ".npy")
     code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), tag=tag, mode=mode, ckpt=ckpt, n_sel=n_sel, out_npy=out_npy,
-                         sig_npy=layer_signal["sig"], sel=layer_signal["sel"])
+                         sig_npy=layer_signal["sig"], sel=layer_signal["sel"], blocks=BLOCKS)
     e = dict(os.environ); e.update(env); e["SOFTSPOKEN_LIB"] = hip_build.DEV_LIB
     r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=900)
     lines = r.stdout.splitlines()
-    print("\n".join(l for l in lines if l.startswith(("LAUNCH", "COVER", "EXPONENTS"))))
+    print("\n".join(l[:400] for l in lines if l.startswith(("LAUNCH", "COVER", "EXPONENTS", "PLAN"))))
     assert r.returncode == 0 and any(l.startswith("CHILD_OK") for l in lines), r.stdout[-3000:] + r.stderr[-3000:]
     launches = [l.split() for l in lines if l.startswith("LAUNCH")]
     uncovered = [l for l in lines if l.startswith("COVER")]
@@ -212,6 +242,9 @@ def _child(tag, mode, env, layer_signal, n_sel=5, hostile=False, ckpt=None):
     assert all(int(l[2]) == 0 for l in expo), "device exponents off the rule: " + " ".join(expo[0])
     # the checkpoints are fixed, and none has a channel on a rounding tie: the excuse must not be where a wrong rule hides
     assert all(int(l[3]) == 0 for l in expo), "channels excused as rounding ties: " + " ".join(expo[0])
+    plans = {l.split(" ", 3)[2]: json.loads(l.split(" ", 3)[3]) for l in lines if l.startswith("PLAN")}
+    assert sorted(plans) == sorted(["spec", "nospec"] + (["ragged"] if n_sel == 5 else [])), sorted(plans)
+    _check_plan(plan_key or tag, plans)
     return out_npy
 
 
@@ -283,11 +316,15 @@ ALTERNATE = [({"SOFTSPOKEN_CONV4": "0"}, "bf16"), ({"SOFTSPOKEN_CONV4": "0", "SO
              ({"SOFTSPOKEN_C1S_FORM": "32"}, "f16x2"), ({"SOFTSPOKEN_C1S_FORM": "32", "SOFTSPOKEN_C1S_ROWS": "16"}, "f16x2")]
 
 
-@pytest.mark.parametrize("env,mode", ALTERNATE, ids=["-".join(f"{k[11:]}={v}" for k, v in e.items()) + "-" + m for e, m in ALTERNATE])
+def _alt_id(env, mode):
+    return "-".join(f"{k[11:]}={v}" for k, v in env.items()) + "-" + mode
+
+
+@pytest.mark.parametrize("env,mode", ALTERNATE, ids=[_alt_id(e, m) for e, m in ALTERNATE])
 def test_every_launch_of_the_alternate_forms(env, mode, layer_signal, build_all):
     """The switch sets of test_gpu_parity's test_alternate_kernel_structures and test_conv1_streaming_kernel_variants_agree, whose
     forms are otherwise held only to the score bars: two windows (the pad and the noise)."""
-    _child("alt", mode, env, layer_signal, n_sel=2)
+    _child("alt", mode, env, layer_signal, n_sel=2, plan_key="alt-" + _alt_id(env, mode))
 
 
 ZOO = [(name, mode) for name in ("seed7", "spread3", "spread6", "signs", "dead", "tinyvar") for mode in ("f16x2", "fp32")] + \
@@ -299,7 +336,7 @@ def test_every_launch_on_the_checkpoint_zoo(name, mode, layer_signal, build_all)
     """The checkpoints of tests/checkpoint_zoo.py (another draw, per-channel gains of 10^+-3 and 10^+-6, negative gammas, dead channels,
     variances of zero), two windows (the pad and the noise): the same bounds, unchanged, and in f16x2 the device's exponents against
     the host emulation of the rule.  Dead channels are exact on both sides (0 / 0 counts as exact in ratio_report)."""
-    _child("zoo_" + name, mode, {}, layer_signal, n_sel=2, ckpt=name)
+    _child("zoo_" + name, mode, {}, layer_signal, n_sel=2, ckpt=name, plan_key=f"zoo_{name}-{mode}")
 
 
 @pytest.mark.parametrize("mode,hostile", [("fp32", False), ("f16x2", False), ("bf16", False), ("f16x2", True), ("fp32", True)])
