@@ -11,23 +11,25 @@
 //     32-channel x 32-column accumulator tile; ReLU'd, split into f16 halves and packed pairwise, registers 8 s .. 8 s + 7 ARE the
 //     B operand of the second conv's K step s (MI355X guide, "an accumulator tile as the next MFMA's operand") -- with the K order
 //     permuted, which the weight banks are packed for (weights.hip pack_conv_stream).  The wave keeps h1 of three rows (48 registers).
-//   * The 3 x 3 needs h1 at columns x - 1, x, x + 1.  Instead of shifting operands, the taps of one dx accumulate into their own
-//     tile, P_dx[x'] = sum_dy W[dy][dx] h1[y + dy][x'], and out[x] = P_-1[x - 1] + P_0[x] + P_+1[x + 1]: two additions per value with a
-//     wavefront DPP shift on one source (v_add_f32_dpp wave_shr:1 / wave_shl:1; tools/probes/dpp_wave_shift.hip shows gfx950 executes
-//     them).  Lanes 0 and 31 of a tile have no neighbour and are not stored: a strip yields 30 columns, nine strips cover a row
-//     (12.5 % of the products are spent on the overlap; in exchange there is NO LDS traffic but the weight fragments, and NO barrier
-//     after the prologue: waves never wait for each other).
+//   * The 3 x 3 needs h1 at columns x - 1, x, x + 1.  There is NO LDS traffic but the weight fragments and the features, and NO barrier
+//     after the prologue: waves never wait for each other.  The two forms differ in how the column neighbours meet.  The 32-column
+//     form (development build) shifts the OUTPUTS: the taps of one dx accumulate into their own tile, P_dx[x'] = sum_dy W[dy][dx]
+//     h1[y + dy][x'], and out[x] = P_-1[x - 1] + P_0[x] + P_+1[x + 1]: two additions per value with a wavefront DPP shift on one source
+//     (v_add_f32_dpp wave_shr:1 / wave_shl:1; tools/probes/dpp_wave_shift.hip shows gfx950 executes them).  Lanes 0 and 31 of its tile
+//     have no neighbour and are not stored: a strip yields 30 columns, nine strips cover a row (12.5 % of the products are spent on
+//     the overlap).  The product's form shifts the OPERANDS (stream16.h) and makes the two h1 pixels beside the strip itself: every
+//     column of a strip is stored, eight strips cover a row.
 //   * Same products as conv4.hip's form (three f16 products per term, fp32 accumulate); the block's 1 -> 32 residual (rank 1) and both
 //     biases ride in spare K slots of the matrix products; ReLU, both planes of c1 and of pool1 = maxpool2x2(c1) written from
 //     registers (the row pair's first row waits in LDS words of its own).
 // Work unit = (window, band of `rows` rows, strip); a wave's units are independent.  LDS: the second conv's banks (36 KB), per wave a
-// feature patch (5 KB) and the pooling row (4 KB).  Two waves per SIMD.
+// feature patch (5 KB) and the pooling row (4 KB; 2 KB in the product's form).  Two waves per SIMD.
 //
 // Two forms, one idea.  conv1_stream_kernel (below, first): one 32-column tile per strip row on v_mfma_f32_32x32x16_f16 -- the round's
 // first version, kept in the DEVELOPMENT build (SOFTSPOKEN_C1S_FORM=32).  conv1_stream16_kernel (further down): two interleaved
 // 16-pixel tiles on v_mfma_f32_16x16x32_f16 -- the product's form; its header says what changes.  Launch table (both): grid = one
 // 512-thread block per CU (8 waves, 2 per SIMD, amdgpu_waves_per_eu(2, 2)), a wave takes units blockIdx * 8 + wave, + 8 * grid, ...;
-// TRACK = per-value f16 range test (false when weights.hip proved the range: ConvPlan::s1_range_proven); dynamic LDS 109 / 95 KB.
+// TRACK = per-value f16 range test (false when weights.hip proved the range: ConvPlan::s1_range_proven); dynamic LDS 109 / 100 KB.
 #include "kernels.h"
 #include "stream16.h"
 #include <algorithm>
@@ -372,27 +374,43 @@ void conv1_stream_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 }
 
 // =========================================================================================================
-// The same kernel on v_mfma_f32_16x16x32_f16 (round 4, late).  Measured first as a timing-only ablation (tools/experiments/
-// r04_mfma_16x16x32_timing.patch): the second conv's 54 products per row as 108 of the small shape, operands unchanged: 2035 -> 1480 us per
-// 1005 windows -- the small shape moves half the accumulator registers per multiply-add and costs about a quarter less energy, which under
-// the power cap is time (tools/probes/mfma_valu_overlap.hip: a matrix-only loop 2.17 -> 1.65 us).  What changes with 16-pixel tiles:
+// The product's form: v_mfma_f32_16x16x32_f16 and stream16.h's core without overlap columns.  The small shape was measured first as a
+// timing-only ablation (tools/experiments/r04_mfma_16x16x32_timing.patch): the second conv's 54 products per row as 108 of the small
+// shape, operands unchanged: 2035 -> 1480 us per 1005 windows -- it moves half the accumulator registers per multiply-add and costs about
+// a quarter less energy, which under the power cap is time (tools/probes/mfma_valu_overlap.hip: a matrix-only loop 2.17 -> 1.65 us).
 //   * Layouts (tools/probes/mfma_16x16x32_layout.hip): A lane l = row l & 15, k = 8 (l >> 4) + j; B lane l = column l & 15, same k; D lane l
-//     = column l & 15, rows 4 (l >> 4) + r.  Lane (g, c) = (l >> 4, l & 15).  A strip's 32 columns are TWO pixel tiles, INTERLEAVED: tile t
-//     holds strip columns m = 2 c + t.  Then the 3 x 3's column neighbours of tile 1 are tile 0's values in the SAME lane and those of
-//     tile 0 are tile 1's one lane over: out[0] = P0[0] + row_shr:1(P-[1]) + P+[1], out[1] = P0[1] + P-[0] + row_shl:1(P+[0]) -- as many
-//     shifted additions as with one 32-column tile; and a pooled pair (x even, x + 1) is (tile 1 lane c, tile 0 lane c + 1): one DPP max.
+//     = column l & 15, rows 4 (l >> 4) + r.  Lane (g, c) = (l >> 4, l & 15).  Work unit = (window, band, strip of 32 columns), EIGHT strips
+//     a row: strip s holds picture columns 32 s .. 32 s + 31 as two pixel tiles, interleaved: tile t's lane c is column 32 s + 2 c + t,
+//     and every lane stores.  The 3 x 3's column neighbours are operands moved a lane (stream16.h): all nine taps go into ONE
+//     accumulator set, which starts from the rank-1 / bias product -- nothing is zeroed, nothing is added up afterwards, out = relu(P).
+//   * The halo: the taps of dx = -1 / +1 need h1 at columns 32 s - 1 and 32 s + 32.  h1 is not in memory, so a THIRD 16-column first-conv
+//     tile makes it: lanes c < 8 take the features around column 32 s - 1, the others those around 32 s + 32 (lanes 0 and 15 are the
+//     ones used), same products, ReLU and split as the other two tiles -- a halo value is the neighbouring strip's own value, bit for
+//     bit.  Left of strip 0 and right of strip 7 it lies outside the picture and is the second conv's zero padding: there the tile's
+//     B operand is cleared (features and the 1.0s against the bias alike), so its products give exact zeros.  The shifted operands are
+//     made once, with the row (S16RowS: 16 DPP moves per row).
 //   * Channels: output row i = 4 g + r of channel tile u is channel 8 g + 4 u + r, in both convs.  So the first conv's two result tiles
 //     of a lane ARE the next operand's eight K values in natural order (k = input channel), and a lane's results of both channel tiles
 //     are channels 8 g .. 8 g + 7 of its pixel: one 16-byte store per pixel tile and plane, no half-wave swaps.
 //   * First conv: K = 32 holds the 9 taps against (b_hi | b_lo) side by side: lanes g = 0 / 1 carry the high halves of rows (r - 1, r) /
 //     (r + 1, and 1.0 for the bias pair), lanes g = 2 / 3 the low halves; w_hi x (b_hi + b_lo) + bias is ONE product, w_lo x b_hi a second
-//     one on the same operand (its A is zero in the b_lo lanes).  8 products per row where the 32-column form issues 3 of twice the size.
-// Per row and wave: 8 + 4 + 108 products of 16 matrix cycles (1920; the other form 58 of 32 = 1856), about the same vector instructions
-// (operand building twice, no swaps, half the pooling).  Same numbers as the other form up to the summation order inside a product.
-// The second conv's core -- operand rows, the tap loop, the shifted combine, the split into 16-byte runs -- is stream16.h's, which
-// conv9s.hip runs as well.
+//     one on the same operand (its A is zero in the b_lo lanes).
+//   * Pooling: the pair (x even, x + 1) is (tile 0, tile 1) of the SAME lane: a plain maximum, and all 16 lanes store a pooled pixel.
+//   * The 12 + 4 products in front of the taps: the first conv's w_hi fragments stay in registers, its w_lo and the rank-1 operand's are
+//     read from the LDS in the TAIL of the row step before (behind the taps, in front of the stores), so they hold no registers during
+//     the taps and are there when the row starts; tap 0's fragments, requested in front of the 16, have 16 products to arrive.
+// Per row and wave: 12 + 4 + 108 = 124 products of 16 matrix cycles, eight strips a row: 992 products per picture row where nine strips
+// of 120 made 1080.  Same numbers as the other forms up to the summation order.
 // =========================================================================================================
-static constexpr int kFPatch16 = (kMaxRows + 6) * kFPitch;   // + a row of zeros (the odd lane groups' second feature row)
+// columns 32 s - 2 .. 32 s + 33 (exactly kFPitch); + a spare row + a row of zeros and a row of ones (the odd lane groups' second feature row)
+static constexpr int kFPatch16 = (kMaxRows + 7) * kFPitch;
+
+// a feature as the patch holds it: f16(x) in the low half, f16(x - f16(x)) in the high half (split_lo's halves, one value per word)
+__device__ __forceinline__ uint32_t s1_split_word(float x) {
+    uint32_t w = pack_f16(x, 0.f);
+    asm("v_fma_mixhi_f16 %0, %0, -1.0, %1 op_sel_hi:[1,0,0]" : "+v"(w) : "v"(x));
+    return w;
+}
 
 template <bool TRACK>
 __global__ __launch_bounds__(64 * kS1Waves) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -401,7 +419,7 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
     char* sW = smem;                                      // [plane][tap][channel tile][lane][16 B]
     char* sK = smem + 2 * kBank;                          // [4][lane][16 B]: the first conv's w_lo operand (channel tile 0, 1), the rank-1 / bias operand (0, 1)
     char* sPrev = sK + 4 * 1024;                          // [wave][2][lane][16 B]: the even row's column maxima of a row pair, for the pooling
-    float* sF = (float*)(sPrev + kS1Waves * 2048);        // [wave][row][kFPitch]: the unit's features, zero outside the picture; last row: zeros
+    uint32_t* sF = (uint32_t*)(sPrev + kS1Waves * 2048);  // [wave][row][kFPitch]: the unit's features, SPLIT (hi | lo << 16), zero outside the picture; last rows: zeros, ones
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, c = lane & 15;
@@ -433,15 +451,23 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             if (tid < 64) { *(u32x4*)(sK + u * 1024 + lane * 16) = lo; *(u32x4*)(sK + (2 + u) * 1024 + lane * 16) = wr; }
         }
     }
-    if (lane < kFPitch) sF[wave * kFPatch16 + (kMaxRows + 5) * kFPitch + lane] = 0.f;     // this wave's row of zeros
-    const uint32_t one1 = g == 1 ? 0x3c000000u : 0u, one2 = g == 1 ? 0x00003c00u : 0u;   // the 1.0s against the bias pair (K slots 3 and 4 of group 1)
-    const bool lo_group = g >= 2;
+    // this wave's row of zeros and its row of ones (1.0 = 0x3c00 | 0 << 16).  Lane group 1's second feature row is the ones: its K slots
+    // 4 .. 7 read (1, 1, 1, 0) where the filter holds (b_lo, 0, 0, 0) -- the 1.0 against b_lo; a one against a zero adds nothing
+    if (lane < kFPitch) { sF[wave * kFPatch16 + (kMaxRows + 5) * kFPitch + lane] = 0u; sF[wave * kFPatch16 + (kMaxRows + 6) * kFPitch + lane] = 0x3c00u; }
+    // a lane's B operand is assembled from the patch's words by byte permutes: the high-half groups g = 0, 1 pick every word's low
+    // 16 bits, the low-half groups g = 2, 3 its high 16 bits (v_perm_b32: bytes 0 .. 3 of the second source, 4 .. 7 of the first)
+    const uint32_t selg = g >= 2 ? 0x07060302u : 0x05040100u;
+    const uint32_t one1 = g == 1 ? 0x00003c00u : 0u;     // the 1.0 against b_hi (K slot 3 of group 1), as the permute's first source
     const char* sKl = sK + lane * 16;
     __syncthreads();                                      // the only barrier
 
     const char* wl_base = sW + lane * 16;
 #ifdef SS_DEVBUILD
-    uint32_t st_sum[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u}, st_prev = 0;      // (segments as in the 32-column form)
+    // stamps (dev build, SOFTSPOKEN_STAMP_LAYER=conv1_1.B): shader-clock time per row, summed per wave: [0] products, [1] h1 production,
+    // [2] split + stores, [3] pooled row, [4] the fence in front of the products (one stamp's own cost); [5] rows; [6] a unit's prologue
+    // (Round 11, per row and wave, 1005 windows, stamps on: taps 2390 | h1 production with the 12 + 4 products in front of the taps 1335 |
+    // split + stores 670 | pooled row 372 | one stamp 223 | the unit's prologue, per row 388.)
+    uint32_t st_sum[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u}, st_prev = 0;
     auto stamp = [&](int seg) {
         if (a.stamps) { const uint32_t t = (uint32_t)__builtin_amdgcn_s_memtime(); if (seg >= 0) st_sum[seg] += t - st_prev; st_prev = t; }
     };
@@ -453,26 +479,19 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
     for (int unit = (int)blockIdx.x * kS1Waves + wave; unit < total_units; unit += (int)gridDim.x * kS1Waves) {
         stamp(-1);
         const int bands = kH / rows_per_unit;
-        const int s = unit % kStrips, b = (unit / kStrips) % bands, n = unit / (kStrips * bands);
-        const int x0 = kStripCols * s - 1, y0 = b * rows_per_unit;
-        const bool edge_strip = s == 0 || s == kStrips - 1;
-        uint32_t keep[2]; bool st_lane[2];
-        int xt[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int mm = 2 * c + t;                     // this lane's strip column in pixel tile t
-            xt[t] = x0 + mm;
-            keep[t] = (unsigned)xt[t] < (unsigned)kW ? 0xffffffffu : 0u;
-            st_lane[t] = mm >= 1 && mm <= kStripCols && xt[t] < kW;
-        }
-        const bool pl_lane = st_lane[1] && 2 * c + 1 < kStripCols;      // tile 1's lane is the left (x even) pixel of a pooled pair
-        // ---- the unit's feature patch (as in the 32-column form) ----
-        float* pf = sF + wave * kFPatch16;
+        const int s = unit % kStrips32, b = (unit / kStrips32) % bands, n = unit / (kStrips32 * bands);
+        const int x0 = 32 * s, y0 = b * rows_per_unit;
+        const int xc = x0 + 2 * c;                        // this lane's picture column in pixel tile 0; tile 1's is the next one
+        // the halo pixel (lanes c < 8: column x0 - 1, the others: x0 + 32) lies outside the picture left of strip 0 and right of strip 7
+        const uint32_t hkeep = (c < 8 ? s > 0 : s < kStrips32 - 1) ? 0xffffffffu : 0u;
+        // ---- the unit's feature patch: rows y0 - 2 .. y0 + rows + 1, columns x0 - 2 .. x0 + 33, zero outside the picture (the first conv's
+        // zero padding), into this wave's LDS region: all loads in flight together, ONE wait per unit (as in the 32-column form) ----
+        uint32_t* pf = sF + wave * kFPatch16;
         {
             const float* fn = a.rank1_src + (size_t)n * kH * kW;
             const int nrow = rows_per_unit + 4;
-            const int cc = lane < 34 ? lane : 33, gx = x0 - 1 + cc;
-            const bool cok = lane < 34 && (unsigned)gx < (unsigned)kW;
+            const int cc = lane < kFPitch ? lane : kFPitch - 1, gx = x0 - 2 + cc;
+            const bool cok = lane < kFPitch && (unsigned)gx < (unsigned)kW;
             const int gxc = min(max(gx, 0), kW - 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             bool fbad = false;
@@ -488,44 +507,57 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             }
 #pragma unroll
             for (int j = 0; j < NR; ++j)
-                if (lane < 34 && j < nrow) pf[j * kFPitch + cc] = tv[j];
+                if (lane < kFPitch && j < nrow) pf[j * kFPitch + cc] = s1_split_word(tv[j]);      // split ONCE per unit and feature
             if (fbad) ovf = 0x7c007c00u;
         }
-        // this lane's feature reads for h1 row r: patch row of picture row Y is Y - y0 + 2; even lane groups read rows r - 1 and r, odd
-        // ones row r + 1 and the row of zeros; columns 2 c + t + (0, 1, 2) = the pixel's x - 1, x, x + 1
-        const float* pcol = pf + 2 * c;
-        const float* zrow = pf + (kMaxRows + 5) * kFPitch + 2 * c;
+        // this lane's feature reads for h1 row r: patch row of picture row Y is Y - y0 + 2, patch column of picture column X is X - x0 + 2;
+        // even lane groups read rows r - 1 and r, odd ones row r + 1 and the row of ones (g = 1) or zeros (g = 3); a pixel's columns
+        // x - 1, x, x + 1 are 2 c + t + 1 + (0, 1, 2) for tiles 0 and 1, (0, 1, 2) / 33 + (0, 1, 2) for the halo tile
+        const uint32_t* pcol = pf + 2 * c + 1;
+        const uint32_t* hcol = pf + (c < 8 ? 0 : 33);
+        const int zoff = (kMaxRows + (g == 1 ? 6 : 5)) * kFPitch;
+        const uint32_t selh = hkeep ? selg : 0x0c0c0c0cu;  // (selector 0x0c: a zero byte) the halo tile's operand outside the picture: zeros
 
-        S16Row H0, H1, H2;
+        S16RowS H0, H1, H2;
         char* prevp = sPrev + wave * 2048 + lane * 16;
-        float fa[2][3], fb[2][3], fcen[2];
+        char* orow = (char*)a.out + (((size_t)n * kH + y0) * kW + (size_t)xc) * (kC * 2) + g * 16;                    // (row y0; tile 1: 64 bytes on)
+        char* prow = (char*)a.pool_out + (((size_t)n * (kH / 2) + (y0 >> 1)) * (kW / 2) + (size_t)(xc >> 1)) * (kC * 2) + g * 16;
+        uint32_t fa[3][3], fb[3][3], fcen[2];             // [tile: 0, 1, halo][dx]: split words
+        // the A fragments of the 12 + 4 products in front of the taps, [channel tile]: read in the tail of the row step before, so that they
+        // occupy no registers during the taps and no product waits for their round trip
+        u32x4 kwl[2], wrq[2];
+        auto request_k = [&] {
+            kwl[0] = *(const u32x4*)(sKl); kwl[1] = *(const u32x4*)(sKl + 1024);
+            wrq[0] = *(const u32x4*)(sKl + 2048); wrq[1] = *(const u32x4*)(sKl + 3072);
+        };
         auto request = [&](int r) {                       // for produce(r) and the output row r - 1
-            const float* q0 = pcol + (r - y0 + 1 + 2 * (g & 1)) * kFPitch;
-            const float* q1 = (g & 1) ? zrow : q0 + kFPitch;
+            const int ro = (r - y0 + 1 + 2 * (g & 1)) * kFPitch, ro1 = (g & 1) ? zoff : ro + kFPitch;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                fa[t][0] = q0[t]; fa[t][1] = q0[t + 1]; fa[t][2] = q0[t + 2];
-                fb[t][0] = q1[t]; fb[t][1] = q1[t + 1]; fb[t][2] = q1[t + 2];
-                fcen[t] = pcol[(r - y0 + 1) * kFPitch + t + 1];
+            for (int t = 0; t < 3; ++t) {
+                const uint32_t* q = t < 2 ? pcol + t : hcol;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { fa[t][i] = q[ro + i]; fb[t][i] = q[ro1 + i]; }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) fcen[t] = pcol[(r - y0 + 1) * kFPitch + t + 1];
+        };
+        auto zero_row = [&](S16RowS& Hn) {
+#pragma unroll
+            for (int pq = 0; pq < 2; ++pq) {
+                Hn.f[0][pq] = u32x4{0u, 0u, 0u, 0u}; Hn.f[1][pq] = u32x4{0u, 0u, 0u, 0u};
+                Hn.l[pq] = u32x4{0u, 0u, 0u, 0u}; Hn.r[pq] = u32x4{0u, 0u, 0u, 0u};
             }
         };
-        auto zero_row = [&](S16Row& Hn) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) Hn.f[t][pl] = u32x4{0u, 0u, 0u, 0u};
-        };
-        auto produce = [&](int r, S16Row& Hn, const u32x4 (&kwl)[2]) {
+        auto produce = [&](int r, S16RowS& Hn) {
             if ((unsigned)r < (unsigned)kH) {             // (wave-uniform)
+                u32x4 halo[2];
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    uint32_t bh[4], bl[4];
-                    bh[0] = pack_f16(fa[t][0], fa[t][1]); bl[0] = split_lo(bh[0], fa[t][0], fa[t][1]);
-                    bh[1] = pack_f16(fa[t][2], 0.f);      bl[1] = split_lo(bh[1], fa[t][2], 0.f);
-                    bh[2] = pack_f16(fb[t][0], fb[t][1]); bl[2] = split_lo(bh[2], fb[t][0], fb[t][1]);
-                    bh[3] = pack_f16(fb[t][2], 0.f);      bl[3] = split_lo(bh[3], fb[t][2], 0.f);
-                    bh[1] |= one1; bh[2] |= one2;
-                    const u32x4 bop = lo_group ? u32x4{bl[0], bl[1], bl[2], bl[3]} : u32x4{bh[0], bh[1], bh[2], bh[3]};
+                for (int t = 0; t < 3; ++t) {
+                    // K slots (x - 1, x | x + 1, 1 or 0 | x - 1, x | x + 1, 0) of the lane's two feature rows, its half of every word
+                    // (a halo pixel outside the picture: all zeros -- h1 = 0, the second conv's zero padding)
+                    const uint32_t sel = t == 2 ? selh : selg;
+                    const u32x4 bop = {__builtin_amdgcn_perm(fa[t][1], fa[t][0], sel), __builtin_amdgcn_perm(one1, fa[t][2], sel),
+                                       __builtin_amdgcn_perm(fb[t][1], fb[t][0], sel), __builtin_amdgcn_perm(0u, fb[t][2], sel)};
                     uint32_t ph[2][2], pl[2][2];
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
@@ -536,57 +568,52 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
                         for (int hq = 0; hq < 2; ++hq) {
                             const float v0 = relu_i(h[2 * hq]), v1 = relu_i(h[2 * hq + 1]);
                             ph[u][hq] = pack_f16(v0, v1);
-                            if constexpr (TRACK) ovf = pk_max_u16(ovf, ph[u][hq]);
+                            if constexpr (TRACK) { if (t < 2) ovf = pk_max_u16(ovf, ph[u][hq]); }     // (a halo value is tested by the strip that stores it)
                             pl[u][hq] = split_lo(ph[u][hq], v0, v1);
                         }
                     }
-                    Hn.f[t][0] = u32x4{ph[0][0], ph[0][1], ph[1][0], ph[1][1]};
-                    Hn.f[t][1] = u32x4{pl[0][0], pl[0][1], pl[1][0], pl[1][1]};
-                    if (edge_strip) {                     // (wave-uniform) h1 outside the picture is the second conv's zero padding
-#pragma unroll
-                        for (int pq = 0; pq < 2; ++pq)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) Hn.f[t][pq][e] &= keep[t];
-                    }
+                    const u32x4 xh = {ph[0][0], ph[0][1], ph[1][0], ph[1][1]}, xl = {pl[0][0], pl[0][1], pl[1][0], pl[1][1]};
+                    if (t < 2) { Hn.f[t][0] = xh; Hn.f[t][1] = xl; } else { halo[0] = xh; halo[1] = xl; }
                 }
-            } else zero_row(Hn);
+                s16_make_shifted(Hn, halo);
+            } else zero_row(Hn);                          // rows outside the picture are zero operands
         };
 
-        auto row_step = [&](int y, const S16Row& Ha, const S16Row& Hb, S16Row& Hn) {
-            const float fc[2] = {fcen[0], fcen[1]};       // f(y, x) (requested with row y + 1's features)
+        // one output row: h1 of row y + 1 into Hn, then the row's products against Ha (row y - 1), Hb (y), Hn (y + 1)
+        auto row_step = [&](int y, const S16RowS& Ha, const S16RowS& Hb, S16RowS& Hn) {
+            const uint32_t fc[2] = {fcen[0], fcen[1]};    // f(y, x), split (requested with row y + 1's features)
             stamp(-1);
-            // a group = one tap: both channel tiles' fragments (four 16-byte reads), requested one group ahead (a group's products: 192 cycles)
-            S16Ring ring;
-            const u32x4 kwl[2] = {*(const u32x4*)(sKl), *(const u32x4*)(sKl + 1024)};
-            const u32x4 wrq[2] = {*(const u32x4*)(sKl + 2048), *(const u32x4*)(sKl + 3072)};
-            ring.rd(wl_base, 0);
+            // tap 0's fragments are requested in front of the 12 + 4 products whose own came in the last tail; every later tap's one tap (12 products) ahead
+            S16Ring3 ring;                                // (two of its slots)
+            ring.rd_tap(0, wl_base, 0);
             __builtin_amdgcn_sched_barrier(0);
-            produce(y + 1, Hn, kwl);
-            request(y + 2);
+            produce(y + 1, Hn);
+            request(y + 2);                               // (unconditional; lands behind this row's products)
             stamp(1);
-            // ---- second conv: P[dx][t][u] = sum over dy of W[dy][dx] x h1[y + dy] (three products per term) ----
-            f32x4 P[3][2][2];
+            // ---- second conv: P[t][u] starts from the rank-1 residual + bias and takes the nine taps (three products per term) ----
+            f32x4 P[2][2];
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {                 // rank-1 residual + bias start P[dx = 0]; the others start at 0
-                const uint32_t fh = pack_f16(fc[t], fc[t]);
-                const uint32_t fl = split_lo(fh, fc[t], fc[t]);
-                u32x4 bop = {(fh & 0xffffu) | (fl << 16), (fh & 0xffffu) | 0x3c000000u, 0x3c00u, 0u};
-                if (g != 0) bop = u32x4{0u, 0u, 0u, 0u};
+            for (int t = 0; t < 2; ++t) {
+                // (f_hi, f_lo, f_hi, 1, 1): the first word is the patch's own.  Lane groups 1 .. 3 hold zeros in wrq: what they put here adds nothing
+                const u32x4 bop = {fc[t], __builtin_amdgcn_perm(0x3c003c00u, fc[t], 0x05040100u), 0x3c00u, 0u};
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    P[0][t][u] = f32x4{0.f, 0.f, 0.f, 0.f}; P[2][t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    P[1][t][u] = s16_mfma(wrq[u], bop, f32x4{0.f, 0.f, 0.f, 0.f});
-                }
+                for (int u = 0; u < 2; ++u) P[t][u] = s16_mfma(wrq[u], bop, f32x4{0.f, 0.f, 0.f, 0.f});
             }
             __builtin_amdgcn_sched_barrier(0);
             stamp(4);
-            s16_taps(ring, wl_base, Ha, Hb, Hn, P, [](int) {});
+            s16_taps_shifted(ring, wl_base, Ha, Hb, Hn, P, [] {}, [](int) {});
+            __builtin_amdgcn_sched_barrier(0);
             stamp(0);
-            // ---- out[x] = P_-1[x - 1] + P_0[x] + P_+1[x + 1], ReLU: tile 0's neighbours are tile 1's lanes c - 1 / c, tile 1's are tile 0's c / c + 1 ----
+            request_k();                                  // (for the next row step)
             float v[2][2][4];
-            s16_combine(P, v);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[t][u][r] = relu_i(P[t][u][r]);
             // a lane's eight values of a pixel tile are channels 8 g .. 8 g + 7 of its pixel: one 16-byte run per plane
-            auto store_px = [&](const float (&val)[2][4], char* dst, bool on, auto track_c) {
+            auto store_px = [&](const float (&val)[2][4], char* dst, auto track_c) {
                 constexpr bool track = TRACK && decltype(track_c)::value;
                 uint32_t kh[4], kl[4];
                 s16_split_px(val, kh, kl);
@@ -594,32 +621,28 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ovf = pk_max_u16(ovf, kh[i]);
                 }
-                if (on) {
-                    *(u32x4*)(dst) = u32x4{kh[0], kh[1], kh[2], kh[3]};
-                    *(u32x4*)(dst + a.lo_delta) = u32x4{kl[0], kl[1], kl[2], kl[3]};
-                }
+                *(u32x4*)(dst) = u32x4{kh[0], kh[1], kh[2], kh[3]};
+                *(u32x4*)(dst + a.lo_delta) = u32x4{kl[0], kl[1], kl[2], kl[3]};
             };
             f32x4 prv[2];
             if (y & 1) { prv[0] = *(const f32x4*)(prevp); prv[1] = *(const f32x4*)(prevp + 1024); }
             __builtin_amdgcn_sched_barrier(0);
+            char* o = orow + (size_t)(y - y0) * (kW * kC * 2);
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-                store_px(v[t], (char*)a.out + (((size_t)n * kH + y) * kW + (size_t)max(xt[t], 0)) * (kC * 2) + g * 16, st_lane[t], std::true_type{});
+            for (int t = 0; t < 2; ++t) store_px(v[t], o + t * (kC * 2), std::true_type{});
             stamp(2);
-            // ---- pooling: the pair (x even, x + 1) is (tile 1 lane c, tile 0 lane c + 1); values are >= 0: integer maxima ----
+            // ---- pooling: the pair (x even, x + 1) is (tile 0, tile 1) of this lane; values are >= 0: integer maxima ----
             float cm[2][4];
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    cm[u][r] = __int_as_float(max(__float_as_int(v[1][u][r]), s16_shl1(__float_as_int(v[0][u][r]))));
+                for (int r = 0; r < 4; ++r) cm[u][r] = __int_as_float(max(__float_as_int(v[0][u][r]), __float_as_int(v[1][u][r])));
             if (y & 1) {                                  // (wave-uniform) second row of a pair
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) cm[u][r] = __int_as_float(max(__float_as_int(cm[u][r]), __float_as_int(prv[u][r])));
-                store_px(cm, (char*)a.pool_out + (((size_t)n * (kH / 2) + (y >> 1)) * (kW / 2) + (size_t)(max(xt[1], 0) >> 1)) * (kC * 2) + g * 16, pl_lane,
-                         std::false_type{});              // (a pooled value is one of the values tested above)
+                store_px(cm, prow + (size_t)((y - y0) >> 1) * ((kW / 2) * kC * 2), std::false_type{});   // (a pooled value is one of the values tested above)
             } else {
                 *(f32x4*)(prevp) = f32x4{cm[0][0], cm[0][1], cm[0][2], cm[0][3]};
                 *(f32x4*)(prevp + 1024) = f32x4{cm[1][0], cm[1][1], cm[1][2], cm[1][3]};
@@ -629,13 +652,12 @@ void conv1_stream16_kernel(ConvArgs a, int rows_per_unit, int total_units) {
             ++st_sum[5];
 #endif
         };
-        {
-            const u32x4 kwl0[2] = {*(const u32x4*)(sKl), *(const u32x4*)(sKl + 1024)};
-            request(y0 - 1); produce(y0 - 1, H0, kwl0);
-            request(y0);     produce(y0, H1, kwl0);
-            request(y0 + 1);
-        }
+        request_k();
+        request(y0 - 1); produce(y0 - 1, H0);
+        request(y0);     produce(y0, H1);
+        request(y0 + 1);
         stamp(6);
+        // the three h1 rows change roles instead of places: three steps per turn
         int k = 0;
         for (; k + 3 <= rows_per_unit; k += 3) {
             row_step(y0 + k, H0, H1, H2);
@@ -668,7 +690,7 @@ size_t conv1_stream_weight_bytes() { return 2 * (size_t)kBank; }
 
 hipError_t launch_conv1_stream(const ConvArgs& a, int form, int rows_per_unit, int num_cus, hipStream_t s) {
     if (!conv1_stream_supports(a) || rows_per_unit < 2 || (rows_per_unit & 1) || kH % rows_per_unit || rows_per_unit > kMaxRows) return hipErrorInvalidValue;
-    const int64_t total = (int64_t)a.N * (kH / rows_per_unit) * kStrips;
+    const int64_t total = (int64_t)a.N * (kH / rows_per_unit) * (form == 16 ? kStrips32 : kStrips);
     if (total >= (int64_t)1 << 30) return hipErrorInvalidValue;
     const int cus = num_cus > 0 ? num_cus : 256;
     const int grid = (int)std::min<int64_t>(cus, (total + kS1Waves - 1) / kS1Waves);
