@@ -556,6 +556,65 @@ int ss_separate_pcm(ss_ctx* ctx, const void* pcm, int format, int sample_rate, i
 int ss_separate_pcm_channels(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames,
                              const ss_region* regions, int64_t n_regions, const ss_separation_params* params, int16_t* out);
 
+/* ---- region bands: the frequency extent of the speech inside each region, from the spec head -----------------------------
+ * The reference's Raven table gives every detection the box 0 .. 8000 Hz (review_exporter.py, low_freq / high_freq).  The spec head's
+ * speech map says where in the 128 mel bands the voice sits; this section reduces it, on the device, to the measures Raven users work
+ * with: the 5 % / 95 % energy frequencies and the peak frequency.  For a file already added (each-channel form: the files
+ * first_file .. first_file + n_channels - 1 of ss_add_pcm_channels*) and n caller-given regions (ss_region: seconds, the "-3" applied):
+ *  1. Bins of a region.  Bin j is centred at t_j = (j + 0.5) 3 / 256 - 3 s and belongs to [start, end) when start <= t_j < end: the
+ *     first bin and the exclusive end are ceil((x + 3.0) * 256.0 / 3.0 - 0.5) for x = start and x = end, evaluated in double from left
+ *     to right (no two of its operations can contract into an FMA), clamped to the covered bins [0, n_bins) of the file (the whole-file
+ *     average's bins, ss_separation_plan_info.n_bins).  A region of the detector's own "%.4f" table keeps its bins under that
+ *     rounding: half a bin is 5.9 ms.  Regions may overlap, repeat, come in any order or be empty; a region without a bin gets "no
+ *     estimate" (step 4), which is no error.  SS_ERR_ARG for a region that is not finite or has end < start.
+ *  2. Maps.  Step 1 of the separation silencer, unchanged: default-step (0.6 s) windows whatever ss_set_window_step says, the spec
+ *     head on exactly the windows that cover a needed bin, a float64 sum in ascending window order divided by the count, stored as
+ *     float32 -- bit for bit what ss_separation_maps returns for those bins.
+ *  3. Profile.  Per region, spec channel c and band m: E_c[m] = sum_j P(y_c[j][m]), P(y) = expm1(min(y * y * ln 10, 600)) in double
+ *     (the power behind a feature value, as the silencer's step 2; the cap keeps any sum of fewer than 2^64 bins finite); a NaN y
+ *     adds 0, an infinite one the cap.  The order of the sum is fixed: the bins of a region are grouped into tiles by their absolute
+ *     number j >> 6, a tile's sum is a sequential ascending float64 sum, and a region's tile sums are added in ascending tile order.
+ *     So the work may be cut at tile boundaries, into as many pieces as memory asks for, without changing a bit.
+ *  4. Bounds, on the speech channel (params->speech_channel, default 1 as in ss_separation_params): C[m] = C[m - 1] + E[m], sequential
+ *     and ascending, T = C[127]; band_low is the smallest m with C[m] >= q_low T, band_high the smallest m with C[m] >= q_high T,
+ *     band_peak the argmax of E (the lowest index on ties).  In Hz, with f[0 .. 129] the front-end's 130 HTK mel points
+ *     (ss_band_edges: the float32 recipe of its filterbank, as doubles): low_hz = f[band_low] (the triangle's lower edge),
+ *     high_hz = f[band_high + 2] (its upper edge), peak_hz = f[band_peak + 1].  speech_share = T_speech / (T_speech + T_env), T_env
+ *     the same sequential sum over the other channel; n_bins = the bins used.  With T == 0 or n_bins == 0 the three band indices are
+ *     -1 and the three frequencies and the share NaN: "no estimate", consumers fall back to their constants.
+ *     Parameters: 0 < q_low < q_high <= 1 (defaults 0.05 / 0.95), speech_channel 0 or 1; otherwise SS_ERR_ARG. */
+typedef struct ss_band_params {
+    double q_low, q_high;              /* defaults 0.05, 0.95 */
+    int32_t speech_channel, reserved;  /* default 1; reserved: 0 */
+} ss_band_params;                      /* NULL params: the defaults */
+
+typedef struct ss_region_band {
+    double low_hz, high_hz, peak_hz, speech_share;
+    int32_t band_low, band_high, band_peak, n_bins;
+} ss_region_band;                      /* 48 bytes */
+
+/* Host only: the 130 mel points f of step 4. */
+int ss_band_edges(double* hz130);
+/* Host only: rule 1 for one region of a file with covered_bins covered bins: *first = its first bin, *count = its bins (0: empty; then
+ * *first is the clamped position of the start).  SS_ERR_ARG for a region that is not finite or has end < start, covered_bins < 0 or a
+ * NULL pointer. */
+int ss_region_bins(double start, double end, int64_t covered_bins, int64_t* first, int64_t* count);
+/* Steps 1 - 4: out[n][n_channels], profile (NULL, or [n][n_channels][2][128]: E of both spec channels in the head's order).
+ * n_channels == 1: the file first_file.  State rules and refusals are ss_separation_maps': the files are already added and stay,
+ * nothing is reset; SS_ERR_STATE on an audio-only context or while a run is in flight; SS_ERR_RANGE under SS_FLAG_F16X2 when the spec
+ * head's passes leave the f16 range (run the file in an fp32 context), with `out` not to be used.  n == 0 is SS_OK.  The last run's
+ * region tables (ss_get_regions*) stay readable; what reads the run's device buffers (ss_get_window_logits, ss_get_avg,
+ * ss_get_region_peaks) answers SS_ERR_STATE afterwards, as after ss_separation_maps or ss_infer_windows -- the passes reuse those
+ * buffers --, whenever a region had a bin: read them first.  Long tables are worked through
+ * in pieces of a fixed number of bins, cut at tile boundaries (step 3): the result does not depend on the cuts. */
+int ss_region_bands(ss_ctx* ctx, int first_file, int n_channels, const ss_region* regions, int64_t n, const ss_band_params* params,
+                    ss_region_band* out, double* profile);
+/* Steps 1, 3 and 4 on maps the caller supplies (ss_separation_maps' layout per signal): maps[n_signals][2][n_bins][128] hold the bins
+ * first_bin .. first_bin + n_bins - 1, and no other bin exists for this call (step 1 clamps to them).  out[n][n_signals], profile as
+ * above.  Needs a device but no weights; SS_ERR_STATE while a run is in flight. */
+int ss_region_bands_from_maps(ss_ctx* ctx, const float* maps, int n_signals, int64_t first_bin, int64_t n_bins, const ss_region* regions,
+                              int64_t n, const ss_band_params* params, ss_region_band* out, double* profile);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */
 int ss_sync(ss_ctx* ctx);
@@ -577,6 +636,11 @@ int ss_debug_fail_workspace_alloc(ss_ctx* ctx, int nth);
  * 256 MB frame buffer, so that a short recording meets the cuts of a long one: a chunk ends when the next piece would pass the number,
  * an interval is cut into pieces of (frames - 8) hops.  frames <= 0: the product's number again.  The bytes written must not depend on it. */
 int ss_debug_set_separation_budget(ss_ctx* ctx, int64_t frames);
+/* ss_region_bands covers at most `bins` bins (never fewer than 64) with one round of network passes, in place of the product's fixed
+ * number, so that a short recording meets the cuts of an hour of speech.  Pieces are cut at tile boundaries (absolute multiples of 64
+ * bins) only; a region may span pieces, its tile sums wait on the device until its last piece is done.  bins <= 0: the product's
+ * number again.  The bytes written must not depend on it. */
+int ss_debug_set_bands_budget(ss_ctx* ctx, int64_t bins);
 /* Activation tensors of the context's last network pass, for per-launch tests.  name: a tensor of the activation workspace ("h1" ... "s9"),
  * "feat" (the pass's features) or "flat_part" (conv_flatten's row-group partial sums, fp32 [n][groups][4][256] read as H = groups,
  * W = 4, C = 256; exponents: the common power of two they carry).  Copies windows [first_window, first_window + n_windows) of one plane as [n][H][W][C], whatever the stored

@@ -56,3 +56,7 @@ hip_selfcheck = True
 # (every channel detected alone -- a voice that reached one microphone is not halved by the mean --, the file's regions are "speech on
 # any channel"; which channel heard a region goes to <detections stem>_channels.csv).  A mono file gives the same results either way.
 hip_channel_mode = os.environ.get('SOFTSPOKEN_CHANNELS', 'mix')
+# region bands: '1' gives every detection its frequency extent (the 5 % / 95 % energy frequencies and the peak of the spec head's
+# speech map inside the region), written to <detections stem>_bands.csv; the Raven export then draws each selection's own box
+# instead of 0 .. 8000 Hz.  '0' (default): nothing is computed and no file is written.
+hip_region_bands = os.environ.get('SOFTSPOKEN_BANDS', '0')

@@ -55,6 +55,14 @@ def channel_mode():
     return mode
 
 
+def region_bands_enabled():
+    """settings.hip_region_bands, checked: '0' or '1'."""
+    v = getattr(settings, "hip_region_bands", "0")
+    if v not in ('0', '1'):
+        raise ValueError(f"settings.hip_region_bands (SOFTSPOKEN_BANDS) must be '0' or '1', not {v!r}")
+    return v == '1'
+
+
 def add_file_to_context(ctx, path, mode=None):
     """Upload a WAV file's samples and decode/mixdown/resample/pad them on the device. -> (file_id, WavInfo)
     mode (default settings.hip_channel_mode) 'each': no mixdown, the file's info.channels channels become the files file_id,

@@ -81,7 +81,7 @@ class ProcessWorker(_Base):
         self.planned_work = planned_work
         self.stop_requested = False
         self._stop_word = ctypes.c_int(0)       # polled by the library between chunks
-        self._channels_file_checked = False     # 'each' mode: the channels file has been cleared of rows beyond the detections CSV
+        self._side_files_checked = set()        # side files (_channels.csv, _bands.csv) already cleared of rows beyond the detections CSV
 
     def stop(self):
         self.stop_requested = True
@@ -116,6 +116,20 @@ class ProcessWorker(_Base):
             block.index = range(len(df), len(df) + n)
             self.detection_project.df = pd.concat([df, block.astype(df.dtypes.to_dict())])
 
+    def _side_file(self, csv_path, suffix, first_id):
+        """The path of the side file <detections stem><suffix>.  The first time a job asks for it, rows left by a detections CSV that has
+        since been deleted or recreated are dropped: their IDs (first_id and up) are about to be handed out again."""
+        side = splitext(csv_path)[0] + suffix
+        if suffix not in self._side_files_checked and exists(side):
+            with open(side, newline="") as fh:
+                rows = list(csv.reader(fh))
+            kept = [r for r in rows[1:] if r and r[0].isdigit() and int(r[0]) < first_id]
+            if len(kept) != len(rows) - 1:
+                with open(side, "w", newline="") as fh:
+                    csv.writer(fh, lineterminator="\n").writerows(rows[:1] + kept)
+        self._side_files_checked.add(suffix)
+        return side
+
     def _append_channel_rows(self, file, first_id, n_regions):
         """settings.hip_channel_mode == 'each': which channel heard each of the file's regions, appended to <detections stem>_channels.csv
         beside the detections CSV -- ID (the region's row in the detections CSV), file_name, n_channels, heard (the channels whose peak is
@@ -130,16 +144,7 @@ class ProcessWorker(_Base):
         if len(peaks) != n_regions:
             logging.warning("%s: %d regions but channel detail for %d -- no rows in the channels file", file, n_regions, len(peaks))
             return
-        side = splitext(csv_path)[0] + "_channels.csv"
-        if not self._channels_file_checked and exists(side):
-            # rows left by a detections CSV that has since been deleted or recreated: their IDs are about to be handed out again
-            with open(side, newline="") as fh:
-                rows = list(csv.reader(fh))
-            kept = [r for r in rows[1:] if r and r[0].isdigit() and int(r[0]) < first_id]
-            if len(kept) != len(rows) - 1:
-                with open(side, "w", newline="") as fh:
-                    csv.writer(fh, lineterminator="\n").writerows(rows[:1] + kept)
-        self._channels_file_checked = True
+        side = self._side_file(csv_path, "_channels.csv", first_id)
         new = not exists(side)
         with open(side, "a", newline="") as fh:
             out = csv.writer(fh, lineterminator="\n")
@@ -148,6 +153,35 @@ class ProcessWorker(_Base):
             for k, row in enumerate(peaks):
                 heard = ";".join(str(c) for c, v in enumerate(row) if v > settings.threshold)
                 out.writerow([first_id + k, basename(file), n_ch, heard, ";".join("%.6f" % v for v in row)])
+
+    def _append_band_rows(self, file, first_id, n_regions):
+        """settings.hip_region_bands == '1': the frequency extent of each of the file's regions, appended to <detections stem>_bands.csv
+        beside the detections CSV -- ID (the region's row in the detections CSV), file_name, channel ('each' mode: one row per channel;
+        'mix': one row, the field empty), low_hz / high_hz / peak_hz (%.1f), speech_share, n_bins (the averaged bins used).  A region
+        without an estimate has the five fields before n_bins empty.  Nothing for a detector without band_detail, a file the bands
+        were refused for, or a project without a detections file.  Stale rows: _side_file's rule, as the channels file."""
+        detail = getattr(self.detector, "band_detail", None)
+        project = getattr(getattr(self.detection_project, "settings", None), "current_project", None)
+        csv_path = project.get("detections_file") if isinstance(project, dict) else None
+        if not detail or file not in detail or not csv_path:
+            return
+        n_ch, bands = detail[file]
+        if len(bands) != n_regions:
+            logging.warning("%s: %d regions but bands for %d -- no rows in the bands file", file, n_regions, len(bands))
+            return
+        side = self._side_file(csv_path, "_bands.csv", first_id)
+        new = not exists(side)
+        with open(side, "a", newline="") as fh:
+            out = csv.writer(fh, lineterminator="\n")
+            if new:
+                out.writerow(["ID", "file_name", "channel", "low_hz", "high_hz", "peak_hz", "speech_share", "n_bins"])
+            for k, row in enumerate(bands):
+                for c, b in enumerate(row):
+                    if int(b["band_low"]) < 0:
+                        est = ["", "", "", ""]
+                    else:
+                        est = ["%.1f" % b["low_hz"], "%.1f" % b["high_hz"], "%.1f" % b["peak_hz"], "%.6f" % b["speech_share"]]
+                    out.writerow([first_id + k, basename(file), c if n_ch >= 1 else ""] + est + [int(b["n_bins"])])
 
     def run(self):
         """The reference's signal sequence per file (worker.py:49-139), with the device ahead of the host: files alternate between
@@ -225,11 +259,15 @@ class ProcessWorker(_Base):
                 files_done += 1
                 self.signals.overallProgressChanged.emit((files_done / total_files) * 100.0)
                 continue
-            first_id = self._next_id() if regions and getattr(settings, "hip_channel_mode", "mix") == "each" else None
+            each = getattr(settings, "hip_channel_mode", "mix") == "each"
+            bands = getattr(settings, "hip_region_bands", "0") == "1"
+            first_id = self._next_id() if regions and (each or bands) else None
             self._append_rows(file, regions)
             self.detection_project.save_detections()
-            if first_id is not None:
+            if first_id is not None and each:
                 self._append_channel_rows(file, first_id, len(regions))
+            if first_id is not None and bands:
+                self._append_band_rows(file, first_id, len(regions))
             self.signals.fileDone.emit(file)
             files_done += 1
             self.signals.overallProgressChanged.emit((files_done / total_files) * 100.0)

@@ -24,7 +24,7 @@ import torch
 
 from root.code.backend import settings
 from root.code.backend.pytorch_neural_nets import SpecUNet_2D
-from root.code.backend.voice_activity import add_file_to_context, channel_mode, get_audio_data
+from root.code.backend.voice_activity import add_file_to_context, channel_mode, get_audio_data, region_bands_enabled
 from softspoken_amd import native as _native
 
 try:                                   # 64-bit content hash at memory speed when the wheel is there, a 64-bit BLAKE2 from the stdlib otherwise
@@ -68,6 +68,9 @@ class NNDetector():
         # settings.hip_channel_mode == 'each': file -> (n_channels, [[peak of channel c ...] per region]) for the regions last returned
         # for that file (each channel's highest averaged score inside the region; a channel heard it when its peak > settings.threshold)
         self.channel_detail = {}
+        # settings.hip_region_bands == '1': file -> (n_channels ('mix': 0), ss_region_band records [regions, max(n_channels, 1)]) for the
+        # regions last returned for that file; no entry for a file whose bands the f16x2 mode refused
+        self.band_detail = {}
 
     # -- checkpoint ---------------------------------------------------------------------------------------
     def load_checkpoint(self, model, file_path='checkpoint.pth'):
@@ -215,13 +218,34 @@ class NNDetector():
             self.ctx, self.fid, self.file, self.brk, self.buf, self.which, self.reported = ctx, fid, file, brk, buf, which, False
             self.n_ch = n_ch              # 'each' mode: the file's channels are the files fid .. fid + n_ch - 1 ('mix': 0)
 
-    def _file_regions(self, ctx, fid, n_ch, file):
-        """The ended run's regions of `file`; 'each' mode (n_ch >= 1): the merged table of its channels, their peaks to channel_detail."""
+    def _file_regions(self, ctx, fid, n_ch, file, bands=True):
+        """The ended run's regions of `file`; 'each' mode (n_ch >= 1): the merged table of its channels, their peaks to channel_detail.
+        bands=False: the caller asks for the file's bands itself (_file_bands), after it has read every file of the run -- the bands'
+        passes take the run's device buffers, which the peaks of the files behind this one still need."""
         if n_ch < 1:
-            return [(float(s), float(e)) for s, e in ctx.regions(fid)]
-        merged = ctx.regions_union(fid, n_ch) if n_ch > 1 else ctx.regions(fid)
-        self.channel_detail[file] = (n_ch, ctx.region_peaks(fid, n_ch).tolist())
-        return [(float(s), float(e)) for s, e in merged]
+            regions = [(float(s), float(e)) for s, e in ctx.regions(fid)]
+        else:
+            merged = ctx.regions_union(fid, n_ch) if n_ch > 1 else ctx.regions(fid)
+            self.channel_detail[file] = (n_ch, ctx.region_peaks(fid, n_ch).tolist())
+            regions = [(float(s), float(e)) for s, e in merged]
+        if bands and region_bands_enabled():
+            self._file_bands(ctx, fid, n_ch, file, regions)
+        return regions
+
+    def _file_bands(self, ctx, fid, n_ch, file, regions):
+        """settings.hip_region_bands: the regions' bands to band_detail -- on the context the file's detection ended on (the fp32 one
+        when f16x2 refused the file).  SS_ERR_RANGE from the spec head's own passes: a warning, no bands for this file, the regions
+        stand."""
+        self.band_detail.pop(file, None)
+        n_sig = max(n_ch, 1)
+        try:
+            bands = ctx.region_bands(fid, regions, n_sig)
+        except _native.NativeError as e:
+            if e.code != _native.SS_ERR_RANGE:
+                raise
+            logging.warning("%s: no region bands (%s)", file, e)
+            return
+        self.band_detail[file] = (n_ch, np.asarray(bands).reshape(len(regions), n_sig))
 
     def file_begin(self, file, handle=None, break_duration=0.5, which=0, ctx=None):
         """Enqueue everything for `file` -> token for file_poll / file_end.  No other file may be in flight on the same context
@@ -298,8 +322,15 @@ class NNDetector():
                 return None
             if not ids:
                 return {}
-            if each:                                                   # the channels of a file are consecutive files of the context
-                return {f: self._file_regions(ctx, fid, n_ch, f) for f, (fid, n_ch) in zip(files, ids)}
+            want_bands = region_bands_enabled()
+            if each or want_bands:                                     # the channels of a file are consecutive files of the context
+                ids = [(fid, n_ch if each else 0) for fid, n_ch in ids]
+                # every file's regions and peaks first: the first bands call hands the run's device buffers to its passes
+                out = {f: self._file_regions(ctx, fid, n_ch, f, bands=False) for f, (fid, n_ch) in zip(files, ids)}
+                if want_bands:
+                    for f, (fid, n_ch) in zip(files, ids):
+                        self._file_bands(ctx, fid, n_ch, f, out[f])
+                return out
             ids = [fid for fid, _ in ids]
             counts, reg = ctx.regions_batch(ids[0], len(ids))          # ids are consecutive after the reset above
             out, at = {}, 0

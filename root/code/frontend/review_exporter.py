@@ -98,6 +98,38 @@ def _optional(df, col):
     return df[col] if col in df.columns else pd.Series([""] * len(df))
 
 
+def _band_boxes(bands) -> dict:
+    """{(ID, file_name): (low_hz, high_hz)} from the region bands of a detection run: a DataFrame with the columns ID, low_hz, high_hz
+    and, as a rule, file_name (the `<detections stem>_bands.csv` side file; several rows per ID in the per-channel mode) or a mapping
+    from ID or (ID, file_name) to (low, high) or to a list of such pairs.  A key's box is the lowest low and the highest high over its
+    entries that have an estimate (both finite).  An entry with a file name serves rows of that recording only -- a manual row whose
+    ID a later detection job has handed out again does not take that detection's box --; one without (file_name None) any row of its ID."""
+    if bands is None:
+        return {}
+    if isinstance(bands, pd.DataFrame):
+        _need(bands, ("ID", "low_hz", "high_hz"), "RavenTxtTransform(bands=)")
+        names = bands["file_name"] if "file_name" in bands.columns else [None] * len(bands)
+        entries = zip(bands["ID"], names, pd.to_numeric(bands["low_hz"], errors="coerce"), pd.to_numeric(bands["high_hz"], errors="coerce"))
+    else:
+        entries = []
+        for key, v in bands.items():
+            key, name = key if isinstance(key, tuple) else (key, None)
+            pairs = [v] if len(v) == 2 and not hasattr(v[0], "__len__") else v
+            entries += [(key, name, lo, hi) for lo, hi in pairs]
+    boxes = {}
+    for key, name, lo, hi in entries:
+        try:
+            key, lo, hi = int(key), float(lo), float(hi)
+        except (TypeError, ValueError):
+            continue
+        if lo != lo or hi != hi or abs(lo) == float("inf") or abs(hi) == float("inf"):
+            continue
+        key = (key, None if name is None or name != name else str(name))
+        old = boxes.get(key)
+        boxes[key] = (lo, hi) if old is None else (min(old[0], lo), max(old[1], hi))
+    return boxes
+
+
 class AudacityTxtTransform(Transform):
     """`<base_dir>/Audacity Outputs/<project_name>/<wav stem>.txt`: one label track per recording,
     tab-separated `start  end  comment`, no header (reference :129-215)."""
@@ -159,13 +191,15 @@ class RavenTxtTransform(Transform):
     """`<base_dir>/Raven Outputs/<project_name>/<project_name>_listfile.txt` (recordings in order of
     first appearance) and `<project_name>.txt` (tab-delimited selection table whose times run on
     through the list: each recording is offset by the summed length of those before it)
-    (reference :341-481)."""
+    (reference :341-481).  bands (not in the reference; see _band_boxes): rows whose ID and file name have a band estimate get their own
+    `Low Freq (Hz)` / `High Freq (Hz)`, rounded to integers; every other row -- a manual one, one without an estimate, any row of
+    a table without an ID column -- keeps low_freq / high_freq.  bands=None: the reference's bytes."""
 
     name = "raven"
     extension = ".txt"
 
     def __call__(self, df, *, base_dir, project_name, precision: int = 6, annotation_label: str = "Human",
-                 low_freq: int = 0, high_freq: int = 8000, **kwargs):
+                 low_freq: int = 0, high_freq: int = 8000, bands=None, **kwargs):
         folder = Path(base_dir) / "Raven Outputs" / project_name
         folder.mkdir(parents=True, exist_ok=True)
         _need(df, ("file_path", "file_name", "start_time", "end_time"), "RavenTxtTransform")
@@ -205,6 +239,12 @@ class RavenTxtTransform(Transform):
             "user_comment": _optional(df, "user_comment"),
             "review_datetime": _optional(df, "review_datetime"),
         })
+        boxes = _band_boxes(bands)
+        if boxes and "ID" in df.columns and len(df):
+            ids = pd.to_numeric(df["ID"], errors="coerce")
+            box = [(boxes.get((int(i), str(f))) or boxes.get((int(i), None))) if i == i else None for i, f in zip(ids, df["file_name"])]
+            table["Low Freq (Hz)"] = pd.Series([low_freq if b is None else int(round(b[0])) for b in box], index=df.index)
+            table["High Freq (Hz)"] = pd.Series([high_freq if b is None else int(round(b[1])) for b in box], index=df.index)
         if "confidence" in df.columns:
             table["confidence"] = df["confidence"]
         table.to_csv(folder / f"{project_name}.txt", sep="\t", index=False, lineterminator="\n")

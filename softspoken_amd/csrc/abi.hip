@@ -305,6 +305,49 @@ extern "C" int ss_separate_pcm_channels(ss_ctx* c, const void* pcm, int format, 
 }
 
 // ------------------------------------------------------------------------------------------------------
+// region bands (separate.hip): each region's frequency extent from the spec head's speech map
+// ------------------------------------------------------------------------------------------------------
+extern "C" int ss_band_edges(double* hz130) {
+    if (!hz130) return fail(nullptr, SS_ERR_ARG, "ss_band_edges: null output");
+    band_edges(hz130);
+    return SS_OK;
+}
+
+extern "C" int ss_region_bins(double start, double end, int64_t covered_bins, int64_t* first, int64_t* count) {
+    if (!first || !count || covered_bins < 0 || !std::isfinite(start) || !std::isfinite(end) || end < start)
+        return fail(nullptr, SS_ERR_ARG, "ss_region_bins: bad argument");
+    region_bins(start, end, 0, covered_bins, *first, *count);
+    return SS_OK;
+}
+
+extern "C" int ss_region_bands(ss_ctx* c, int first_file, int n_channels, const ss_region* regions, int64_t n, const ss_band_params* params,
+                               ss_region_band* out, double* profile) {
+    std::string err;
+    if (int rc = check_band_args(regions, n, params, err)) return fail(c, rc, "ss_region_bands: " + err);
+    if (n > 0 && !out) return fail(c, SS_ERR_ARG, "ss_region_bands: null output");
+    int rc = check_model_idle(c);
+    if (rc) return rc;
+    if (n_channels < 1 || first_file < 0 || (int64_t)first_file + n_channels > (int64_t)c->files.size())
+        return fail(c, SS_ERR_ARG, "ss_region_bands: bad file range");
+    hipSetDevice(c->device);
+    return region_bands(c, nullptr, first_file, n_channels, 0, 0, regions, n, params, out, profile);
+}
+
+extern "C" int ss_region_bands_from_maps(ss_ctx* c, const float* maps, int n_signals, int64_t first_bin, int64_t n_bins, const ss_region* regions,
+                                         int64_t n, const ss_band_params* params, ss_region_band* out, double* profile) {
+    std::string err;
+    if (int rc = check_band_args(regions, n, params, err)) return fail(c, rc, "ss_region_bands_from_maps: " + err);
+    if (n > 0 && !out) return fail(c, SS_ERR_ARG, "ss_region_bands_from_maps: null output");
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    if (!maps || n_signals < 1 || n_signals > 1024 || first_bin < 0 || n_bins < 1 || n_bins > ((int64_t)1 << 22) ||
+        first_bin > ((int64_t)1 << 40))
+        return fail(c, SS_ERR_ARG, "ss_region_bands_from_maps: bad maps");
+    hipSetDevice(c->device);
+    return region_bands(c, maps, 0, n_signals, first_bin, n_bins, regions, n, params, out, profile);
+}
+
+// ------------------------------------------------------------------------------------------------------
 // review-screen spectrogram: voice_activity.py:148-154
 // ------------------------------------------------------------------------------------------------------
 extern "C" int64_t ss_stft512_frames(int64_t n) { return n < 0 ? -1 : 1 + n / 256; }
@@ -896,6 +939,11 @@ extern "C" int ss_debug_fail_workspace_alloc(ss_ctx* c, int nth) {
 extern "C" int ss_debug_set_separation_budget(ss_ctx* c, int64_t frames) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
     c->sep_budget = frames < 0 ? 0 : frames;
+    return SS_OK;
+}
+extern "C" int ss_debug_set_bands_budget(ss_ctx* c, int64_t bins) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    c->bands_budget = bins < 0 ? 0 : bins;
     return SS_OK;
 }
 extern "C" int ss_debug_activation(ss_ctx* c, const char* name, int plane, int64_t first_window, int64_t n_windows, void* out, int64_t out_bytes,

@@ -172,6 +172,7 @@ struct ss_ctx {
     int* d_range_flag = nullptr; int* h_range_flag = nullptr;    // f16x2: set by the conv kernels when a value does not fit an f16
     int fail_alloc_after = -1;                            // dev build's test hook (ss_debug_fail_workspace_alloc): the n-th workspace allocation from now fails
     int64_t sep_budget = 0;                               // dev build's test hook (ss_debug_set_separation_budget): frames per chunk of ss_separate_pcm; 0: from kSepFrameBytes
+    int64_t bands_budget = 0;                             // dev build's test hook (ss_debug_set_bands_budget): bins per piece of ss_region_bands; 0: kBandsPieceBins
     bool split_range_ok = true;                           // f16x2: cleared while packing when a folded weight has no f16 representation
     // f16x2: power-of-two channel exponents of every activation tensor, by Act, then of the features and of conv_flatten's partial sums
     // (weights.hip; all zero in the other modes and under SOFTSPOKEN_NORM=0): a tensor T holds 2^act_exp[T][c] x the value of channel c
@@ -253,6 +254,7 @@ int ensure(ss_ctx* c, T** p, size_t* cap, size_t need_elems, bool keep = false) 
 // weights.hip
 int build_tables(ss_ctx* c, const Blob& bl);
 int build_model(ss_ctx* c, const Blob& bl);
+const float* mel_edges_hz();                              // the filterbank's 130 band edges (the front-end's table)
 // engine.hip
 int ensure_workspace(ss_ctx* c, int n);                  // the main workspace holds >= n windows, or an error
 void free_workspace(ss_ctx* c);                           // both workspaces
@@ -290,6 +292,13 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
 int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                           int64_t n_regions, const ss_separation_params* params, int16_t* out);
 void free_separation(ss_ctx* c);
+// separate.hip, region bands (include/softspoken.h "region bands")
+int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err);
+void band_edges(double* hz130);
+void region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count);   // rule 1, clamped to [lo, hi)
+// maps == nullptr: the spec head on files fid .. fid + nsig - 1; otherwise the caller's maps of bins first_bin .. first_bin + n_bins - 1
+int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_bin, int64_t n_bins, const ss_region* regions, int64_t n,
+                 const ss_band_params* params, ss_region_band* out, double* profile);
 // host.hip
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
 bool step_ok(double step_s);                              // a window step ss_set_window_step accepts

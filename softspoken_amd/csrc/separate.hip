@@ -30,6 +30,9 @@ struct SepSeg { int64_t a, b, s0, s1, k0, rec0, out0; };                        
                                                                                   // frames k0.. in records rec0.., first output slot out0
 struct SepBand { int32_t m0, m1; float w0, w1; };                                // STFT bin -> two mel bands and weights (m0 < 0: >= 8 kHz)
 
+struct BandSeg { int32_t cb0, n, out, pad; };         // (region, tile): compact bins cb0 .. cb0 + n - 1 of the piece's maps -> tile sum `out`
+struct BandRegion { int32_t seg0, nseg, n_bins, pad; };   // a region's tile sums seg0 .. seg0 + nseg - 1 (ascending tiles), its bins
+
 struct SepTables { int N = 0; float2* tw = nullptr; float* win = nullptr; SepBand* band = nullptr; };
 
 struct SepState {
@@ -43,6 +46,13 @@ struct SepState {
     SepFrame* d_frames = nullptr; size_t frames_cap = 0;
     SepSeg* d_segs = nullptr; size_t segs_cap = 0;
     float2* d_fout = nullptr; size_t fout_cap = 0;
+    // region bands
+    BandSeg* d_bseg = nullptr; size_t bseg_cap = 0;
+    BandRegion* d_breg = nullptr; size_t breg_cap = 0;
+    double* d_bpart = nullptr; size_t bpart_cap = 0;
+    ss_region_band* d_bout = nullptr; size_t bout_cap = 0;
+    double* d_bprof = nullptr; size_t bprof_cap = 0;
+    double* d_hz = nullptr;
 };
 
 // =========================================================================================================
@@ -374,7 +384,8 @@ void free_separation(ss_ctx* c) {
     if (!c->sep) return;
     SepState& s = *c->sep;
     for (auto& kv : s.tables) { hipFree(kv.second.tw); hipFree(kv.second.win); hipFree(kv.second.band); }
-    void* p[] = {s.d_cbin, s.d_slot, s.d_sum, s.d_count, s.d_map, s.d_gain, s.d_frames, s.d_segs, s.d_fout};
+    void* p[] = {s.d_cbin, s.d_slot, s.d_sum, s.d_count, s.d_map, s.d_gain, s.d_frames, s.d_segs, s.d_fout,
+                 s.d_bseg, s.d_breg, s.d_bpart, s.d_bout, s.d_bprof, s.d_hz};
     for (void* q : p) if (q) hipFree(q);
     delete c->sep;
     c->sep = nullptr;
@@ -657,6 +668,260 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
 int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                           int64_t n_regions, const ss_separation_params* params, int16_t* out) {
     return separate_run(c, ch > 1, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
+// =========================================================================================================
+// region bands (include/softspoken.h "region bands"): the maps of step 1 reduced on the device to each region's band bounds
+//
+//   host   rule 1 per region -> the disjoint union of the regions' bin ranges (sep_run_maps' bin_ranges), cut at absolute tile
+//          boundaries into pieces of at most kBandsPieceBins bins -> segments (region, tile) over the piece that holds the tile
+//   per piece   sep_run_maps -> d_map [nsig][2][ncb][128];  band_profile_kernel: one tile sum [256] per (segment, signal)
+//   at the end  band_bounds_kernel: per (region, signal) the tile sums added in ascending tile order -> E, C, the bounds
+// =========================================================================================================
+static constexpr int64_t kBandsPieceBins = 16384;      // most bins of one sep_run_maps round: 48 MB of sums and maps per signal
+
+// P(y) = expm1(min(y^2 ln 10, 600)); NaN -> 0
+__device__ __forceinline__ double band_power(float yf) {
+#pragma clang fp contract(off)
+    if (yf != yf) return 0.0;
+    const double y = (double)yf;
+    const double a = y * y * 2.302585092994045684;
+    return expm1(a < 600.0 ? a : 600.0);
+}
+
+// Block = one segment of one signal (blockIdx.y), thread = (spec channel, band): the sequential ascending sum of P over the segment's
+// bins (at most 64: one tile's share of a region).  A bin row of a channel is 128 consecutive floats: the loads of a wave are 256 B
+// runs.  part [nsig][nseg_total][256].
+__global__ __launch_bounds__(256) void band_profile_kernel(const float* __restrict__ map, int ncb, const BandSeg* __restrict__ segs,
+                                                           int nseg_total, double* __restrict__ part) {
+    const BandSeg sg = segs[blockIdx.x];
+    const int sig = blockIdx.y, ch = threadIdx.x >> 7, m = threadIdx.x & 127;
+    const float* p = map + (((size_t)sig * 2 + ch) * ncb + sg.cb0) * 128 + m;
+    double s = 0.0;
+    for (int i = 0; i < sg.n; ++i) s += band_power(p[(size_t)i * 128]);
+    part[((size_t)sig * nseg_total + sg.out) * 256 + threadIdx.x] = s;
+}
+
+// Block = one region of one signal (blockIdx.y).  Every thread adds its (channel, band)'s tile sums in ascending tile order; lane 0
+// forms C over the speech channel and lane 128 T_env, both sequentially (that fixes the rounding); the two quantile predicates and
+// the argmax are evaluated by 128 lanes and min-reduced in LDS.  out [n][nsig], profile (nullable) [n][nsig][2][128].
+__global__ __launch_bounds__(256) void band_bounds_kernel(const double* __restrict__ part, int nseg_total, const BandRegion* __restrict__ regs,
+                                                          int speech_ch, double q_low, double q_high, const double* __restrict__ hz,
+                                                          ss_region_band* __restrict__ out, double* __restrict__ profile) {
+#pragma clang fp contract(off)
+    __shared__ double E[256];
+    __shared__ double Cs[128];
+    __shared__ double tot[2], emax;
+    __shared__ int idx[3];
+    const int r = blockIdx.x, sig = blockIdx.y, nsig = gridDim.y, t = threadIdx.x;
+    const BandRegion rg = regs[r];
+    const double* p = part + ((size_t)sig * nseg_total + rg.seg0) * 256 + t;
+    double e = 0.0;
+    for (int k = 0; k < rg.nseg; ++k) e += p[(size_t)k * 256];
+    if (profile) profile[((size_t)r * nsig + sig) * 256 + t] = e;
+    E[t] = e;
+    if (t < 3) idx[t] = 128;
+    __syncthreads();
+    if (t == 0) {
+        const double* Es = E + speech_ch * 128;
+        double c = 0.0, mx = 0.0;
+        for (int m = 0; m < 128; ++m) { c += Es[m]; Cs[m] = c; mx = Es[m] > mx ? Es[m] : mx; }
+        tot[0] = c; emax = mx;
+    } else if (t == 128) {
+        const double* Ee = E + (1 - speech_ch) * 128;
+        double c = 0.0;
+        for (int m = 0; m < 128; ++m) c += Ee[m];
+        tot[1] = c;
+    }
+    __syncthreads();
+    const double T = tot[0];
+    if (t < 128) {
+        if (Cs[t] >= q_low * T) atomicMin(&idx[0], t);
+        if (Cs[t] >= q_high * T) atomicMin(&idx[1], t);
+        if (E[speech_ch * 128 + t] == emax) atomicMin(&idx[2], t);
+    }
+    __syncthreads();
+    if (t == 0) {
+        ss_region_band o;
+        o.n_bins = rg.n_bins;
+        if (rg.n_bins == 0 || !(T > 0.0)) {
+            o.low_hz = o.high_hz = o.peak_hz = o.speech_share = __builtin_nan("");
+            o.band_low = o.band_high = o.band_peak = -1;
+        } else {
+            o.band_low = idx[0]; o.band_high = idx[1]; o.band_peak = idx[2];
+            o.low_hz = hz[idx[0]]; o.high_hz = hz[idx[1] + 2]; o.peak_hz = hz[idx[2] + 1];
+            o.speech_share = T / (T + tot[1]);
+        }
+        out[(size_t)r * nsig + sig] = o;
+    }
+}
+
+// the front-end's own table of band edges (weights.hip), not mel_points() above: the two differ by a float32 ulp at 19 edges, and a
+// band's reported frequency is the edge its features were computed with
+void band_edges(double* hz130) {
+    const float* f = mel_edges_hz();
+    for (int i = 0; i < 130; ++i) hz130[i] = (double)f[i];
+}
+
+// rule 1: the bins whose centres lie in [start, end), clamped to the bins [lo, hi)
+static int64_t band_edge_bin(double x, int64_t lo, int64_t hi) {
+#pragma clang fp contract(off)
+    const double s = (x + 3.0) * 256.0;
+    const double q = s / 3.0;
+    const double v = std::ceil(q - 0.5);
+    if (!(v > (double)lo)) return lo;
+    if (v >= (double)hi) return hi;
+    return (int64_t)v;
+}
+
+void region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count) {
+    first = band_edge_bin(start, lo, hi);
+    count = std::max<int64_t>(0, band_edge_bin(end, lo, hi) - first);
+}
+
+int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err) {
+    if (n < 0 || (n > 0 && !regions)) { err = "bad region table"; return SS_ERR_ARG; }
+    if (n > (int64_t)1 << 24) { err = "too many regions"; return SS_ERR_ARG; }
+    if (p) {
+        if (!(p->q_low > 0.0 && p->q_low < p->q_high && p->q_high <= 1.0)) { err = "need 0 < q_low < q_high <= 1"; return SS_ERR_ARG; }
+        if (p->speech_channel != 0 && p->speech_channel != 1) { err = "speech_channel must be 0 or 1"; return SS_ERR_ARG; }
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(regions[i].start) || !std::isfinite(regions[i].end) || regions[i].end < regions[i].start) {
+            err = "region " + std::to_string(i) + " is not finite or ends before it starts";
+            return SS_ERR_ARG;
+        }
+    return SS_OK;
+}
+
+int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_bin, int64_t n_bins, const ss_region* regions, int64_t n,
+                 const ss_band_params* params, ss_region_band* out, double* profile) {
+    if (n == 0) return SS_OK;
+    const ss_band_params prm = params ? *params : ss_band_params{0.05, 0.95, 1, 0};
+    SepState& st = sep_state(c);
+    int64_t W = 0, lo = first_bin, hi = first_bin + n_bins;
+    if (!maps) {
+        const FileRec& f = c->files[fid];
+        for (int s = 1; s < nsig; ++s)
+            if (c->files[fid + s].n_padded != f.n_padded || c->files[fid + s].duration != f.duration)
+                return fail(c, SS_ERR_ARG, "ss_region_bands: the files are not the channels of one recording");
+        file_geometry(f.duration, f.n_padded, W, hi);
+        lo = 0;
+    }
+    // rule 1, then the disjoint union of the non-empty ranges
+    std::vector<std::pair<int64_t, int64_t>> rb((size_t)n), un;       // [first, end) per region; union as inclusive pairs
+    for (int64_t i = 0; i < n; ++i) {
+        int64_t b0, cnt;
+        region_bins(regions[i].start, regions[i].end, lo, hi, b0, cnt);
+        rb[i] = {b0, b0 + cnt};
+        if (cnt > 0) un.emplace_back(b0, b0 + cnt - 1);
+    }
+    std::sort(un.begin(), un.end());
+    size_t nu = 0;
+    for (size_t i = 0; i < un.size(); ++i) {
+        if (nu && un[i].first <= un[nu - 1].second + 1) un[nu - 1].second = std::max(un[nu - 1].second, un[i].second);
+        else un[nu++] = un[i];
+    }
+    un.resize(nu);
+    // tile chunks of the union, gathered into pieces.  Caller's maps: one piece, compact bin = bin - first_bin.
+    struct Chunk { int64_t b0, b1; int piece; int64_t cb0; };       // bins [b0, b1) of one tile, at compact bin cb0 of its piece
+    struct Piece { std::vector<std::pair<int64_t, int64_t>> br; int64_t ncb = 0; size_t seg0 = 0, nseg = 0; };
+    std::vector<Chunk> chunks;
+    std::vector<Piece> pieces;
+    if (maps) {
+        pieces.emplace_back();
+        pieces[0].ncb = n_bins;
+        chunks.push_back(Chunk{lo, hi, 0, 0});
+    } else {
+        int64_t budget = kBandsPieceBins;
+#ifdef SS_DEVBUILD      // ss_debug_set_bands_budget: the tests move the cuts through a short recording
+        if (c->bands_budget > 0) budget = std::max<int64_t>(64, c->bands_budget);
+#endif
+        for (const auto& u : un)
+            for (int64_t b = u.first; b <= u.second;) {
+                const int64_t e = std::min(u.second + 1, ((b >> 6) + 1) << 6);
+                if (pieces.empty() || pieces.back().ncb + (e - b) > budget) pieces.emplace_back();
+                Piece& pc = pieces.back();
+                chunks.push_back(Chunk{b, e, (int)pieces.size() - 1, pc.ncb});
+                if (!pc.br.empty() && pc.br.back().second + 1 == b) pc.br.back().second = e - 1;
+                else pc.br.emplace_back(b, e - 1);
+                pc.ncb += e - b;
+                b = e;
+            }
+    }
+    // segments: region by region, ascending tiles; every one lies inside one chunk's piece
+    std::vector<BandRegion> regs((size_t)n);
+    std::vector<std::vector<BandSeg>> psegs(pieces.size());
+    int64_t nseg_total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        regs[i] = BandRegion{(int32_t)nseg_total, 0, (int32_t)(rb[i].second - rb[i].first), 0};
+        for (int64_t b = rb[i].first; b < rb[i].second;) {
+            const int64_t e = std::min(rb[i].second, ((b >> 6) + 1) << 6);
+            size_t k = 0;
+            if (!maps) {
+                auto it = std::upper_bound(chunks.begin(), chunks.end(), b, [](int64_t v, const Chunk& ck) { return v < ck.b0; });
+                k = (size_t)(it - chunks.begin()) - 1;
+            }
+            const Chunk& ck = chunks[k];
+            psegs[ck.piece].push_back(BandSeg{(int32_t)(ck.cb0 + (b - ck.b0)), (int32_t)(e - b), (int32_t)nseg_total, 0});
+            ++nseg_total; ++regs[i].nseg;
+            b = e;
+        }
+        if (nseg_total > (int64_t)INT32_MAX / 2) return fail(c, SS_ERR_ARG, "ss_region_bands: too many region tiles");
+    }
+    std::vector<BandSeg> segs;
+    segs.reserve((size_t)nseg_total);
+    for (size_t p = 0; p < pieces.size(); ++p) {
+        pieces[p].seg0 = segs.size(); pieces[p].nseg = psegs[p].size();
+        segs.insert(segs.end(), psegs[p].begin(), psegs[p].end());
+    }
+    const size_t ns = (size_t)nsig;
+    int rc;
+    if ((rc = ensure(c, &st.d_bseg, &st.bseg_cap, std::max<size_t>(segs.size(), 1)))) return rc;
+    if ((rc = ensure(c, &st.d_breg, &st.breg_cap, (size_t)n))) return rc;
+    if ((rc = ensure(c, &st.d_bpart, &st.bpart_cap, std::max<size_t>((size_t)nseg_total * ns * 256, 1)))) return rc;
+    if ((rc = ensure(c, &st.d_bout, &st.bout_cap, (size_t)n * ns))) return rc;
+    if (profile && (rc = ensure(c, &st.d_bprof, &st.bprof_cap, (size_t)n * ns * 256))) return rc;
+    if (!st.d_hz) {
+        double f[130];
+        band_edges(f);
+        HIPCHK(c, hipMalloc((void**)&st.d_hz, sizeof f));
+        HIPCHK(c, hipMemcpy(st.d_hz, f, sizeof f, hipMemcpyHostToDevice));
+    }
+    if (!segs.empty()) HIPCHK(c, hipMemcpy(st.d_bseg, segs.data(), segs.size() * sizeof(BandSeg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(st.d_breg, regs.data(), (size_t)n * sizeof(BandRegion), hipMemcpyHostToDevice));
+    for (const Piece& pc : pieces) {
+        if (!pc.nseg) continue;
+        int64_t ncb = pc.ncb;
+        if (maps) {
+            if ((rc = ensure(c, &st.d_map, &st.map_cap, ns * (size_t)n_bins * 256))) return rc;
+            HIPCHK(c, hipMemcpyAsync(st.d_map, maps, ns * (size_t)n_bins * 256 * 4, hipMemcpyHostToDevice, c->stream));
+        } else {
+            std::vector<std::pair<int64_t, int64_t>> wr;
+            for (const auto& b : pc.br) {
+                int64_t w0, w1;
+                covering_windows(b.first, b.second, W, w0, w1);
+                if (!wr.empty() && w0 <= wr.back().second + 1) wr.back().second = std::max(wr.back().second, w1);
+                else wr.emplace_back(w0, w1);
+            }
+            if ((rc = sep_run_maps(c, fid, nsig, W, pc.br, wr, nullptr, ncb))) return rc;
+            if (ncb != pc.ncb) return fail(c, SS_ERR_HIP, "ss_region_bands: the maps do not hold the piece's bins");
+        }
+        ScopedLaunch sl(c, c->stream, "band_profile_kernel", 0.0, (double)pc.nseg * ns * (64.0 * 256 * 4 + 256 * 8));
+        hipLaunchKernelGGL(band_profile_kernel, dim3((unsigned)pc.nseg, (unsigned)nsig), dim3(256), 0, c->stream, st.d_map, (int)ncb,
+                           st.d_bseg + pc.seg0, (int)nseg_total, st.d_bpart);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        ScopedLaunch sl(c, c->stream, "band_bounds_kernel", 0.0, (double)nseg_total * ns * 256 * 8 + (double)n * ns * (48 + (profile ? 2048 : 0)));
+        hipLaunchKernelGGL(band_bounds_kernel, dim3((unsigned)n, (unsigned)nsig), dim3(256), 0, c->stream, st.d_bpart, (int)nseg_total, st.d_breg,
+                           prm.speech_channel, prm.q_low, prm.q_high, st.d_hz, st.d_bout, profile ? st.d_bprof : nullptr);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(out, st.d_bout, (size_t)n * ns * sizeof(ss_region_band), hipMemcpyDeviceToHost, c->stream));
+    if (profile) HIPCHK(c, hipMemcpyAsync(profile, st.d_bprof, (size_t)n * ns * 256 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
 }
 
 }  // namespace ss

@@ -423,6 +423,8 @@ static const float kMelEdgesHz[130] = {
     0x1.cb2112p+12f, 0x1.d50ca8p+12f, 0x1.df2a62p+12f, 0x1.e97b1ep+12f, 0x1.f3fffcp+12f,
 };
 
+const float* mel_edges_hz() { return kMelEdgesHz; }
+
 int build_tables(ss_ctx* c, const Blob& bl) {
     std::string err;
     const double PI = 3.14159265358979323846;

@@ -84,6 +84,19 @@ class SeparationPlanInfo(C.Structure):
                 ("n_ranges", C.c_int64), ("cap_ranges", C.c_int64), ("ranges", C.POINTER(SeparationRange))]
 
 
+class BandParams(C.Structure):
+    _fields_ = [("q_low", C.c_double), ("q_high", C.c_double), ("speech_channel", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RegionBand(C.Structure):
+    _fields_ = [("low_hz", C.c_double), ("high_hz", C.c_double), ("peak_hz", C.c_double), ("speech_share", C.c_double),
+                ("band_low", C.c_int32), ("band_high", C.c_int32), ("band_peak", C.c_int32), ("n_bins", C.c_int32)]
+
+
+# struct ss_region_band as a numpy record (48 bytes)
+REGION_BAND_DTYPE = np.dtype([("low_hz", "<f8"), ("high_hz", "<f8"), ("peak_hz", "<f8"), ("speech_share", "<f8"),
+                              ("band_low", "<i4"), ("band_high", "<i4"), ("band_peak", "<i4"), ("n_bins", "<i4")])
+
 ABOVE_FMAX = {"mute": 0, "keep": 1}      # SS_ABOVE_FMAX_MUTE / _KEEP
 
 
@@ -173,12 +186,17 @@ _SIGS = {
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
     "ss_separate_pcm_channels": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
+    "ss_band_edges": (C.c_int, [_P]),
+    "ss_region_bins": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ss_region_bands": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(BandParams), _P, _P]),
+    "ss_region_bands_from_maps": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(BandParams), _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 # exported by the development build only (libsoftspoken_hip_dev.so, loaded through SOFTSPOKEN_LIB by tests and tools)
 _DEV_SIGS = {
     "ss_debug_fail_workspace_alloc": (C.c_int, [_P, C.c_int]),
     "ss_debug_set_separation_budget": (C.c_int, [_P, C.c_int64]),
+    "ss_debug_set_bands_budget": (C.c_int, [_P, C.c_int64]),
     "ss_debug_activation": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 
@@ -360,6 +378,35 @@ def separation_plan(sr: int, frames: int, regions, **params) -> dict:
     return out
 
 
+def band_edges() -> np.ndarray:
+    """The 130 HTK mel points f of the region bands (ss_band_edges, host only): band m's triangle spans f[m] .. f[m + 2] Hz."""
+    out = np.empty(130, dtype=np.float64)
+    _check(lib().ss_band_edges(_ptr(out)))
+    return out
+
+
+def region_bins(start: float, end: float, covered_bins: int) -> tuple[int, int]:
+    """(first bin, bins) of the region [start, end) s in a file with covered_bins covered bins (ss_region_bins, host only): the bins
+    whose centres (j + 0.5) 3 / 256 - 3 s lie inside."""
+    first, count = C.c_int64(0), C.c_int64(0)
+    _check(lib().ss_region_bins(float(start), float(end), int(covered_bins), C.byref(first), C.byref(count)))
+    return first.value, count.value
+
+
+def band_params(q_low: float = 0.05, q_high: float = 0.95, speech_channel: int = 1) -> BandParams:
+    return BandParams(float(q_low), float(q_high), int(speech_channel), 0)
+
+
+def _band_call(fn, ctx, head, regions, n_sig, q_low, q_high, speech_channel, profile):
+    """The tail shared by ss_region_bands and ss_region_bands_from_maps: (bands [n, n_sig] records, profile [n, n_sig, 2, 128] or None)."""
+    n = len(regions)
+    p = band_params(q_low, q_high, speech_channel)
+    out = np.zeros((n, n_sig), dtype=REGION_BAND_DTYPE)
+    prof = np.zeros((n, n_sig, 2, 128), dtype=np.float64) if profile else None
+    _check(fn(ctx, *head, _regions(regions), n, C.byref(p), _ptr(out) if n else None, _ptr(prof) if profile and n else None), ctx)
+    return out, prof
+
+
 # ---- context --------------------------------------------------------------------------------------
 class Context:
     """One detector context on one GPU (not thread-safe; one per device)."""
@@ -479,6 +526,38 @@ class Context:
         out = np.empty((2, int(n_bins), 128), dtype=np.float32)
         self._ck(lib().ss_separation_maps(self._h, int(fid), int(first_bin), int(n_bins), _ptr(out)))
         return out
+
+    def region_bands(self, fid: int, regions, n_channels: int = 1, q_low: float = .05, q_high: float = .95, speech_channel: int = 1,
+                     profile: bool = False):
+        """Each region's frequency extent from the spec head's speech map (ss_region_bands): a REGION_BAND_DTYPE array [n] (n_channels
+        == 1) or [n, n_channels] (the files fid .. fid + n_channels - 1 of add_pcm_channels); low_hz / high_hz / peak_hz are NaN and the
+        band indices -1 where there is no estimate.  profile=True: -> (bands, E) with E float64 [n, (n_channels,) 2, 128]."""
+        out, prof = _band_call(lib().ss_region_bands, self._h, (int(fid), int(n_channels)), regions, int(n_channels), q_low, q_high,
+                               speech_channel, profile)
+        if int(n_channels) == 1:
+            out, prof = out[:, 0], (prof[:, 0] if profile else None)
+        return (out, prof) if profile else out
+
+    def region_bands_from_maps(self, maps, first_bin: int, regions, q_low: float = .05, q_high: float = .95, speech_channel: int = 1,
+                               profile: bool = False):
+        """region_bands on maps the caller supplies (ss_region_bands_from_maps): maps float32 [2, n_bins, 128] or [n_signals, 2, n_bins,
+        128] for the bins first_bin .., as separation_maps returns them; the result is shaped as region_bands'."""
+        maps = np.ascontiguousarray(maps, dtype=np.float32)
+        single = maps.ndim == 3
+        if single:
+            maps = maps[None]
+        if maps.ndim != 4 or maps.shape[1] != 2 or maps.shape[3] != 128:
+            raise ValueError("maps must be [2, n_bins, 128] or [n_signals, 2, n_bins, 128]")
+        ns, nb = maps.shape[0], maps.shape[2]
+        out, prof = _band_call(lib().ss_region_bands_from_maps, self._h, (_ptr(maps), ns, int(first_bin), nb), regions, ns, q_low, q_high,
+                               speech_channel, profile)
+        if single:
+            out, prof = out[:, 0], (prof[:, 0] if profile else None)
+        return (out, prof) if profile else out
+
+    def debug_set_bands_budget(self, bins: int):
+        """Development build only: region_bands covers at most `bins` bins per round of passes (floor 64; <= 0: the product's number)."""
+        self._ck(lib().ss_debug_set_bands_budget(self._h, int(bins)))
 
     def stft512_magnitude(self, samples) -> np.ndarray:
         """|STFT| (n_fft = win = 512, hop 256, centred, zero padded) of a mono float32 signal -> float32 [257, 1 + n // 256]."""

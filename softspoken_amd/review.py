@@ -125,9 +125,15 @@ class ReviewTable:
             proj = self.project_manager.current_project
             df.to_csv(proj['review_file'], index=False)
             exporter = review_exporter.ReviewExportManager(df)
+            # region bands of the detection run (<detections stem>_bands.csv, written with SOFTSPOKEN_BANDS=1): Raven's boxes per row
+            extra = {}
+            detections = proj.get('detections_file')
+            side = os.path.splitext(detections)[0] + "_bands.csv" if detections else None
+            if side and os.path.exists(side):
+                extra["bands"] = pd.read_csv(side)
             for tr in (review_exporter.AudacityTxtTransform(), review_exporter.KaleidoscopeCsvTransform(),
                        review_exporter.RavenTxtTransform()):
                 exporter.register_transform(tr)
                 exporter.export(tr.name, dst=".", base_dir=Path(self.project_manager.projects_folder),
-                                project_name=proj["name"])
+                                project_name=proj["name"], **(extra if tr.name == "raven" else {}))
         return df
