@@ -615,6 +615,43 @@ int ss_region_bands(ss_ctx* ctx, int first_file, int n_channels, const ss_region
 int ss_region_bands_from_maps(ss_ctx* ctx, const float* maps, int n_signals, int64_t first_bin, int64_t n_bins, const ss_region* regions,
                               int64_t n, const ss_band_params* params, ss_region_band* out, double* profile);
 
+/* ---- stream bands: each final region's frequency extent as a stream returns it ------------------------------------------------
+ * A stream opened with ss_stream_open_bands returns, with every region ss_stream_regions returns, that region's ss_region_band (and,
+ * with want_profile, its profile), in the same step as the region: no new latency bound.
+ * Equality.  Let R be the concatenation of the regions the stream returned, Bs and Ps of the bands and profiles.  Bs and Ps equal, as
+ * bytes (NaNs by bit pattern), `out` and `profile` of ss_region_bands(ctx', first_file, C, R, n, params, out, profile) after ss_add_pcm
+ * + ss_run of the whole recording on a context ctx' of the same precision; an each-channel stream of C channels is compared with
+ * ss_add_pcm_channels and out[n][C], every channel under the merged table.  This holds for any split into pieces and any cadence of
+ * steps, whichever other streams (of any kind, with or without bands) shared the steps, and across ss_stream_export / ss_stream_import
+ * between contexts of the same precision.  Steps 1 - 4 of "region bands" apply unchanged: rule 1 on the ss_region values the stream
+ * returns; the maps as float64 sums over a bin's covering default-step windows in ascending window order, divided by the count, stored
+ * as float32 (0 for a bin no window covers, which exists only behind the last window of a closed stream); P(y), the cap at 600, NaN
+ * adds 0, tiles by j >> 6; the sequential C, the quantiles, the first argmax, the Hz edges and "no estimate" as they stand.
+ * Everything else the stream returns (regions, averages, peaks, output) is bit for bit what the same stream returns with bands off,
+ * and streams without bands run in passes of their own, which make exactly the launches of a context that never saw a band stream.
+ * State (counted by ss_stream_info.state_bytes), bounded and independent of the stream's and of any region's length.  Per lane (one
+ * lane; one per channel of an each-channel stream): five vectors of 256 doubles (10 KB) -- the sum of the candidate region's completed
+ * tiles, the running sum of its current tile, a snapshot of both taken before the candidate's current last bin (its exclusive end under
+ * rule 1), and the profile of a region that is final but not returned yet --, and the float64 map sums of the bins that a window
+ * already covers but that are not final: 2 KB per bin for at most the 256 bins of a window plus the bins of one step (51.2) and of the
+ * resampler's look-ahead, about 0.6 MB.  break_s adds nothing: a gap is walked through, not held.
+ * Refusals.  SS_ERR_STATE: a context whose window step is not the default 0.6 s (the maps are defined on default-step windows), an
+ * audio-only context, ss_stream_bands on a stream without bands, `profile` on a stream opened without want_profile.  SS_ERR_ARG:
+ * params as in ss_region_bands.  Under SS_FLAG_F16X2 a step whose passes -- the spec head's among them -- set the range flag returns
+ * SS_ERR_RANGE and commits nothing, band state included.
+ * Images.  A stream with bands exports "SSSTRM05" (the content of the older images plus the band parameters, the accumulators and the
+ * carried map sums; a finished stream carries none, its image holds zeros there); every other stream writes the image it always wrote;
+ * ss_stream_import reads all five.  An "SSSTRM05" image that
+ * does not hold together -- a wrong length, a bad lane count or parameters, a step other than the default -- is SS_ERR_ARG. */
+/* The one open call that expresses every combination (erase / with_output as ss_stream_open_channels; each_channel != 0: one lane per
+ * channel; params NULL: the defaults).  The three older open calls keep bands off. */
+int ss_stream_open_bands(ss_ctx* ctx, int format, int sample_rate, int channels, double threshold, double break_s,
+                         const ss_stream_erase* erase, int with_output, int each_channel, const ss_band_params* params, int want_profile,
+                         int* stream_id);
+/* The last step's records out[n][lanes] (and profile, NULL or [n][lanes][2][128]) for the n regions ss_stream_regions returns; both
+ * NULL: *n_out alone.  SS_ERR_CAPACITY when cap_regions < n. */
+int ss_stream_bands(ss_ctx* ctx, int stream_id, ss_region_band* out, double* profile, int64_t cap_regions, int64_t* n_out);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */
 int ss_sync(ss_ctx* ctx);

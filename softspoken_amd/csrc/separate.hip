@@ -17,6 +17,7 @@
 // channels of a complex FFT their own gains.  Steps 2 and 4 and the plan are the mix's.
 #include "engine.h"
 #include "dsp.h"
+#include "bands.h"
 
 #include <algorithm>
 #include <atomic>
@@ -680,15 +681,6 @@ int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch
 // =========================================================================================================
 static constexpr int64_t kBandsPieceBins = 16384;      // most bins of one sep_run_maps round: 48 MB of sums and maps per signal
 
-// P(y) = expm1(min(y^2 ln 10, 600)); NaN -> 0
-__device__ __forceinline__ double band_power(float yf) {
-#pragma clang fp contract(off)
-    if (yf != yf) return 0.0;
-    const double y = (double)yf;
-    const double a = y * y * 2.302585092994045684;
-    return expm1(a < 600.0 ? a : 600.0);
-}
-
 // Block = one segment of one signal (blockIdx.y), thread = (spec channel, band): the sequential ascending sum of P over the segment's
 // bins (at most 64: one tile's share of a region).  A bin row of a channel is 128 consecutive floats: the loads of a wave are 256 B
 // runs.  part [nsig][nseg_total][256].
@@ -702,58 +694,19 @@ __global__ __launch_bounds__(256) void band_profile_kernel(const float* __restri
     part[((size_t)sig * nseg_total + sg.out) * 256 + threadIdx.x] = s;
 }
 
-// Block = one region of one signal (blockIdx.y).  Every thread adds its (channel, band)'s tile sums in ascending tile order; lane 0
-// forms C over the speech channel and lane 128 T_env, both sequentially (that fixes the rounding); the two quantile predicates and
-// the argmax are evaluated by 128 lanes and min-reduced in LDS.  out [n][nsig], profile (nullable) [n][nsig][2][128].
+// Block = one region of one signal (blockIdx.y).  Every thread adds its (channel, band)'s tile sums in ascending tile order; the bounds
+// are band_bounds_block's (bands.h, shared with the streams' kernel).  out [n][nsig], profile (nullable) [n][nsig][2][128].
 __global__ __launch_bounds__(256) void band_bounds_kernel(const double* __restrict__ part, int nseg_total, const BandRegion* __restrict__ regs,
                                                           int speech_ch, double q_low, double q_high, const double* __restrict__ hz,
                                                           ss_region_band* __restrict__ out, double* __restrict__ profile) {
 #pragma clang fp contract(off)
-    __shared__ double E[256];
-    __shared__ double Cs[128];
-    __shared__ double tot[2], emax;
-    __shared__ int idx[3];
     const int r = blockIdx.x, sig = blockIdx.y, nsig = gridDim.y, t = threadIdx.x;
     const BandRegion rg = regs[r];
     const double* p = part + ((size_t)sig * nseg_total + rg.seg0) * 256 + t;
     double e = 0.0;
     for (int k = 0; k < rg.nseg; ++k) e += p[(size_t)k * 256];
     if (profile) profile[((size_t)r * nsig + sig) * 256 + t] = e;
-    E[t] = e;
-    if (t < 3) idx[t] = 128;
-    __syncthreads();
-    if (t == 0) {
-        const double* Es = E + speech_ch * 128;
-        double c = 0.0, mx = 0.0;
-        for (int m = 0; m < 128; ++m) { c += Es[m]; Cs[m] = c; mx = Es[m] > mx ? Es[m] : mx; }
-        tot[0] = c; emax = mx;
-    } else if (t == 128) {
-        const double* Ee = E + (1 - speech_ch) * 128;
-        double c = 0.0;
-        for (int m = 0; m < 128; ++m) c += Ee[m];
-        tot[1] = c;
-    }
-    __syncthreads();
-    const double T = tot[0];
-    if (t < 128) {
-        if (Cs[t] >= q_low * T) atomicMin(&idx[0], t);
-        if (Cs[t] >= q_high * T) atomicMin(&idx[1], t);
-        if (E[speech_ch * 128 + t] == emax) atomicMin(&idx[2], t);
-    }
-    __syncthreads();
-    if (t == 0) {
-        ss_region_band o;
-        o.n_bins = rg.n_bins;
-        if (rg.n_bins == 0 || !(T > 0.0)) {
-            o.low_hz = o.high_hz = o.peak_hz = o.speech_share = __builtin_nan("");
-            o.band_low = o.band_high = o.band_peak = -1;
-        } else {
-            o.band_low = idx[0]; o.band_high = idx[1]; o.band_peak = idx[2];
-            o.low_hz = hz[idx[0]]; o.high_hz = hz[idx[1] + 2]; o.peak_hz = hz[idx[2] + 1];
-            o.speech_share = T / (T + tot[1]);
-        }
-        out[(size_t)r * nsig + sig] = o;
-    }
+    band_bounds_block(e, rg.n_bins, speech_ch, q_low, q_high, hz, out + ((size_t)r * nsig + sig));
 }
 
 // the front-end's own table of band edges (weights.hip), not mel_points() above: the two differ by a float32 ulp at 19 edges, and a

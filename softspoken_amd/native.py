@@ -182,6 +182,9 @@ _SIGS = {
     "ss_stream_open_channels": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.POINTER(C.c_int)]),
     "ss_stream_avg_channel": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_stream_region_peaks": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_open_bands": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.c_int,
+                                       C.POINTER(BandParams), C.c_int, C.POINTER(C.c_int)]),
+    "ss_stream_bands": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
@@ -850,6 +853,30 @@ class Context:
         self._ck(lib().ss_stream_open_channels(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s),
                                                C.byref(e) if erase is not None else None, int(bool(with_output)), C.byref(sid)))
         return sid.value
+
+    def stream_open_bands(self, fmt: int, sr: int, channels: int, threshold: float = 0.1, break_s: float = 0.5, erase=None,
+                          with_output: bool = False, each_channel: bool = False, q_low: float = .05, q_high: float = .95,
+                          speech_channel: int = 1, profile: bool = False) -> int:
+        """A stream that returns with every region its frequency extent (stream_bands after every step; ss_stream_open_bands): any
+        combination of output (erase / with_output as stream_open_channels) and each_channel.  Needs the default window step."""
+        sid = C.c_int(-1)
+        e = _erase(erase)
+        p = band_params(q_low, q_high, speech_channel)
+        self._ck(lib().ss_stream_open_bands(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s),
+                                            C.byref(e) if erase is not None else None, int(bool(with_output)), int(bool(each_channel)),
+                                            C.byref(p), int(bool(profile)), C.byref(sid)))
+        return sid.value
+
+    def stream_bands(self, sid: int, lanes: int = 1, profile: bool = False):
+        """(REGION_BAND_DTYPE records [regions the last step returned, lanes], profiles float64 [regions, lanes, 2, 128] or None)."""
+        n = C.c_int64(0)
+        self._ck(lib().ss_stream_bands(self._h, int(sid), None, None, 0, C.byref(n)))
+        out = np.zeros((n.value, int(lanes)), dtype=REGION_BAND_DTYPE)
+        prof = np.zeros((n.value, int(lanes), 2, 128), dtype=np.float64) if profile else None
+        if n.value or profile:                                # (a profile asked of a stream opened without one is refused, regions or not)
+            pp = (prof if n.value else np.zeros(1)) if profile else None
+            self._ck(lib().ss_stream_bands(self._h, int(sid), _ptr(out) if n.value else None, _ptr(pp) if profile else None, n.value, C.byref(n)))
+        return out, prof
 
     def stream_avg_channel(self, sid: int, channel: int):
         """stream_avg of one channel's lane of an each-channel stream (channel 0 of a mix stream: stream_avg)."""

@@ -21,6 +21,12 @@ native.Context.add_pcm_channels is to add_pcm) and the stream's table is "speech
     ...; regions, merged, bin_idx = det.step()[s]       # merged: per bin the highest of the channels' scores
     s.avg(1); s.peaks()                                 # channel 1's own series; [regions, channels] peaks of the step's regions
 
+bands=True (or a dict of q_low, q_high, speech_channel, profile) gives every region its frequency extent, in the step that returns
+the region and bytes equal to native.Context.region_bands on the whole recording (default window step only):
+
+    s = det.open(PCM_S16, 16000, 1, bands=True)
+    ...; regions, avg, bin_idx, bands = det.step()[s]   # bands: REGION_BAND_DTYPE records [regions, lanes]; also s.bands()
+
 The f16x2 mode reports SS_ERR_RANGE for a step whose passes met a value without an f16 representation (a NaN or Inf sample of a
 float stream), and commits nothing of it.  The rule of the drop-in (SpecUNet_2D.range_refused): the first such step says nothing about
 the checkpoint -- the streams that had windows in it move to an fp32 context of the same weights (ss_stream_export / import) and
@@ -38,7 +44,9 @@ from . import native as _native
 class Stream:
     """One recording of a StreamDetector.  Hashable: step() returns its results keyed by it."""
 
-    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None, channel_mode: str = "mix"):
+    def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None, channel_mode: str = "mix",
+                 band_params=None):
+        self.band_params = band_params                     # None: opened without bands; else dict(q_low, q_high, speech_channel, profile)
         self._det, self._ctx, self._sid = det, ctx, sid
         self.format, self.sample_rate, self.channels = fmt, sr, channels
         self.erase = erase                                 # None: opened without output
@@ -64,6 +72,19 @@ class Stream:
         """float64 [regions the last step returned, channels]: each channel's highest score inside each region (each-channel streams of
         more than one channel)."""
         return self._ctx.stream_region_peaks(self._sid, self.channels)
+
+    @property
+    def lanes(self) -> int:
+        return self.channels if self.channel_mode == "each" else 1
+
+    def bands(self) -> np.ndarray:
+        """REGION_BAND_DTYPE records [regions the last step returned, lanes] (lanes: 1, or the channels of an each-channel stream):
+        each region's frequency extent.  Only on a stream opened with bands=."""
+        return self._ctx.stream_bands(self._sid, self.lanes)[0]
+
+    def band_profiles(self) -> np.ndarray:
+        """float64 [regions the last step returned, lanes, 2, 128]: E of both spec channels (a stream opened with bands=dict(profile=True))."""
+        return self._ctx.stream_bands(self._sid, self.lanes, profile=True)[1]
 
     def output(self):
         """The frames the last step returned: (first_frame, int16 array [n, channels]) -- final, contiguous from step to step, the
@@ -109,24 +130,39 @@ class StreamDetector:
         return self._fp32
 
     def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5, erase=None,
-             channel_mode: str = "mix") -> Stream:
+             channel_mode: str = "mix", bands=False) -> Stream:
         """erase: None -- detection only; dict(pad_s=, min_len_s=) (either may be left out: 0) -- the stream also returns its frames
         as 16-bit PCM with the detected speech zeroed (Stream.output() after every step).
         channel_mode: "mix" -- detection on the channel mean; "each" -- on every channel alone: the regions and the series step()
         returns are the merged ones ("speech on any channel"), every channel is zeroed over them, Stream.avg(c) / Stream.peaks() give
-        the channels' own."""
+        the channels' own.
+        bands: False -- none; True or dict(q_low=.05, q_high=.95, speech_channel=1, profile=False) -- every region comes with its
+        frequency extent (Stream.bands(), Stream.band_profiles(), the fourth entry of step()'s tuples).  Needs the 0.6 s window step."""
         if channel_mode not in ("mix", "each"):
             raise ValueError(f"channel_mode must be 'mix' or 'each', not {channel_mode!r}")
+        bp = None
+        if bands:
+            bp = dict(q_low=.05, q_high=.95, speech_channel=1, profile=False)
+            if bands is not True:
+                unknown = set(bands) - set(bp)
+                if unknown:
+                    raise ValueError(f"bands: unknown keys {sorted(unknown)}")
+                bp.update(bands)
+            if self.window_step is not None and self.window_step != _native.check_step(0.6):
+                raise ValueError(f"bands need the default 0.6 s window step, not {self.window_step}")
         ctx = self._fp32_ctx() if self._switched else self._main
         if erase is not None:
             erase = dict(pad_s=float(erase.get("pad_s", 0.0)), min_len_s=float(erase.get("min_len_s", 0.0)))
-        if channel_mode == "each":
+        if bp is not None:
+            sid = ctx.stream_open_bands(fmt, sr, channels, threshold, break_s, erase, False, channel_mode == "each", bp["q_low"], bp["q_high"],
+                                        bp["speech_channel"], bp["profile"])
+        elif channel_mode == "each":
             sid = ctx.stream_open_channels(fmt, sr, channels, threshold, break_s, erase)
         elif erase is None:
             sid = ctx.stream_open(fmt, sr, channels, threshold, break_s)
         else:
             sid = ctx.stream_open_output(fmt, sr, channels, threshold, break_s, erase)
-        s = Stream(self, ctx, sid, fmt, sr, channels, erase, channel_mode)
+        s = Stream(self, ctx, sid, fmt, sr, channels, erase, channel_mode, bp)
         self._streams.append(s)
         return s
 
@@ -164,7 +200,7 @@ class StreamDetector:
 
     def step(self) -> dict:
         """One step over every stream -> {stream: (regions [(start, end)], avg float64[n], bin_idx int64[n])}: what became final (an
-        each-channel stream: its merged regions and merged series)."""
+        each-channel stream: its merged regions and merged series).  A stream opened with bands= has a fourth entry: Stream.bands()."""
         if not self._switched:
             self._step_main()
         if self._fp32 is not None and self._fp32 is not self._main:
@@ -172,7 +208,7 @@ class StreamDetector:
         out = {}
         for s in self._streams:
             a, idx = s._ctx.stream_avg(s._sid)
-            out[s] = (s._ctx.stream_regions(s._sid), a, idx)
+            out[s] = (s._ctx.stream_regions(s._sid), a, idx) + ((s.bands(),) if s.band_params is not None else ())
         return out
 
     def close(self):
