@@ -652,6 +652,40 @@ int ss_stream_open_bands(ss_ctx* ctx, int format, int sample_rate, int channels,
  * NULL: *n_out alone.  SS_ERR_CAPACITY when cap_regions < n. */
 int ss_stream_bands(ss_ctx* ctx, int stream_id, ss_region_band* out, double* profile, int64_t cap_regions, int64_t* n_out);
 
+/* ---- separation streams: the rule ----------------------------------------------------------------------------------------------
+ * The missing cell beside ss_silence_pcm, ss_stream_open_output and ss_separate_pcm is a stream with output whose output is separated
+ * instead of zeroed: everything it returns, concatenated, is to equal, byte for byte,
+ *     ss_separate_pcm(the whole recording, ss_erase_table(R, erase), params),   R = the regions the same stream returned.
+ * This header holds the host side of it -- which frames a step of such a stream may return as final, and how far they lag -- so that the
+ * rule stands and is tested without a GPU (tests/test_stream_separate_host.py).  The stream itself (an open call, the kernels, the
+ * image) is not built: see DESIGN.md section 20.
+ *
+ * Which frames a step may return (ss_stream_separate_limit).  With F = round(fade_s x sample_rate), N and hop = N / 4 the STFT's, b the
+ * final bins, H the frames decoded and Lz = ss_stream_output_limit(...) clamped to [0, H], a frame n may be returned before the close
+ * when
+ *   1. n < Lz - F.  Its blend weight w(min(n - a, e - 1 - n)) is decided.  Membership and the interval's start a are decided below Lz
+ *      (the zeroing rule).  The end e is not: a pending region that passes the filter grows (e >= Lz); an interval that ends at or
+ *      behind Lz can be joined by a later padded region that touches it (break_s < 2 pad_s), which removes its fade-out; the end of the
+ *      recording clamps e to a value >= H >= Lz.  In every case e >= Lz now and later, so e - 1 - n >= F and the weight is
+ *      w(min(n - a, F)).  An interval that ends below Lz is final: no later region starts below Lz.
+ *   2. n + N <= H.  The STFT frames floor(n / hop) - 1 .. + 2 over n read samples below n + N; the zeros behind the recording are
+ *      known only at the close.
+ *   3. STFT frame floor(n / hop) + 2 reads, unclamped, the bins j0, j0 + 1 <= b - 1: its gains (and those of the three frames before
+ *      it) are final, and the clamp to the last covered bin -- known only at the close -- does not act, since every final bin of an
+ *      open stream is a covered bin of the whole file.
+ * A step may return [frames_out, min(max(limit, frames_out), H)), limit the smallest of the three; the close returns the rest.
+ * Latency.  Such a frame at audio time t is returned by the first step after the stream holds audio past t + D_sep,
+ *     D_sep = D + fade_s + (N + 1) / sample_rate            (ss_stream_separate_latency; D of the streaming silencer):
+ * condition 1 costs F frames behind Lz >= H - D, condition 2 N frames, condition 3 less than B + N / sample_rate <= D + N / sample_rate
+ * (the frame two hops ahead must lie half a bin below the first non-final bin). */
+/* Host only: the limit frame of the rule above (the smallest of its three conditions), before the clamp to [frames_out, frames
+ * decoded]; it may be negative.  pending / pending_start / pending_end as ss_stream_output_limit; params as ss_separation_plan
+ * validates them (NULL: the defaults).  INT64_MIN on a bad argument. */
+int64_t ss_stream_separate_limit(int sample_rate, int64_t frames_decoded, int64_t bins_final, int pending, double pending_start,
+                                 double pending_end, const ss_stream_erase* erase, const ss_separation_params* params);
+/* Host only: D_sep in seconds; NaN on a bad argument. */
+double ss_stream_separate_latency(int sample_rate, double break_s, const ss_stream_erase* erase, const ss_separation_params* params);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */
 int ss_sync(ss_ctx* ctx);

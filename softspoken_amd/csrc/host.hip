@@ -317,6 +317,38 @@ extern "C" int64_t ss_stream_output_limit(int sr, int64_t bins_final, int pendin
     const double f = std::nearbyint(L * (double)sr);
     return (int64_t)std::min(std::max(f, -9.0e18), 9.0e18);
 }
+static int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) --q; return q; }
+
+// The separation streams' limit (include/softspoken.h "separation streams: the rule"): the smallest of the three conditions' first
+// frames that may not be returned.  Condition 3 in integers: frame k reads the bins j0, j0 + 1 with j0 = floor((512 (k hop + 3 sr) - 3 sr) / (6 sr));
+// j0 <= b - 2 <=> 512 k hop <= sr (6 b - 1539) - 1, and frame n needs frame floor(n / hop) + 2.
+extern "C" int64_t ss_stream_separate_limit(int sr, int64_t frames_decoded, int64_t bins_final, int pending, double pending_start,
+                                            double pending_end, const ss_stream_erase* erase, const ss_separation_params* params) {
+    std::string err;
+    if (sr <= 0 || sr > 768000 || frames_decoded < 0 || bins_final < 0 || bins_final > ((int64_t)1 << 40) || check_separation_params(params, err)) return INT64_MIN;
+    const int64_t lz = ss_stream_output_limit(sr, bins_final, pending, pending_start, pending_end, erase);
+    if (lz == INT64_MIN) return INT64_MIN;
+    const ss_separation_params prm = params ? *params : separation_defaults();
+    const int64_t F = (int64_t)std::nearbyint(prm.fade_s * (double)sr), N = sep_fft_size(sr), hop = N / 4;
+    const int64_t c1 = std::min(std::max<int64_t>(lz, 0), frames_decoded) - F, c2 = frames_decoded - N;
+    int64_t c3 = 0;
+    if (bins_final >= 1) {
+        const int64_t T = floor_div((int64_t)sr * (6 * bins_final - 1539) - 1, 512);
+        c3 = (floor_div(T, hop) - 1) * hop;
+    }
+    return std::min(c1, std::min(c2, c3));
+}
+
+extern "C" double ss_stream_separate_latency(int sr, double break_s, const ss_stream_erase* erase, const ss_separation_params* params) {
+    std::string err;
+    if (sr <= 0 || sr > 768000 || !std::isfinite(break_s) || !erase_ok(erase) || check_separation_params(params, err)) return std::nan("");
+    const ss_stream_erase e = erase ? *erase : ss_stream_erase{0, 0};
+    const ss_separation_params prm = params ? *params : separation_defaults();
+    const double half = sr == SS_SAMPLE_RATE ? 0.0 : std::ceil(32.0 / std::min(1.0, 22050.0 / (double)sr));
+    const double B = 3.0 + 2.0 * (3.0 / 256.0) + half / (double)sr, D = B + std::max(break_s, 0.0) + e.pad_s + e.min_len_s;
+    return D + prm.fade_s + (double)(sep_fft_size(sr) + 1) / (double)sr;
+}
+
 // Canonical 44-byte RIFF/WAVE header of a 16-bit PCM file (what libsndfile writes for subtype PCM_16).
 extern "C" int ss_wav_header_pcm16(int sr, int ch, int64_t frames, void* out44) {
     const int64_t data = frames * ch * 2;

@@ -185,6 +185,9 @@ _SIGS = {
     "ss_stream_open_bands": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.c_int,
                                        C.POINTER(BandParams), C.c_int, C.POINTER(C.c_int)]),
     "ss_stream_bands": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ss_stream_separate_limit": (C.c_int64, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase),
+                                             C.POINTER(SeparationParams)]),
+    "ss_stream_separate_latency": (C.c_double, [C.c_int, C.c_double, C.POINTER(StreamErase), C.POINTER(SeparationParams)]),
     "ss_separation_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), C.POINTER(SeparationPlanInfo)]),
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
@@ -365,6 +368,28 @@ def separation_params(fade_s: float = 0.01, min_gain: float = 0.0, above_fmax="m
     """struct ss_separation_params; above_fmax: "mute" / "keep" (or the SS_ABOVE_FMAX_* code itself: unknown codes reach the library)."""
     code = ABOVE_FMAX[above_fmax] if isinstance(above_fmax, str) else int(above_fmax)
     return SeparationParams(float(fade_s), float(min_gain), code, int(speech_channel))
+
+
+def stream_separate_limit(sr: int, frames_decoded: int, bins_final: int, pending=None, pad_s: float = 0.0, min_len_s: float = 0.0, **params) -> int:
+    """The frame up to which a separation stream's output would be decided (ss_stream_separate_limit, host only), before the clamp to
+    [frames_out, frames decoded].  pending as stream_output_limit's; params: separation_params' keywords."""
+    e = StreamErase(float(pad_s), float(min_len_s))
+    p = separation_params(**params)
+    ps, pe = pending if pending is not None else (0.0, 0.0)
+    v = lib().ss_stream_separate_limit(int(sr), int(frames_decoded), int(bins_final), int(pending is not None), float(ps), float(pe), C.byref(e), C.byref(p))
+    if v == -2 ** 63:
+        raise ValueError("ss_stream_separate_limit: bad argument")
+    return int(v)
+
+
+def stream_separate_latency(sr: int, break_s: float, pad_s: float = 0.0, min_len_s: float = 0.0, **params) -> float:
+    """D_sep in seconds (ss_stream_separate_latency, host only): the most audio a frame returned under that rule lags behind."""
+    e = StreamErase(float(pad_s), float(min_len_s))
+    p = separation_params(**params)
+    v = lib().ss_stream_separate_latency(int(sr), float(break_s), C.byref(e), C.byref(p))
+    if v != v:
+        raise ValueError("ss_stream_separate_latency: bad argument")
+    return float(v)
 
 
 def separation_plan(sr: int, frames: int, regions, **params) -> dict:
