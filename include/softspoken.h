@@ -556,6 +556,50 @@ int ss_separate_pcm(ss_ctx* ctx, const void* pcm, int format, int sample_rate, i
 int ss_separate_pcm_channels(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames,
                              const ss_region* regions, int64_t n_regions, const ss_separation_params* params, int16_t* out);
 
+/* ---- source output: silenced audio in the recording's own sample encoding -------------------------------------------------
+ * ss_silence_pcm, ss_separate_pcm and ss_separate_pcm_channels end in the reference's sf.write(path, data, sr): 16-bit PCM whatever the
+ * recording was (a 16-bit source comes back moved by one LSB at half of its codes, a 24-bit or float one loses its depth, floats beyond
+ * +-1 wrap).  The *_source calls keep the encoding: outside the erased intervals the output is the input's bytes, inside them it is the
+ * same audio in the same encoding.  fmt is the recording's enum ss_pcm_format, fb = channels x bytes per sample the frame size; the
+ * merged frame ranges of a region table are ss_silence_pcm's (Python round, clamped to the file, merged).  `out` takes frames x fb
+ * bytes; SS_ERR_CAPACITY when cap_bytes is smaller.
+ *   Zeroing (ss_silence_pcm_source).  A byte whose frame lies in no range is the input byte -- nothing is decoded, so NaN payloads, -0.0,
+ *   out-of-range floats and denormals pass through --; a byte whose frame lies in a range is the encoding's zero: 0x80 for SS_PCM_U8, 0x00
+ *   for the other eleven.  Any context will do (audio-only included).
+ *   Encode of a float32 y.  An integer format of b bits has S = 2^(b-1): q = rint(y x S), the product in float32 (exact: a power of two),
+ *   rounded to nearest even, SATURATED to [-S, S - 1]; a NaN gives 0.  U8 stores q + 128, S8 q.  F32 stores y's bits, F64 (double)y.  The
+ *   big-endian formats 7-12 store the same value with its bytes reversed.  The scale is the decode's own 2^(b-1), not 2^(b-1) - 1, so an
+ *   8-, 16- or 24-bit sample that goes through decode and encode unchanged comes back as itself; saturation in place of the 16-bit
+ *   path's wrap is deliberate (the 16-bit path keeps its wrap).
+ *   Separation (ss_separate_pcm_source, ss_separate_pcm_channels_source).  Steps 1-3 of the separation silencer and step 4's
+ *   y = x + w (p - x) unchanged; inside a merged interval every sample is the encode of y, outside the bytes are the input's.  State,
+ *   refusals and reset counting are ss_separate_pcm's and ss_separate_pcm_channels'. */
+int ss_silence_pcm_source(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames,
+                          const ss_region* regions, int64_t n_regions, void* out, int64_t cap_bytes);
+int ss_separate_pcm_source(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, const ss_region* regions,
+                           int64_t n_regions, const ss_separation_params* params, void* out, int64_t cap_bytes);
+int ss_separate_pcm_channels_source(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames,
+                                    const ss_region* regions, int64_t n_regions, const ss_separation_params* params, void* out,
+                                    int64_t cap_bytes);
+/* The 44-byte RIFF/WAVE header in front of such output for the little-endian encodings 1-6: format tag 1 (PCM) or 3 (IEEE float); for
+ * SS_PCM_S16 it is ss_wav_header_pcm16's.  SS_ERR_ARG for the encodings 7-12 (AIFF's) and for a data chunk of 4 GiB or more.  Host only. */
+int ss_wav_header(int format, int sample_rate, int channels, int64_t frames, void* out44);
+
+/* Streams.  ss_stream_open_source opens a stream with output (ss_stream_open_output; each_channel != 0: ss_stream_open_channels' lanes)
+ * whose output stays in the stream's own encoding; erase == NULL: pad_s = min_len_s = 0.  ss_stream_output_bytes reads it:
+ * frames [*first_frame, *first_frame + *n_frames) as *n_frames x fb bytes (out == NULL asks for the two counts; SS_ERR_CAPACITY when
+ * cap_bytes is smaller).  Equality: the concatenation of everything it returned equals, byte for byte,
+ *     ss_silence_pcm_source(the whole recording, E(R)),    R = the regions the same stream returned;
+ * the limit rule (ss_stream_output_limit), the bound D, the carried state and the refused-step behaviour are the streaming silencer's.
+ * ss_stream_output on such a stream, and ss_stream_output_bytes on any other, answer SS_ERR_STATE.  A step that holds no such stream
+ * makes exactly the launches it made before; 16-bit and source-output streams may share a step.
+ * Images: such a stream exports "SSSTRM06" (those eight bytes, then the "SSSTRM03" / "SSSTRM04" image of the same stream with 16-bit
+ * output, whole); every other stream writes the image it wrote before, and ss_stream_import reads all six.  Band streams have no
+ * source output. */
+int ss_stream_open_source(ss_ctx* ctx, int format, int sample_rate, int channels, double threshold, double break_s,
+                          const ss_stream_erase* erase, int each_channel, int* stream_id);
+int ss_stream_output_bytes(ss_ctx* ctx, int stream_id, void* out, int64_t cap_bytes, int64_t* first_frame, int64_t* n_frames);
+
 /* ---- region bands: the frequency extent of the speech inside each region, from the spec head -----------------------------
  * The reference's Raven table gives every detection the box 0 .. 8000 Hz (review_exporter.py, low_freq / high_freq).  The spec head's
  * speech map says where in the 128 mel bands the voice sits; this section reduces it, on the device, to the measures Raven users work

@@ -60,3 +60,7 @@ hip_channel_mode = os.environ.get('SOFTSPOKEN_CHANNELS', 'mix')
 # speech map inside the region), written to <detections stem>_bands.csv; the Raven export then draws each selection's own box
 # instead of 0 .. 8000 Hz.  '0' (default): nothing is computed and no file is written.
 hip_region_bands = os.environ.get('SOFTSPOKEN_BANDS', '0')
+# encoding of the silenced copies SilenceJob writes: 'pcm16' (default: the reference's sf.write, a 16-bit PCM WAV whatever the recording
+# was) or 'source' (the recording's own file image -- header, metadata chunks, container -- with only the erased intervals' sample bytes
+# replaced, in the recording's own sample encoding; written to <name>_silenced<the source's extension>)
+hip_silence_encoding = os.environ.get('SOFTSPOKEN_SILENCE_ENCODING', 'pcm16')

@@ -55,6 +55,14 @@ def channel_mode():
     return mode
 
 
+def silence_encoding():
+    """settings.hip_silence_encoding, checked: 'pcm16' or 'source'."""
+    enc = getattr(settings, "hip_silence_encoding", "pcm16")
+    if enc not in ('pcm16', 'source'):
+        raise ValueError(f"settings.hip_silence_encoding (SOFTSPOKEN_SILENCE_ENCODING) must be 'pcm16' or 'source', not {enc!r}")
+    return enc
+
+
 def region_bands_enabled():
     """settings.hip_region_bands, checked: '0' or '1'."""
     v = getattr(settings, "hip_region_bands", "0")

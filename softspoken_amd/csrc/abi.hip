@@ -73,7 +73,7 @@ extern "C" void ss_destroy(ss_ctx* c) {
     for (void* p : c->user_host) hipHostFree(p);
     free_workspace(c);
     for (auto& kv : c->taps) hipFree(kv.second.first);
-    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_batch, c->d_sil_out, c->d_sil_ranges, c->d_sx, c->d_sm, c->d_peaks};
+    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_batch, c->d_sil_out, c->d_sil_ranges, c->d_src_out, c->d_sx, c->d_sm, c->d_peaks};
     for (void* p : singles) if (p) hipFree(p);
     for (hipEvent_t ev : c->evpool) hipEventDestroy(ev);
     for (hipEvent_t ev : c->pass_ev) hipEventDestroy(ev);
@@ -245,6 +245,44 @@ extern "C" int ss_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, in
     return SS_OK;
 }
 
+// The output arguments of the *_source calls: `out` takes frames x channels x bytes-per-sample bytes
+static int check_source_out(ss_ctx* c, const char* who, int format, int ch, int64_t frames, const void* out, int64_t cap_bytes) {
+    const int64_t bytes = frames * ch * (int64_t)pcm_bytes_per_sample(format);
+    if (cap_bytes < 0 || (!out && bytes > 0)) return fail(c, SS_ERR_ARG, std::string(who) + ": bad argument");
+    if (cap_bytes < bytes) return fail(c, SS_ERR_CAPACITY, std::string(who) + ": the output takes " + std::to_string(bytes) + " bytes, room for " + std::to_string(cap_bytes));
+    return SS_OK;
+}
+
+// ss_silence_pcm in the recording's own encoding: no decode, the bytes of the merged frame ranges replaced by the encoding's zero
+extern "C" int ss_silence_pcm_source(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                                     int64_t n_regions, void* out, int64_t cap_bytes) {
+    int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
+    if (rc) return rc;
+    if ((!regions && n_regions > 0) || n_regions < 0) return fail(c, SS_ERR_ARG, "ss_silence_pcm_source: bad argument");
+    if ((rc = check_source_out(c, "ss_silence_pcm_source", format, ch, frames, out, cap_bytes))) return rc;
+    if (frames == 0) return SS_OK;
+    hipSetDevice(c->device);
+    const int64_t fb = (int64_t)ch * (int64_t)pcm_bytes_per_sample(format);
+    const size_t bytes = (size_t)(frames * fb);
+    std::vector<int64_t> ranges = silence_ranges(regions, n_regions, sr, frames);
+    for (int64_t& r : ranges) r *= fb;                        // byte ranges: the kernel knows no frames
+    size_t cap_b = c->pcm_cap;
+    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
+    c->pcm_cap = cap_b;
+    if ((rc = ensure(c, &c->d_src_out, &c->src_out_cap, bytes + 16))) return rc;
+    if ((rc = ensure(c, &c->d_sil_ranges, &c->sil_ranges_cap, ranges.size() + 2))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    if (!ranges.empty())
+        HIPCHK(c, hipMemcpyAsync(c->d_sil_ranges, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedLaunch sl(c, c->stream, "silence_source_kernel", 0.0, 2.0 * (double)bytes);
+        HIPCHK(c, launch_silence_source(c->d_pcm, (int64_t)bytes, c->d_sil_ranges, (int)(ranges.size() / 2), format, c->d_src_out, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(out, c->d_src_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // `ranges` and the caller's buffers are free again
+    return SS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // separation silencer (separate.hip): silencer_ui.py:974-998 with the spec head of pytorch_neural_nets.py:125-130,184-185
 // ------------------------------------------------------------------------------------------------------
@@ -302,6 +340,30 @@ extern "C" int ss_separate_pcm_channels(ss_ctx* c, const void* pcm, int format, 
     if ((rc = check_separation_params(params, err))) return fail(c, rc, "ss_separate_pcm_channels: " + err);
     hipSetDevice(c->device);
     return separate_pcm_channels(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
+// the two in the recording's own encoding: the same checks in the same order, then the capacity
+static int separate_source_call(ss_ctx* c, const char* who, bool each, const void* pcm, int format, int sr, int ch, int64_t frames,
+                                const ss_region* regions, int64_t n_regions, const ss_separation_params* params, void* out, int64_t cap_bytes) {
+    int rc = check_model_idle(c);
+    if (rc) return rc;
+    if ((rc = check_pcm_args(c, pcm, format, sr, ch, frames))) return rc;
+    if ((!regions && n_regions > 0) || n_regions < 0) return fail(c, SS_ERR_ARG, std::string(who) + ": bad argument");
+    if ((rc = check_source_out(c, who, format, ch, frames, out, cap_bytes))) return rc;
+    std::string err;
+    if ((rc = check_separation_params(params, err))) return fail(c, rc, std::string(who) + ": " + err);
+    hipSetDevice(c->device);
+    return separate_pcm_source(c, each && ch > 1, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
+extern "C" int ss_separate_pcm_source(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                                      int64_t n_regions, const ss_separation_params* params, void* out, int64_t cap_bytes) {
+    return separate_source_call(c, "ss_separate_pcm_source", false, pcm, format, sr, ch, frames, regions, n_regions, params, out, cap_bytes);
+}
+
+extern "C" int ss_separate_pcm_channels_source(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                                               int64_t n_regions, const ss_separation_params* params, void* out, int64_t cap_bytes) {
+    return separate_source_call(c, "ss_separate_pcm_channels_source", true, pcm, format, sr, ch, frames, regions, n_regions, params, out, cap_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -68,4 +68,45 @@ __device__ __forceinline__ float decode_sample(const unsigned char* p, int forma
     }
 }
 
+// float32 -> an integer sample of S = 2^(bits-1) steps per unit (decode_sample's own scale, so a decoded 8-, 16- or 24-bit sample comes
+// back as itself): the float32 product y * S -- exact, S being a power of two -- rounded to nearest even, saturated to [-S, S - 1]; a
+// NaN gives 0.  hi = S - 1.
+__device__ __forceinline__ int quantize_sample(float y, float S, int hi) {
+    const float q = rintf(y * S);
+    if (!(q == q)) return 0;
+    if (q >= S) return hi;
+    if (q <= -S) return -hi - 1;
+    return (int)q;
+}
+
+// float32 -> PCM, the inverse of decode_sample (include/softspoken.h "source output"): sample idx of `p` in `format`.  The integer formats
+// store quantize_sample (U8 offset by 128), F32 y's bits, F64 (double)y; 7-12 the same value with its bytes reversed.  24-bit samples are
+// three byte stores; every other store is one aligned word of the sample's size (p aligned to it).
+__device__ __forceinline__ void encode_sample(unsigned char* p, int format, int64_t idx, float y) {
+    switch (format) {
+        case 1: p[idx] = (unsigned char)(quantize_sample(y, 128.0f, 127) + 128); break;
+        case 2: ((short*)p)[idx] = (short)quantize_sample(y, 32768.0f, 32767); break;
+        case 3: {
+            const unsigned v = (unsigned)quantize_sample(y, 8388608.0f, 8388607);
+            unsigned char* b = p + idx * 3;
+            b[0] = (unsigned char)v; b[1] = (unsigned char)(v >> 8); b[2] = (unsigned char)(v >> 16);
+            break;
+        }
+        case 4: ((int*)p)[idx] = quantize_sample(y, 2147483648.0f, 2147483647); break;
+        case 5: ((float*)p)[idx] = y; break;
+        case 6: ((double*)p)[idx] = (double)y; break;
+        case 7: p[idx] = (unsigned char)quantize_sample(y, 128.0f, 127); break;
+        case 8: ((unsigned short*)p)[idx] = __builtin_bswap16((unsigned short)quantize_sample(y, 32768.0f, 32767)); break;
+        case 9: {
+            const unsigned v = (unsigned)quantize_sample(y, 8388608.0f, 8388607);
+            unsigned char* b = p + idx * 3;
+            b[2] = (unsigned char)v; b[1] = (unsigned char)(v >> 8); b[0] = (unsigned char)(v >> 16);
+            break;
+        }
+        case 10: ((uint32_t*)p)[idx] = __builtin_bswap32((uint32_t)quantize_sample(y, 2147483648.0f, 2147483647)); break;
+        case 11: ((uint32_t*)p)[idx] = __builtin_bswap32(__builtin_bit_cast(uint32_t, y)); break;
+        default: ((uint64_t*)p)[idx] = __builtin_bswap64(__builtin_bit_cast(uint64_t, (double)y)); break;
+    }
+}
+
 }  // namespace ss

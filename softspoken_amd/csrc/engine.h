@@ -190,6 +190,7 @@ struct ss_ctx {
     float* d_sm = nullptr; size_t sm_cap = 0;
     short* d_sil_out = nullptr; size_t sil_out_cap = 0;          // silencer output / frame ranges
     int64_t* d_sil_ranges = nullptr; size_t sil_ranges_cap = 0;
+    unsigned char* d_src_out = nullptr; size_t src_out_cap = 0;  // source-encoding output (ss_silence_pcm_source, ss_separate_pcm*_source): bytes
     float* d_mono = nullptr; size_t mono_cap = 0;
     double* d_peaks = nullptr; size_t peaks_cap = 0;             // ss_get_region_peaks: results, then the regions' bin ranges and the channels' offsets
     ss::BatchFile* d_batch = nullptr; size_t batch_cap = 0;
@@ -291,6 +292,9 @@ int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t
                  const ss_separation_params* params, int16_t* out);
 int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                           int64_t n_regions, const ss_separation_params* params, int16_t* out);
+// the two with their output in the recording's own encoding (frames x channels x bytes-per-sample bytes); each: one pass per channel
+int separate_pcm_source(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                        int64_t n_regions, const ss_separation_params* params, void* out);
 void free_separation(ss_ctx* c);
 // separate.hip, region bands (include/softspoken.h "region bands")
 int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err);

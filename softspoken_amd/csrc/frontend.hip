@@ -1188,6 +1188,69 @@ hipError_t launch_silence_encode(const void* pcm, int format, int channels, int6
     return hipGetLastError();
 }
 
+// The bytes of one 16-byte word that lie inside a range replaced by the zero byte (zero4: it, four times).  b0: the word's first byte
+// number; lo: the first range whose end is beyond b0; ranges: n_ranges disjoint ascending [begin, end) byte pairs.
+__device__ __forceinline__ uint4 zero_bytes_in_ranges(uint4 w, int64_t b0, int lo, const int64_t* __restrict__ ranges, int n_ranges, unsigned zero4) {
+    unsigned v[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        unsigned m = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t b = b0 + 4 * q + j;
+            while (lo < n_ranges && ranges[2 * lo + 1] <= b) ++lo;
+            if (lo < n_ranges && ranges[2 * lo] <= b) m |= 0xffu << (8 * j);
+        }
+        v[q] = (v[q] & ~m) | (zero4 & m);
+    }
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// Source-encoding silencer (include/softspoken.h "source output"): the recording's bytes with every byte inside a range replaced by the
+// encoding's zero byte; nothing is decoded.  `ranges` holds n_ranges disjoint, ascending [begin, end) BYTE pairs (the host multiplies the
+// frame ranges by the frame size).  A thread takes one 16-byte word: one load, one binary search for the word's first byte, then the word
+// as loaded (no range meets it), the zero pattern (a range covers it) or a byte-wise merge (an edge falls inside it).  in and out are
+// 16-byte aligned; the last nbytes % 16 bytes are loaded and stored one by one.
+__global__ __launch_bounds__(256) void silence_source_kernel(const unsigned char* __restrict__ in, int64_t nbytes,
+                                                             const int64_t* __restrict__ ranges, int n_ranges, unsigned zero4,
+                                                             unsigned char* __restrict__ out) {
+    const int64_t words = (nbytes + 15) / 16;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < words; t += (int64_t)gridDim.x * 256) {
+        const int64_t b0 = t * 16;
+        const bool whole = b0 + 16 <= nbytes;
+        uint4 w = make_uint4(0, 0, 0, 0);
+        if (whole) w = *(const uint4*)(in + b0);
+        else {
+            unsigned v[4] = {0, 0, 0, 0};
+            for (int j = 0; b0 + j < nbytes; ++j) v[j >> 2] |= (unsigned)in[b0 + j] << (8 * (j & 3));
+            w = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        int lo = 0, hi = n_ranges;                         // first range whose end is beyond b0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ranges[2 * mid + 1] <= b0) lo = mid + 1; else hi = mid;
+        }
+        if (lo < n_ranges && ranges[2 * lo] < b0 + 16) {   // the range meets the word
+            if (ranges[2 * lo] <= b0 && ranges[2 * lo + 1] >= b0 + 16) w = make_uint4(zero4, zero4, zero4, zero4);
+            else w = zero_bytes_in_ranges(w, b0, lo, ranges, n_ranges, zero4);
+        }
+        if (whole) *(uint4*)(out + b0) = w;
+        else {
+            const unsigned v[4] = {w.x, w.y, w.z, w.w};
+            for (int j = 0; b0 + j < nbytes; ++j) out[b0 + j] = (unsigned char)(v[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
+hipError_t launch_silence_source(const void* pcm, int64_t nbytes, const int64_t* d_byte_ranges, int n_ranges, int format, void* out, hipStream_t s) {
+    if (nbytes <= 0) return hipSuccess;
+    const unsigned zero4 = format == 1 ? 0x80808080u : 0u;      // SS_PCM_U8 is offset binary
+    const unsigned gx = (unsigned)std::min<int64_t>(((nbytes + 15) / 16 + 255) / 256, 16384);
+    hipLaunchKernelGGL(silence_source_kernel, dim3(gx), dim3(256), 0, s, (const unsigned char*)pcm, nbytes, d_byte_ranges, n_ranges, zero4,
+                       (unsigned char*)out);
+    return hipGetLastError();
+}
+
 hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, int n_files, int64_t max_out, int L, int M, int half,
                                  const float* taps, float* arena, int num_cus, hipStream_t s) {
     if (n_files <= 0 || max_out <= 0) return hipSuccess;
@@ -1496,6 +1559,61 @@ __global__ __launch_bounds__(256) void stream_copy_bytes_kernel(const StreamCopy
     }
 }
 
+// Streaming silencer in the streams' own encodings: stream_silence_kernel with bytes in and bytes out, silence_source_kernel's three
+// paths per 16-byte output word.  The word's 16 source bytes come from seg0 (the first n0 bytes) or seg1 at any alignment, loaded as
+// stream_copy_bytes_kernel loads: one 16-byte word where the source is 16-byte aligned, four 4-byte words where it is 4-byte aligned,
+// byte by byte otherwise and where the word straddles the two segments or the end.  Every stream's output starts at a multiple of 16.
+__global__ __launch_bounds__(256) void stream_silence_source_kernel(const StreamSilenceSource* __restrict__ ds, int n, unsigned char* __restrict__ out) {
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const StreamSilenceSource d = ds[k];
+        unsigned char* o = out + d.out_off;
+        const int64_t words = (d.n + 15) / 16;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < words; t += (int64_t)gridDim.x * 256) {
+            const int64_t i0 = t * 16;
+            const bool whole = i0 + 16 <= d.n;
+            const bool one_seg = whole && (i0 >= d.n0 || i0 + 16 <= d.n0);
+            uint4 w;
+            if (one_seg) {
+                const unsigned char* s = i0 >= d.n0 ? d.seg1 + (i0 - d.n0) : d.seg0 + i0;
+                const unsigned rel = (unsigned)((uintptr_t)s & 15);
+                if (rel == 0) w = *(const uint4*)s;
+                else if ((rel & 3) == 0) { const unsigned* s4 = (const unsigned*)s; w = make_uint4(s4[0], s4[1], s4[2], s4[3]); }
+                else {
+                    unsigned b[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        b[q] = (unsigned)s[4 * q] | ((unsigned)s[4 * q + 1] << 8) | ((unsigned)s[4 * q + 2] << 16) | ((unsigned)s[4 * q + 3] << 24);
+                    w = make_uint4(b[0], b[1], b[2], b[3]);
+                }
+            } else {
+                unsigned b[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int64_t i = i0 + j;
+                    if (i < d.n) b[j >> 2] |= (unsigned)(i < d.n0 ? d.seg0[i] : d.seg1[i - d.n0]) << (8 * (j & 3));
+                }
+                w = make_uint4(b[0], b[1], b[2], b[3]);
+            }
+            const int64_t b0 = d.byte0 + i0;
+            int lo = 0, hi = d.n_ranges;                    // first range whose end is beyond b0
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (d.ranges[2 * mid + 1] <= b0) lo = mid + 1; else hi = mid;
+            }
+            if (lo < d.n_ranges && d.ranges[2 * lo] < b0 + 16) {
+                if (d.ranges[2 * lo] <= b0 && d.ranges[2 * lo + 1] >= b0 + 16) w = make_uint4(d.zero4, d.zero4, d.zero4, d.zero4);
+                else w = zero_bytes_in_ranges(w, b0, lo, d.ranges, d.n_ranges, d.zero4);
+            }
+            if (whole) *(uint4*)(o + i0) = w;
+            else {
+                const unsigned v[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) if (i0 + j < d.n) o[i0 + j] = (unsigned char)(v[j >> 2] >> (8 * (j & 3)));
+            }
+        }
+    }
+}
+
 static dim3 stream_grid(int n, int64_t max_elems) {
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_elems + 255) / 256, 1024));
     return dim3(gx, (unsigned)std::min(n, 65535));
@@ -1534,6 +1652,11 @@ hipError_t launch_stream_union(const StreamUnion* d, int n, int64_t max_bins, do
 hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s) {
     if (n <= 0 || max_samples <= 0) return hipSuccess;
     hipLaunchKernelGGL(stream_silence_kernel, stream_grid(n, (max_samples + 3) / 4), dim3(256), 0, s, d, n, out);
+    return hipGetLastError();
+}
+hipError_t launch_stream_silence_source(const StreamSilenceSource* d, int n, int64_t max_bytes, unsigned char* out, hipStream_t s) {
+    if (n <= 0 || max_bytes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_silence_source_kernel, stream_grid(n, (max_bytes + 15) / 16), dim3(256), 0, s, d, n, out);
     return hipGetLastError();
 }
 hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s) {

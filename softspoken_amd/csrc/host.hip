@@ -362,3 +362,20 @@ extern "C" int ss_wav_header_pcm16(int sr, int ch, int64_t frames, void* out44) 
     memcpy(h + 36, "data", 4); u32(40, (uint32_t)data);
     return SS_OK;
 }
+
+// The same 44 bytes for any of the little-endian encodings 1-6: format tag 1 (PCM) or 3 (IEEE float), the sample's own width.  For
+// SS_PCM_S16 these are ss_wav_header_pcm16's bytes.  The big-endian encodings 7-12 have no RIFF/WAVE form.
+extern "C" int ss_wav_header(int format, int sr, int ch, int64_t frames, void* out44) {
+    if (!out44 || format < SS_PCM_U8 || format > SS_PCM_F64 || sr <= 0 || ch < 1 || ch > 64 || frames < 0 || frames > ((int64_t)1 << 36))
+        return fail(nullptr, SS_ERR_ARG, "ss_wav_header: bad argument (encodings 1-6 only)");
+    const int64_t bps = (int64_t)pcm_bytes_per_sample(format), data = frames * ch * bps;
+    if (data + 36 > 0xFFFFFFFFLL) return fail(nullptr, SS_ERR_ARG, "ss_wav_header: bad argument (a RIFF file holds < 4 GiB)");
+    unsigned char* h = (unsigned char*)out44;
+    auto u32 = [&](int at, uint32_t v) { for (int i = 0; i < 4; ++i) h[at + i] = (unsigned char)(v >> (8 * i)); };
+    auto u16 = [&](int at, uint32_t v) { h[at] = (unsigned char)v; h[at + 1] = (unsigned char)(v >> 8); };
+    memcpy(h, "RIFF", 4); u32(4, (uint32_t)(36 + data)); memcpy(h + 8, "WAVEfmt ", 8); u32(16, 16);
+    u16(20, format >= SS_PCM_F32 ? 3 : 1); u16(22, (uint32_t)ch); u32(24, (uint32_t)sr); u32(28, (uint32_t)((int64_t)sr * ch * bps));
+    u16(32, (uint32_t)(ch * bps)); u16(34, (uint32_t)(8 * bps));
+    memcpy(h + 36, "data", 4); u32(40, (uint32_t)data);
+    return SS_OK;
+}

@@ -276,6 +276,9 @@ hipError_t launch_stft512_mag(const float* x, int64_t n, int64_t n_frames, float
 // silencer: decode -> zero [begin,end) frame ranges (disjoint, ascending) -> 16-bit PCM
 hipError_t launch_silence_encode(const void* pcm, int format, int channels, int64_t frames, const int64_t* d_ranges, int n_ranges,
                                  short* out, hipStream_t s);
+// source-encoding silencer: the nbytes of pcm with the bytes inside d_byte_ranges (disjoint ascending [begin, end) byte pairs) replaced
+// by the zero byte of `format`; pcm and out 16-byte aligned
+hipError_t launch_silence_source(const void* pcm, int64_t nbytes, const int64_t* d_byte_ranges, int n_ranges, int format, void* out, hipStream_t s);
 // decode + mixdown + polyphase resampling in one launch (no mono tensor); applies when resample_fused_applies says so
 bool resample_fused_applies(int L, int M, int half);
 hipError_t launch_resample_fused(const void* pcm, int format, int channels, const BatchFile* d_files, int n_files, int64_t max_out, int L, int M,
@@ -318,6 +321,11 @@ struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, 
 struct StreamSilence { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, frame0, n, out_off;
                        int32_t n_ranges, format, channels, pad; };
 struct StreamCopyBytes { const unsigned char* src; unsigned char* dst; int64_t n; };   // n bytes, any alignment
+// streaming silencer in the stream's own encoding: bytes [byte0, byte0 + n) of the recording -> out[out_off ..) (out_off a multiple of 16);
+// the first n0 bytes are read from seg0, the others from seg1, at any alignment; bytes inside ranges (n_ranges disjoint ascending
+// [begin, end) pairs of recording BYTE numbers) become the zero byte (zero4: it, four times)
+struct StreamSilenceSource { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, byte0, n, out_off;
+                             int32_t n_ranges; uint32_t zero4; };
 // each-channel streams (ss_stream_open_channels): the pushed frames of a stream of `channels` lanes -> channel c's samples at
 // dst[c stride ..), no mean; pcm_off is a multiple of 16 (the fast form reads a 16-bit stereo frame as one 32-bit word)
 struct StreamDecodeChannels { int64_t pcm_off; int64_t frames; float* dst; int64_t stride; int32_t format, channels; };
@@ -326,6 +334,7 @@ struct StreamDecodeChannels { int64_t pcm_off; int64_t frames; float* dst; int64
 struct StreamUnion { int64_t in_off, nb, out_off; int32_t lanes, pad; };
 hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s);
 hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s);
+hipError_t launch_stream_silence_source(const StreamSilenceSource* d, int n, int64_t max_bytes, unsigned char* out, hipStream_t s);
 hipError_t launch_stream_copy(const StreamCopy* d, int n, int64_t max_n, hipStream_t s);
 hipError_t launch_stream_decode(const void* pcm, const StreamDecode* d, int n, int64_t max_frames, hipStream_t s);
 hipError_t launch_stream_resample(const StreamResample* d, int n, int64_t max_n, hipStream_t s);

@@ -268,34 +268,58 @@ __global__ __launch_bounds__(256) void sep_stft_form_kernel(const unsigned char*
     }
 }
 
-// Output samples of the pieces in segs (out0 ascending, `total` samples in all) x channels: p = the four frames over the sample, added in
-// ascending frame order; y = x + w (p - x) over the fade ramps; lrintf(y * 32767) as silence_encode_kernel.
+// Output sample `idx` (of total x channels) of the pieces in segs (out0 ascending): p = the four frames over the sample, added in
+// ascending frame order; y = x + w (p - x) over the fade ramps.  at: the sample's index n channels + c in the recording.
+__device__ __forceinline__ float sep_blend_sample(const unsigned char* __restrict__ pcm, int format, int channels, const SepSeg* __restrict__ segs,
+                                                  int n_segs, int hop, int N, int npairs, const float2* __restrict__ fout, int64_t F, int64_t idx,
+                                                  int64_t& at) {
+#pragma clang fp contract(off)
+    const int64_t t = idx / channels;
+    const int c = (int)(idx - t * channels);
+    int lo = 0, hi = n_segs - 1;                             // last piece with out0 <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].out0 <= t) lo = mid; else hi = mid - 1;
+    }
+    const SepSeg sg = segs[lo];
+    const int64_t n = sg.s0 + (t - sg.out0);
+    const int64_t kb = n / hop;                              // frames kb - 1 .. kb + 2 hold sample n (N = 4 hop)
+    float p = 0.f;
+    for (int64_t k = kb - 1; k <= kb + 2; ++k) {
+        const float2 v = fout[((size_t)(sg.rec0 + (k - sg.k0)) * npairs + (c >> 1)) * N + (n - k * hop + N / 2)];
+        p += (c & 1) ? v.y : v.x;
+    }
+    at = n * channels + c;
+    const float x = decode_sample(pcm, format, at);
+    const int64_t d = std::min(n - sg.a, sg.b - 1 - n);
+    const float w = d < F ? (float)(0.5 - 0.5 * cospi(((double)d + 0.5) / (double)F)) : 1.0f;
+    return x + w * (p - x);
+}
+
+// The blend over `total` samples x channels, encoded as silence_encode_kernel encodes: lrintf(y * 32767), no clipping.
 __global__ __launch_bounds__(256) void sep_blend_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
                                                         const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
                                                         int npairs, const float2* __restrict__ fout, int64_t F, short* __restrict__ out) {
 #pragma clang fp contract(off)
     const int64_t all = total * channels;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < all; idx += (int64_t)gridDim.x * 256) {
-        const int64_t t = idx / channels;
-        const int c = (int)(idx - t * channels);
-        int lo = 0, hi = n_segs - 1;                             // last piece with out0 <= t
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (segs[mid].out0 <= t) lo = mid; else hi = mid - 1;
-        }
-        const SepSeg sg = segs[lo];
-        const int64_t n = sg.s0 + (t - sg.out0);
-        const int64_t kb = n / hop;                              // frames kb - 1 .. kb + 2 hold sample n (N = 4 hop)
-        float p = 0.f;
-        for (int64_t k = kb - 1; k <= kb + 2; ++k) {
-            const float2 v = fout[((size_t)(sg.rec0 + (k - sg.k0)) * npairs + (c >> 1)) * N + (n - k * hop + N / 2)];
-            p += (c & 1) ? v.y : v.x;
-        }
-        const float x = decode_sample(pcm, format, n * channels + c);
-        const int64_t d = std::min(n - sg.a, sg.b - 1 - n);
-        const float w = d < F ? (float)(0.5 - 0.5 * cospi(((double)d + 0.5) / (double)F)) : 1.0f;
-        const float y = x + w * (p - x);
-        out[n * channels + c] = (short)__float2int_rn(y * 32767.0f);
+        int64_t at;
+        const float y = sep_blend_sample(pcm, format, channels, segs, n_segs, hop, N, npairs, fout, F, idx, at);
+        out[at] = (short)__float2int_rn(y * 32767.0f);
+    }
+}
+
+// The same blend stored in the recording's own encoding (dsp.h encode_sample: the decode's scale, saturated), over a copy of the PCM:
+// the bytes outside the intervals stay the input's.
+__global__ __launch_bounds__(256) void sep_blend_source_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
+                                                               const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
+                                                               int npairs, const float2* __restrict__ fout, int64_t F,
+                                                               unsigned char* __restrict__ out) {
+    const int64_t all = total * channels;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < all; idx += (int64_t)gridDim.x * 256) {
+        int64_t at;
+        const float y = sep_blend_sample(pcm, format, channels, segs, n_segs, hop, N, npairs, fout, F, idx, at);
+        encode_sample(out, format, at, y);
     }
 }
 
@@ -561,8 +585,10 @@ static hipError_t launch_sep_stft_n(int N, bool each, const void* pcm, int forma
 static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes of resynthesised frames held at once (pieces / chunks)
 
 // each (ss_separate_pcm_channels, ch > 1): the signals are the channels alone, every channel's STFT gets the gains of its own maps
-static int separate_run(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                        int64_t n_regions, const ss_separation_params* params, int16_t* out) {
+// src: the output in the recording's own encoding (out: frames x ch x bytes-per-sample bytes) -- a device copy of the PCM in place of
+// the transcode, sep_blend_source_kernel in place of sep_blend_kernel; otherwise out is int16
+static int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                        int64_t n_regions, const ss_separation_params* params, void* out) {
     const ss_separation_params prm = params ? *params : separation_defaults();
     SepPlan pl;
     separation_plan(sr, frames, regions, n_regions, pl);
@@ -573,9 +599,12 @@ static int separate_run(ss_ctx* c, bool each, const void* pcm, int format, int s
     if (rc) return rc;
     if (frames == 0) return SS_OK;
     SepState& st = sep_state(c);
-    const size_t total = (size_t)frames * ch;
-    if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
-    {   // the transcode of the whole file: what ss_silence_pcm writes outside its ranges
+    const size_t total = (size_t)frames * ch, pcm_bytes = total * pcm_bytes_per_sample(format);
+    if (src) {   // the recording's own bytes: what ss_silence_pcm_source writes outside its ranges
+        if ((rc = ensure(c, &c->d_src_out, &c->src_out_cap, pcm_bytes + 16))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_src_out, c->d_pcm, pcm_bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {     // the transcode of the whole file: what ss_silence_pcm writes outside its ranges
+        if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
         ScopedLaunch sl(c, c->stream, "sep_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
         HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, nullptr, 0, c->d_sil_out, c->stream));
     }
@@ -649,26 +678,39 @@ static int separate_run(ss_ctx* c, bool each, const void* pcm, int format, int s
                                             (size_t)ncb * 128, *tb, gain_hi, st.d_fout, c->stream));
             }
             const int64_t all = ck.total * ch;
-            ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
             const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
+            if (src) {
+                ScopedLaunch sl(c, c->stream, "sep_blend_source_kernel", 0.0, (double)all * (16.0 + 2.0 * pcm_bytes_per_sample(format)));
+                hipLaunchKernelGGL(sep_blend_source_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
+                                   st.d_segs + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_src_out);
+                HIPCHK(c, hipGetLastError());
+                continue;
+            }
+            ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
             hipLaunchKernelGGL(sep_blend_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch, st.d_segs + ck.seg0,
                                (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_sil_out);
             HIPCHK(c, hipGetLastError());
         }
     }
-    HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
+    if (src) HIPCHK(c, hipMemcpyAsync(out, c->d_src_out, pcm_bytes, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // fr / sg and the caller's buffers are free again
     return SS_OK;
 }
 
 int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
                  const ss_separation_params* params, int16_t* out) {
-    return separate_run(c, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+    return separate_run(c, false, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                           int64_t n_regions, const ss_separation_params* params, int16_t* out) {
-    return separate_run(c, ch > 1, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+    return separate_run(c, ch > 1, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+}
+
+int separate_pcm_source(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                        int64_t n_regions, const ss_separation_params* params, void* out) {
+    return separate_run(c, each, true, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 // =========================================================================================================

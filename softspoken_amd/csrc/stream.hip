@@ -165,6 +165,7 @@ struct StreamRec {
     // current half of the byte arena (byte offset raw_off, a multiple of 16) -- or in h_raw after an import (on_host); er_rng: the frame
     // ranges [begin, end) of the returned regions' erase table that reach past frames_out (ascending, merged)
     bool out_on = false; ss_stream_erase er{0, 0};
+    bool src_out = false;                                 // the output in the stream's own encoding (ss_stream_open_source): o_off counts bytes
     int64_t frames_out = 0, erased = 0, raw_off = 0;
     std::vector<int64_t> er_rng; std::vector<unsigned char> h_raw;
     int64_t o_first = 0, o_n = 0, o_off = 0;          // the last step's frames: o_n of them at the pinned output buffer + o_off (int16s)
@@ -298,6 +299,8 @@ struct StreamSet {
     unsigned char* h_up2 = nullptr; size_t h_up2_cap = 0;
     short* d_out = nullptr; size_t out_cap = 0;
     unsigned char* h_out = nullptr; size_t h_out_cap = 0;
+    unsigned char* d_outb = nullptr; size_t outb_cap = 0;               // the source-encoding streams' output, bytes
+    unsigned char* h_outb = nullptr; size_t h_outb_cap = 0;
     // streams with bands: the step's final maps [bins][256] of every band lane, the upload of the walk's events and the lanes'
     // descriptors behind the flags download, the records and profiles on the device and in pinned memory, the 130 band edges
     float* d_fmap = nullptr; size_t fmap_cap = 0;
@@ -314,9 +317,9 @@ void free_streams(ss_ctx* c) {
     StreamSet* S = c->streams;
     if (!S) return;
     for (float* a : S->arena) if (a) hipFree(a);
-    void* ds[] = {S->d_up, S->d_newlg, S->d_avg, S->d_flags, S->barena[0], S->barena[1], S->d_up2, S->d_out, S->d_fmap, S->d_up3, S->d_bout, S->d_bprof, S->d_hz, S->d_spec};
+    void* ds[] = {S->d_up, S->d_newlg, S->d_avg, S->d_flags, S->barena[0], S->barena[1], S->d_up2, S->d_out, S->d_outb, S->d_fmap, S->d_up3, S->d_bout, S->d_bprof, S->d_hz, S->d_spec};
     for (void* p : ds) if (p) hipFree(p);
-    void* hs[] = {S->h_up, S->h_up2, S->h_out, S->h_up3, S->h_bres};
+    void* hs[] = {S->h_up, S->h_up2, S->h_out, S->h_outb, S->h_up3, S->h_bres};
     for (void* p : hs) if (p) hipHostFree(p);
     delete S;
     c->streams = nullptr;
@@ -389,6 +392,16 @@ extern "C" int ss_stream_open_output(ss_ctx* c, int format, int sr, int ch, doub
 extern "C" int ss_stream_open_channels(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
                                        int with_output, int* id) {
     return open_stream(c, format, sr, ch, threshold, break_s, erase, erase != nullptr || with_output != 0, id, true);
+}
+
+// a stream with output in its own encoding: ss_stream_open_channels' stream (each_channel == 0: the mix's) read through
+// ss_stream_output_bytes
+extern "C" int ss_stream_open_source(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
+                                     int each_channel, int* id) {
+    int rc = open_stream(c, format, sr, ch, threshold, break_s, erase, true, id, each_channel != 0);
+    if (rc) return rc;
+    find_stream(c, *id)->src_out = true;
+    return SS_OK;
 }
 
 extern "C" int ss_stream_open_bands(ss_ctx* c, int format, int sr, int ch, double threshold, double break_s, const ss_stream_erase* erase,
@@ -499,10 +512,23 @@ extern "C" int ss_stream_output(ss_ctx* c, int id, int16_t* out, int64_t cap_fra
     StreamRec* s = find_stream(c, id);
     if (!s || !first_frame || !n_frames) return fail(c, SS_ERR_ARG, "ss_stream_output: bad argument");
     if (!s->out_on) return fail(c, SS_ERR_STATE, "ss_stream_output: the stream was opened without output (ss_stream_open_output)");
+    if (s->src_out) return fail(c, SS_ERR_STATE, "ss_stream_output: the stream's output is in its own encoding (ss_stream_output_bytes)");
     *first_frame = s->o_first; *n_frames = s->o_n;
     if (!out) return SS_OK;
     if (cap_frames < s->o_n) return fail(c, SS_ERR_CAPACITY, "ss_stream_output: capacity < " + std::to_string(s->o_n));
     if (s->o_n) memcpy(out, (const int16_t*)c->streams->h_out + s->o_off, (size_t)(s->o_n * s->ch) * 2);
+    return SS_OK;
+}
+
+extern "C" int ss_stream_output_bytes(ss_ctx* c, int id, void* out, int64_t cap_bytes, int64_t* first_frame, int64_t* n_frames) {
+    StreamRec* s = find_stream(c, id);
+    if (!s || !first_frame || !n_frames) return fail(c, SS_ERR_ARG, "ss_stream_output_bytes: bad argument");
+    if (!s->src_out) return fail(c, SS_ERR_STATE, "ss_stream_output_bytes: the stream was not opened with ss_stream_open_source");
+    *first_frame = s->o_first; *n_frames = s->o_n;
+    if (!out) return SS_OK;
+    const int64_t bytes = s->o_n * s->frame_bytes();
+    if (cap_bytes < bytes) return fail(c, SS_ERR_CAPACITY, "ss_stream_output_bytes: capacity < " + std::to_string(bytes));
+    if (bytes) memcpy(out, c->streams->h_outb + s->o_off, (size_t)bytes);
     return SS_OK;
 }
 
@@ -634,7 +660,7 @@ static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*
     std::vector<OutPlan> ops;
     std::vector<int64_t> rng_all;
     auto al = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
-    int64_t total_out = 0, raw_need = 0;
+    int64_t total_out = 0, total_outb = 0, raw_need = 0;      // int16 samples; bytes of the source-encoding streams; carried bytes
     for (auto& [sp, p] : act) {
         StreamRec& s = *sp;
         if (!s.out_on) continue;
@@ -671,7 +697,8 @@ static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*
             if (hi > lo) { rng_all.push_back(lo); rng_all.push_back(hi); o.erased += hi - lo; }
         }
         o.n_rng = ((int64_t)rng_all.size() - o.rng_at) / 2;
-        o.out_off = total_out; total_out = al(total_out + (o.limit - s.frames_out) * s.ch, 8);
+        if (s.src_out) { o.out_off = total_outb; total_outb = al(total_outb + (o.limit - s.frames_out) * s.frame_bytes(), 16); }
+        else { o.out_off = total_out; total_out = al(total_out + (o.limit - s.frames_out) * s.ch, 8); }
         o.raw_off = raw_need; raw_need = al(raw_need + (s.frames_in - o.limit) * s.frame_bytes(), 16);
         ops.push_back(o);
     }
@@ -681,15 +708,21 @@ static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*
     if ((rc = ensure(c, &S.barena[bnxt], &S.barena_cap[bnxt], (size_t)std::max<int64_t>(raw_need, 16)))) return rc;
     if ((rc = ensure(c, &S.d_out, &S.out_cap, (size_t)std::max<int64_t>(total_out, 8)))) return rc;
     if ((rc = ensure_pinned(c, &S.h_out, &S.h_out_cap, (size_t)std::max<int64_t>(total_out, 8) * 2))) return rc;
+    if (total_outb > 0) {
+        if ((rc = ensure(c, &S.d_outb, &S.outb_cap, (size_t)total_outb + 16))) return rc;
+        if ((rc = ensure_pinned(c, &S.h_outb, &S.h_outb_cap, (size_t)total_outb + 16))) return rc;
+    }
     const size_t o_sil = 0, o_cpb = (size_t)al((int64_t)(ops.size() * sizeof(StreamSilence)), 64);
-    const size_t o_rng = o_cpb + (size_t)al((int64_t)(2 * ops.size() * sizeof(StreamCopyBytes)), 64);
+    const size_t o_src = o_cpb + (size_t)al((int64_t)(2 * ops.size() * sizeof(StreamCopyBytes)), 64);
+    const size_t o_rng = o_src + (size_t)al((int64_t)(ops.size() * sizeof(StreamSilenceSource)), 64);
     const size_t up2 = o_rng + rng_all.size() * 8 + 64;
     if ((rc = ensure(c, &S.d_up2, &S.up2_cap, up2))) return rc;
     if ((rc = ensure_pinned(c, &S.h_up2, &S.h_up2_cap, up2))) return rc;
     std::vector<StreamSilence> sil;
     std::vector<StreamCopyBytes> cpb;
-    int64_t max_samples = 0, max_bytes = 0;
-    double in_bytes = 0, carried = 0;
+    std::vector<StreamSilenceSource> srcs;
+    int64_t max_samples = 0, max_bytes = 0, max_src = 0;
+    double in_bytes = 0, carried = 0, src_bytes = 0;
     for (const OutPlan& o : ops) {
         StreamRec& s = *o.s;
         const StreamPlan& p = *o.p;
@@ -697,7 +730,13 @@ static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*
         // the frames [frames_out, f0) carried from earlier steps, and the step's own [f0, frames_in) in the upload
         const unsigned char* seg0 = p.was_host ? S.d_up + p.raw_up_off : S.barena[S.bcur] + s.raw_off;
         const unsigned char* seg1 = S.d_up + p.up_off;
-        if (n > 0) {
+        if (n > 0 && s.src_out) {   // bytes in, bytes out: the ranges as byte numbers of the recording
+            for (int64_t i = o.rng_at; i < o.rng_at + 2 * o.n_rng; ++i) rng_all[(size_t)i] *= fb;
+            srcs.push_back(StreamSilenceSource{seg0, seg1, (const int64_t*)(S.d_up2 + o_rng) + o.rng_at, std::min(n, p.f0 - s.frames_out) * fb,
+                                               s.frames_out * fb, n * fb, o.out_off, (int32_t)o.n_rng, s.format == SS_PCM_U8 ? 0x80808080u : 0u});
+            max_src = std::max(max_src, n * fb);
+            src_bytes += (double)(n * fb);
+        } else if (n > 0) {
             sil.push_back(StreamSilence{seg0, seg1, (const int64_t*)(S.d_up2 + o_rng) + o.rng_at, std::min(n, p.f0 - s.frames_out), s.frames_out, n,
                                         o.out_off, (int32_t)o.n_rng, s.format, s.ch, 0});
             max_samples = std::max(max_samples, n * s.ch);
@@ -715,17 +754,23 @@ static int step_output(ss_ctx* c, StreamSet& S, std::vector<std::pair<StreamRec*
     }
     if (!sil.empty()) memcpy(S.h_up2 + o_sil, sil.data(), sil.size() * sizeof(StreamSilence));
     if (!cpb.empty()) memcpy(S.h_up2 + o_cpb, cpb.data(), cpb.size() * sizeof(StreamCopyBytes));
+    if (!srcs.empty()) memcpy(S.h_up2 + o_src, srcs.data(), srcs.size() * sizeof(StreamSilenceSource));
     if (!rng_all.empty()) memcpy(S.h_up2 + o_rng, rng_all.data(), rng_all.size() * 8);
     HIPCHK(c, hipMemcpyAsync(S.d_up2, S.h_up2, o_rng + rng_all.size() * 8, hipMemcpyHostToDevice, c->stream));
     {
         ScopedLaunch sl(c, c->stream, "stream_silence_kernel", 0.0, in_bytes + 2.0 * (double)total_out);
         HIPCHK(c, launch_stream_silence((const StreamSilence*)(S.d_up2 + o_sil), (int)sil.size(), max_samples, S.d_out, c->stream));
     }
+    if (!srcs.empty()) {        // (the copy of the carried PCM below writes the other half of the byte arena: either order will do)
+        ScopedLaunch sl(c, c->stream, "stream_silence_source_kernel", 0.0, 2.0 * src_bytes);
+        HIPCHK(c, launch_stream_silence_source((const StreamSilenceSource*)(S.d_up2 + o_src), (int)srcs.size(), max_src, S.d_outb, c->stream));
+    }
     {
         ScopedLaunch sl(c, c->stream, "stream_copy_bytes", 0.0, 2.0 * carried);
         HIPCHK(c, launch_stream_copy_bytes((const StreamCopyBytes*)(S.d_up2 + o_cpb), (int)cpb.size(), max_bytes, c->stream));
     }
     if (!sil.empty()) HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, (size_t)total_out * 2, hipMemcpyDeviceToHost, c->stream));
+    if (!srcs.empty()) HIPCHK(c, hipMemcpyAsync(S.h_outb, S.d_outb, (size_t)total_outb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
     for (const OutPlan& o : ops) {
@@ -1164,12 +1209,40 @@ struct ImageLanes { int32_t lanes, with_out; };
 // then every lane's map sums [256][bs_n] of the bins [bins_done, bins_done + bs_n)), then the held raw PCM of a stream with output
 constexpr char kMagicBands[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '5'};
 struct ImageBands { int32_t lanes, with_out, want_prof, parked, speech_channel, reserved; double q_low, q_high; int64_t bs_n; };
+// "SSSTRM06": a stream with output in its own encoding (ss_stream_open_source) -- these eight bytes, then the image the stream would
+// write without that property ("SSSTRM03" or "SSSTRM04"), whole
+constexpr char kMagicSource[8] = {'S', 'S', 'S', 'T', 'R', 'M', '0', '6'};
 constexpr int64_t kMaxCarriedBins = 4096;             // (a stream carries the sums of about 300 bins)
 }  // namespace
+
+static int export_image(ss_ctx* c, StreamRec* s, void* buf, int64_t cap, int64_t* n_out);
+static int import_image(ss_ctx* c, const void* buf, int64_t n, int* id);
 
 extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64_t* n_out) {
     StreamRec* s = find_stream(c, id);
     if (!s || !n_out) return fail(c, SS_ERR_ARG, "ss_stream_export: bad argument");
+    if (!s->src_out) return export_image(c, s, buf, cap, n_out);
+    int rc = export_image(c, s, buf ? (unsigned char*)buf + 8 : nullptr, buf ? std::max<int64_t>(cap - 8, 0) : 0, n_out);
+    *n_out += 8;
+    if (rc == SS_OK && buf) memcpy(buf, kMagicSource, 8);
+    return rc;
+}
+
+extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) {
+    if (!c || !buf || !id || n < (int64_t)sizeof(ImageHdr)) return fail(c, SS_ERR_ARG, "ss_stream_import: bad argument");
+    if (memcmp(buf, kMagicSource, 8) != 0) return import_image(c, buf, n, id);
+    const unsigned char* inner = (const unsigned char*)buf + 8;
+    if (n < 8 + (int64_t)sizeof(ImageHdr) || (memcmp(inner, kMagicOut, 8) != 0 && memcmp(inner, kMagicLanes, 8) != 0))
+        return fail(c, SS_ERR_FORMAT, "ss_stream_import: not a stream image");
+    int rc = import_image(c, inner, n - 8, id);
+    if (rc) return rc;
+    StreamRec* s = find_stream(c, *id);
+    if (!s->out_on) { ss_stream_free(c, *id); return fail(c, SS_ERR_FORMAT, "ss_stream_import: a source-output image of a stream without output"); }
+    s->src_out = true;
+    return SS_OK;
+}
+
+static int export_image(ss_ctx* c, StreamRec* s, void* buf, int64_t cap, int64_t* n_out) {
     const bool each = s->lanes > 1, bands = s->bands_on;
     const bool with_step = bands || each || s->out_on || s->step != SS_STEP_DEFAULT;
     const int64_t band_doubles = bands ? (int64_t)s->lanes * 256 * (kBandAcc + s->bs_n) : 0;
@@ -1243,7 +1316,7 @@ extern "C" int ss_stream_export(ss_ctx* c, int id, void* buf, int64_t cap, int64
     return SS_OK;
 }
 
-extern "C" int ss_stream_import(ss_ctx* c, const void* buf, int64_t n, int* id) {
+static int import_image(ss_ctx* c, const void* buf, int64_t n, int* id) {
     if (!c || !buf || !id || n < (int64_t)sizeof(ImageHdr)) return fail(c, SS_ERR_ARG, "ss_stream_import: bad argument");
     if (!c->has_model) return fail(c, SS_ERR_STATE, "context was created without weights (audio-only)");
     ImageHdr h;

@@ -180,6 +180,8 @@ _SIGS = {
     "ss_stream_output": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ss_stream_get_output_info": (C.c_int, [_P, C.c_int, C.POINTER(StreamOutputInfo)]),
     "ss_stream_open_channels": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.POINTER(C.c_int)]),
+    "ss_stream_open_source": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.POINTER(C.c_int)]),
+    "ss_stream_output_bytes": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ss_stream_avg_channel": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_stream_region_peaks": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ss_stream_open_bands": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(StreamErase), C.c_int, C.c_int,
@@ -192,6 +194,12 @@ _SIGS = {
     "ss_separation_maps": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P]),
     "ss_separate_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
     "ss_separate_pcm_channels": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P]),
+    "ss_silence_pcm_source": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, C.c_int64]),
+    "ss_separate_pcm_source": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(SeparationParams), _P,
+                                         C.c_int64]),
+    "ss_separate_pcm_channels_source": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64,
+                                                  C.POINTER(SeparationParams), _P, C.c_int64]),
+    "ss_wav_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
     "ss_band_edges": (C.c_int, [_P]),
     "ss_region_bins": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ss_region_bands": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(BandParams), _P, _P]),
@@ -320,6 +328,13 @@ def format_csv_rows(file_path: str, file_name: str, regions, first_id: int = 1) 
 def wav_header_pcm16(sr: int, channels: int, frames: int) -> bytes:
     buf = C.create_string_buffer(44)
     _check(lib().ss_wav_header_pcm16(int(sr), int(channels), int(frames), buf))
+    return buf.raw
+
+
+def wav_header(fmt: int, sr: int, channels: int, frames: int) -> bytes:
+    """The 44-byte RIFF/WAVE header of a file in one of the little-endian encodings 1-6 (ss_wav_header)."""
+    buf = C.create_string_buffer(44)
+    _check(lib().ss_wav_header(int(fmt), int(sr), int(channels), int(frames), buf))
     return buf.raw
 
 
@@ -548,6 +563,37 @@ class Context:
         self._ck(lib().ss_separate_pcm_channels(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions),
                                                 C.byref(p), _ptr(out)))
         return out
+
+    def silence_pcm_source(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int, regions) -> np.ndarray:
+        """silence_pcm in the recording's own encoding (ss_silence_pcm_source): uint8 (frames, channels x bytes per sample), the input's
+        bytes with the frames of the (start_s, end_s) regions replaced by the encoding's zero."""
+        pcm = np.ascontiguousarray(pcm)
+        self._need_bytes(pcm, fmt, channels, frames)
+        out = np.empty((frames, channels * _BPS[fmt]), dtype=np.uint8)
+        self._ck(lib().ss_silence_pcm_source(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions), _ptr(out),
+                                             out.nbytes))
+        return out
+
+    def _separate_source(self, fn, pcm, fmt, sr, channels, frames, regions, fade_s, min_gain, above_fmax, speech_channel):
+        pcm = np.ascontiguousarray(pcm)
+        self._need_bytes(pcm, fmt, channels, frames)
+        p = separation_params(fade_s, min_gain, above_fmax, speech_channel)
+        out = np.empty((frames, channels * _BPS[fmt]), dtype=np.uint8)
+        self._ck(fn(self._h, _ptr(pcm), fmt, sr, channels, frames, _regions(regions), len(regions), C.byref(p), _ptr(out), out.nbytes))
+        return out
+
+    def separate_pcm_source(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int, regions, fade_s: float = 0.01,
+                            min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> np.ndarray:
+        """separate_pcm in the recording's own encoding (ss_separate_pcm_source): uint8 (frames, channels x bytes per sample); the input's
+        bytes outside the regions, the separated audio encoded with the decode's own scale (saturated) inside.  Resets the context."""
+        return self._separate_source(lib().ss_separate_pcm_source, pcm, fmt, sr, channels, frames, regions, fade_s, min_gain, above_fmax,
+                                     speech_channel)
+
+    def separate_pcm_channels_source(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, frames: int, regions, fade_s: float = 0.01,
+                                     min_gain: float = 0.0, above_fmax="mute", speech_channel: int = 1) -> np.ndarray:
+        """separate_pcm_channels in the recording's own encoding (ss_separate_pcm_channels_source)."""
+        return self._separate_source(lib().ss_separate_pcm_channels_source, pcm, fmt, sr, channels, frames, regions, fade_s, min_gain,
+                                     above_fmax, speech_channel)
 
     def separation_maps(self, fid: int, first_bin: int, n_bins: int) -> np.ndarray:
         """Averaged spec-head maps of bins [first_bin, first_bin + n_bins) of file fid: float32 [2, n_bins, 128]."""
@@ -929,6 +975,26 @@ class Context:
         out = np.zeros((n.value, int(channels)), dtype=np.int16)
         if n.value:
             self._ck(lib().ss_stream_output(self._h, int(sid), _ptr(out), n.value, C.byref(first), C.byref(n)))
+        return first.value, out
+
+    def stream_open_source(self, fmt: int, sr: int, channels: int, threshold: float = 0.1, break_s: float = 0.5, erase=None,
+                           each_channel: bool = False) -> int:
+        """A stream with output in its own encoding (ss_stream_open_source): stream_output_bytes after every step.  each_channel as
+        stream_open_channels; erase None: pad_s = min_len_s = 0."""
+        sid = C.c_int(-1)
+        e = _erase(erase)
+        self._ck(lib().ss_stream_open_source(self._h, int(fmt), int(sr), int(channels), float(threshold), float(break_s), C.byref(e),
+                                             int(bool(each_channel)), C.byref(sid)))
+        return sid.value
+
+    def stream_output_bytes(self, sid: int, frame_bytes: int):
+        """The frames the last step of a source-output stream returned -> (first_frame, uint8 array [n, frame_bytes]), frame_bytes =
+        channels x bytes per sample of the stream's encoding."""
+        first, n = C.c_int64(0), C.c_int64(0)
+        self._ck(lib().ss_stream_output_bytes(self._h, int(sid), None, 0, C.byref(first), C.byref(n)))
+        out = np.zeros((n.value, int(frame_bytes)), dtype=np.uint8)
+        if n.value:
+            self._ck(lib().ss_stream_output_bytes(self._h, int(sid), _ptr(out), out.nbytes, C.byref(first), C.byref(n)))
         return first.value, out
 
     def stream_output_info(self, sid: int) -> dict:

@@ -14,6 +14,12 @@ A stream opened with erase= also returns its frames as final 16-bit PCM with the
     with StreamWavWriter("feed.wav", 48000, 2) as w:
         ...; s.push(samples); det.step(); w.write(s.output())      # (first_frame, int16 [n, channels]): contiguous from step to step
 
+encoding="source" keeps the stream's own sample encoding: output() returns the frames as bytes, the input's outside the erased intervals
+(the concatenation equals native.Context.silence_pcm_source of the whole recording), and StreamWavWriter(..., fmt=) writes its header:
+
+    s = det.open(PCM_S24, 48000, 2, erase=dict(pad_s=0.05), encoding="source")
+    with StreamWavWriter("feed.wav", 48000, 2, fmt=PCM_S24) as w: ...; w.write(s.output())   # (first_frame, uint8 [n, 6])
+
 A recording of several channels is detected on its channel mean by default; channel_mode="each" detects every channel alone (what
 native.Context.add_pcm_channels is to add_pcm) and the stream's table is "speech on any channel":
 
@@ -45,7 +51,8 @@ class Stream:
     """One recording of a StreamDetector.  Hashable: step() returns its results keyed by it."""
 
     def __init__(self, det: "StreamDetector", ctx, sid: int, fmt: int, sr: int, channels: int, erase=None, channel_mode: str = "mix",
-                 band_params=None):
+                 band_params=None, encoding: str = "pcm16"):
+        self.encoding = encoding                           # "pcm16": int16 output; "source": bytes in the stream's own encoding
         self.band_params = band_params                     # None: opened without bands; else dict(q_low, q_high, speech_channel, profile)
         self._det, self._ctx, self._sid = det, ctx, sid
         self.format, self.sample_rate, self.channels = fmt, sr, channels
@@ -88,7 +95,10 @@ class Stream:
 
     def output(self):
         """The frames the last step returned: (first_frame, int16 array [n, channels]) -- final, contiguous from step to step, the
-        detected speech zeroed.  Only on a stream opened with erase=."""
+        detected speech zeroed.  Only on a stream opened with erase=.  A stream opened with encoding="source": (first_frame, uint8
+        array [n, channels x bytes per sample]), the frames in the stream's own encoding."""
+        if self.encoding == "source":
+            return self._ctx.stream_output_bytes(self._sid, self.channels * _native._BPS[self.format])
         return self._ctx.stream_output(self._sid, self.channels)
 
     def output_info(self) -> dict:
@@ -130,14 +140,20 @@ class StreamDetector:
         return self._fp32
 
     def open(self, fmt: int, sr: int, channels: int = 1, threshold: float = 0.1, break_s: float = 0.5, erase=None,
-             channel_mode: str = "mix", bands=False) -> Stream:
+             channel_mode: str = "mix", bands=False, encoding: str = "pcm16") -> Stream:
         """erase: None -- detection only; dict(pad_s=, min_len_s=) (either may be left out: 0) -- the stream also returns its frames
         as 16-bit PCM with the detected speech zeroed (Stream.output() after every step).
         channel_mode: "mix" -- detection on the channel mean; "each" -- on every channel alone: the regions and the series step()
         returns are the merged ones ("speech on any channel"), every channel is zeroed over them, Stream.avg(c) / Stream.peaks() give
         the channels' own.
         bands: False -- none; True or dict(q_low=.05, q_high=.95, speech_channel=1, profile=False) -- every region comes with its
-        frequency extent (Stream.bands(), Stream.band_profiles(), the fourth entry of step()'s tuples).  Needs the 0.6 s window step."""
+        frequency extent (Stream.bands(), Stream.band_profiles(), the fourth entry of step()'s tuples).  Needs the 0.6 s window step.
+        encoding: "pcm16" -- the output is 16-bit PCM; "source" -- it stays in the stream's own encoding (a stream with output, erase
+        None meaning pad_s = min_len_s = 0; not together with bands)."""
+        if encoding not in ("pcm16", "source"):
+            raise ValueError(f"encoding must be 'pcm16' or 'source', not {encoding!r}")
+        if encoding == "source" and bands:
+            raise ValueError("band streams have no source-encoding output")
         if channel_mode not in ("mix", "each"):
             raise ValueError(f"channel_mode must be 'mix' or 'each', not {channel_mode!r}")
         bp = None
@@ -153,7 +169,10 @@ class StreamDetector:
         ctx = self._fp32_ctx() if self._switched else self._main
         if erase is not None:
             erase = dict(pad_s=float(erase.get("pad_s", 0.0)), min_len_s=float(erase.get("min_len_s", 0.0)))
-        if bp is not None:
+        if encoding == "source":
+            erase = erase or dict(pad_s=0.0, min_len_s=0.0)
+            sid = ctx.stream_open_source(fmt, sr, channels, threshold, break_s, erase, channel_mode == "each")
+        elif bp is not None:
             sid = ctx.stream_open_bands(fmt, sr, channels, threshold, break_s, erase, False, channel_mode == "each", bp["q_low"], bp["q_high"],
                                         bp["speech_channel"], bp["profile"])
         elif channel_mode == "each":
@@ -162,7 +181,7 @@ class StreamDetector:
             sid = ctx.stream_open(fmt, sr, channels, threshold, break_s)
         else:
             sid = ctx.stream_open_output(fmt, sr, channels, threshold, break_s, erase)
-        s = Stream(self, ctx, sid, fmt, sr, channels, erase, channel_mode, bp)
+        s = Stream(self, ctx, sid, fmt, sr, channels, erase, channel_mode, bp, encoding)
         self._streams.append(s)
         return s
 
@@ -218,17 +237,26 @@ class StreamDetector:
 
 
 class StreamWavWriter:
-    """A 16-bit PCM WAV file that grows with a stream's output: write() appends what a step returned, close() rewrites the 44-byte
-    header (ss_wav_header_pcm16) with the final frame count.
+    """A WAV file that grows with a stream's output: write() appends what a step returned, close() rewrites the 44-byte header with
+    the final frame count.  fmt None: 16-bit PCM (ss_wav_header_pcm16); fmt one of the little-endian encodings 1-6: the output of a
+    stream opened with encoding="source" (ss_wav_header; the AIFF encodings 7-12 have no WAV form and are refused).
 
         with StreamWavWriter(path, 16000, 1) as w:
             ...; det.step(); w.write(s.output())
     """
 
-    def __init__(self, path, sr: int, channels: int):
+    def __init__(self, path, sr: int, channels: int, fmt: int | None = None):
         self.sample_rate, self.channels, self.frames = int(sr), int(channels), 0
+        self.format = None if fmt is None else int(fmt)
+        if self.format is not None and not (_native.PCM_U8 <= self.format <= _native.PCM_F64):
+            raise ValueError(f"a WAV file holds the encodings 1-6, not {fmt!r}")
         self._f = open(path, "wb")
-        self._f.write(_native.wav_header_pcm16(self.sample_rate, self.channels, 0))
+        self._f.write(self._header(0))
+
+    def _header(self, frames: int) -> bytes:
+        if self.format is None:
+            return _native.wav_header_pcm16(self.sample_rate, self.channels, frames)
+        return _native.wav_header(self.format, self.sample_rate, self.channels, frames)
 
     def write(self, output):
         """output: Stream.output()'s pair, or an int16 array [n, channels]; a pair must continue where the file ends."""
@@ -238,7 +266,10 @@ class StreamWavWriter:
                 raise ValueError(f"output starts at frame {first}, the file holds {self.frames}")
         else:
             a = output
-        a = np.ascontiguousarray(a, dtype="<i2").reshape(-1, self.channels)
+        if self.format is None:
+            a = np.ascontiguousarray(a, dtype="<i2").reshape(-1, self.channels)
+        else:
+            a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, self.channels * _native._BPS[self.format])
         self._f.write(a.tobytes())
         self.frames += len(a)
 
@@ -246,7 +277,7 @@ class StreamWavWriter:
         if self._f is None:
             return
         self._f.seek(0)
-        self._f.write(_native.wav_header_pcm16(self.sample_rate, self.channels, self.frames))
+        self._f.write(self._header(self.frames))
         self._f.close()
         self._f = None
 
