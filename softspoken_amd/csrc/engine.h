@@ -8,6 +8,7 @@
 // Not part of the C ABI.
 #pragma once
 #include "../../include/softspoken.h"
+#include "hostdefs.h"
 #include "kernels.h"
 #include "net.h"
 
@@ -16,17 +17,6 @@
 #include <vector>
 
 namespace ss {
-
-// bytes of one sample of enum ss_pcm_format (WAV: little endian; AIFF: big endian, 7..12)
-inline size_t pcm_bytes_per_sample(int format) {
-    switch (format) {
-        case SS_PCM_U8: case SS_PCM_S8: return 1;
-        case SS_PCM_S16: case SS_PCM_S16BE: return 2;
-        case SS_PCM_S24: case SS_PCM_S24BE: return 3;
-        case SS_PCM_F64: case SS_PCM_F64BE: return 8;
-        default: return 4;
-    }
-}
 
 // ---- errors --------------------------------------------------------------------------------------------
 int fail(ss_ctx* c, int code, const std::string& msg);       // records the message (context + calling thread), returns code
@@ -104,15 +94,6 @@ struct Workspace {
     int64_t lo_delta = 0;                                 // f16x2: byte distance from a tensor's high plane to its low plane
     float* feat = nullptr; float* flat = nullptr;         // front-end features; conv_flatten's row-group partial sums
     int flat_groups = 0;                                  // row groups the last FLAT launch wrote per window into `flat`
-};
-
-// Gap merge of runs of bins above the threshold, in bin order (NNDetector.py:131-141, then worker.py:100's shift by the 3 s of padding):
-// a run whose start lies at most brk seconds behind the current region's end extends it, any other run emits the region and opens the
-// next.  bins (optional): first and last bin of every emitted region.  The callers keep their own scans for the runs.
-struct RunMerger {
-    double brk = 0; bool have = false; ss_region cur{0, 0}; int64_t reg0 = 0, reg1 = 0;
-    void add(int64_t first_bin, int64_t last_bin, std::vector<ss_region>& out, std::vector<int64_t>* bins = nullptr);
-    void flush(std::vector<ss_region>& out, std::vector<int64_t>* bins = nullptr);      // emits the current region, if any
 };
 
 struct KStat { std::string name; int64_t launches = 0; double ms = 0, flops = 0, bytes = 0, issued = 0; };
@@ -299,20 +280,11 @@ void free_separation(ss_ctx* c);
 // separate.hip, region bands (include/softspoken.h "region bands")
 int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err);
 void band_edges(double* hz130);
-void region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count);   // rule 1, clamped to [lo, hi)
 // maps == nullptr: the spec head on files fid .. fid + nsig - 1; otherwise the caller's maps of bins first_bin .. first_bin + n_bins - 1
 int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_bin, int64_t n_bins, const ss_region* regions, int64_t n,
                  const ss_band_params* params, ss_region_band* out, double* profile);
 // host.hip
-double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
-bool step_ok(double step_s);                              // a window step ss_set_window_step accepts
-int64_t step_samples(double step_s);                      // floor(22050 step): samples between window starts
-inline double step_bins(double step_s) { return step_s * 256.0 / 3.0; }   // s_b: bins between window starts, before the rounding of a start
 std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);
-// the streaming silencer's erase table (ss_erase_table): the length filter and the padding of one region of the table
-bool erase_ok(const ss_stream_erase* e);                  // NULL, or both parameters finite and >= 0
-inline bool erase_keeps(const ss_region& r, double min_len_s) { return !(r.end - r.start <= min_len_s); }
-inline ss_region erase_padded(const ss_region& r, double pad_s) { return ss_region{r.start - pad_s, r.end + pad_s}; }
 double now_ms();
 
 }  // namespace ss

@@ -6,6 +6,8 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "stream_desc.h"
+
 namespace ss {
 
 // Development switches (tools/, tests of alternate kernel forms): compiled into libsoftspoken_hip_dev.so only (-DSS_DEVBUILD).
@@ -308,30 +310,7 @@ hipError_t launch_region_peaks(const double* avg, const int32_t* count, const in
                                int64_t n_regions, double* peaks, hipStream_t s);
 
 // ---- streaming detection (stream.hip): one launch per step for all streams, a descriptor per stream ----------------------------
-struct StreamCopy { const float* src; float* dst; int64_t n; };                       // src == nullptr: n zeros
-struct StreamDecode { int64_t pcm_off; int64_t frames; float* dst; int32_t format, channels; };
-// outputs [m0, m0 + n) -> out[0 .. n); input sample idx is mono[idx - mono_base] for mono_base <= idx < frames, zero past `frames`
-struct StreamResample { const float* mono; int64_t mono_base, frames; const float* taps; float* out; int64_t m0, n; int32_t L, M, half, pad; };
-// bins [b0, b0 + nb) from the windows [w0, W) whose logits lie back to back at `logits`; results at avg / flags [out_off ..); step: the
-// stream's window step in seconds (window i starts at bin rint(i step / (3 / 256)), as ss_window_start_bin), s_b = step x 256 / 3
-struct StreamAvg { const float* logits; int64_t w0; int32_t W, pad; int64_t b0, nb, out_off; double threshold, step, s_b; };
-// streaming silencer: frames [frame0, frame0 + n) of a stream -> out[out_off ..) as interleaved int16; the first n0 frames are read from
-// seg0, the others from seg1 (native encoding, each aligned to a sample); frames inside ranges (n_ranges disjoint ascending [begin, end)
-// pairs of recording frame numbers) are zero
-struct StreamSilence { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, frame0, n, out_off;
-                       int32_t n_ranges, format, channels, pad; };
-struct StreamCopyBytes { const unsigned char* src; unsigned char* dst; int64_t n; };   // n bytes, any alignment
-// streaming silencer in the stream's own encoding: bytes [byte0, byte0 + n) of the recording -> out[out_off ..) (out_off a multiple of 16);
-// the first n0 bytes are read from seg0, the others from seg1, at any alignment; bytes inside ranges (n_ranges disjoint ascending
-// [begin, end) pairs of recording BYTE numbers) become the zero byte (zero4: it, four times)
-struct StreamSilenceSource { const unsigned char* seg0; const unsigned char* seg1; const int64_t* ranges; int64_t n0, byte0, n, out_off;
-                             int32_t n_ranges; uint32_t zero4; };
-// each-channel streams (ss_stream_open_channels): the pushed frames of a stream of `channels` lanes -> channel c's samples at
-// dst[c stride ..), no mean; pcm_off is a multiple of 16 (the fast form reads a 16-bit stereo frame as one 32-bit word)
-struct StreamDecodeChannels { int64_t pcm_off; int64_t frames; float* dst; int64_t stride; int32_t format, channels; };
-// the merged series of such a stream: its `lanes` lanes' nb new bins lie at avg / flags [in_off + l nb ..); the OR of the flag bits and
-// the fmax of the averages (a NaN passed over) go to avg / flags [out_off ..)
-struct StreamUnion { int64_t in_off, nb, out_off; int32_t lanes, pad; };
+// (the descriptors: stream_desc.h)
 hipError_t launch_stream_silence(const StreamSilence* d, int n, int64_t max_samples, short* out, hipStream_t s);
 hipError_t launch_stream_copy_bytes(const StreamCopyBytes* d, int n, int64_t max_bytes, hipStream_t s);
 hipError_t launch_stream_silence_source(const StreamSilenceSource* d, int n, int64_t max_bytes, unsigned char* out, hipStream_t s);

@@ -127,7 +127,7 @@ def output_limit(sr: int, bins_final: int, pending, pad_s: float, min_len_s: flo
 
 
 def decided_ranges(walk: Walk, sr: int, pad_s: float, min_len_s: float, limit: int):
-    """What a step erases below `limit` (stream.hip step_output): the returned regions, a final current region, P's certain part."""
+    """What a step erases below `limit` (stream_plan.h plan_output): the returned regions, a final current region, P's certain part."""
     rows = list(walk.regions)
     P, D = walk.pending()
     if D is not None:

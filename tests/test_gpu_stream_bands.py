@@ -5,7 +5,9 @@ Everything else a band stream returns is compared with the same stream opened wi
 
 Recordings are 12 s (20 windows, about 1500 bins, 24 tiles); the heads are the crafted `spread` and `mixed` heads of
 tests/separation_ref.py on the session checkpoint's body (the session head's speech map is 0 almost everywhere)."""
+import json
 import math
+import os
 import struct
 
 import numpy as np
@@ -735,3 +737,76 @@ def test_a_window_step_other_than_the_default_is_a_value_error_where_open_is_cal
         StreamDetector(context_factory=lambda p: _NoContext(), precision="fp32", step=0.3).open(native.PCM_S16, 16000, 1, bands=True)
     with pytest.raises(ValueError):
         StreamDetector(context_factory=lambda p: _NoContext(), precision="fp32").open(native.PCM_S16, 16000, 1, bands=dict(q=1))
+
+
+# ---- 10. the structure of a step ------------------------------------------------------------------------------------------------
+# A context whose passes hold four windows: a band lane's windows of one step span several passes, passes are shared by lanes of
+# different streams, and one band stream is stepped before its first push.  What the streams return is the whole-file bytes; what
+# every step launches is held to the table recorded before the step was split into layout, run and commit
+# (tests/golden/stream_step_plan.json, tests/golden/make_stream_step_plan.py).
+STEP_PLAN_SECONDS = 8.0
+STEP_PLAN_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stream_step_plan.json")
+# name: (layout, bands, piece seconds, the round of its first push)
+STEP_PLAN_STREAMS = {"band_each": ("each48", True, 0.5, 0), "plain": ("mono16", False, 1.3, 0), "band_late": ("mix48", True, 0.9, 3)}
+
+
+def step_plan_threshold(native, ctx):
+    fid, n = add_whole(native, ctx, rec("each48", STEP_PLAN_SECONDS), "each48")
+    ctx.run(0.1, 0.5)
+    return float(np.median(np.fmax.reduce(np.asarray([ctx.avg(fid + c)[0] for c in range(n)]), axis=0)))
+
+
+def step_plan_run(native, ctx, thr):
+    """The three streams, every one pushed a piece per round from its first round on, one step per round on a profiling context of
+    chunk 4; -> ({name: (Got, every lane's averages step by step)}, [[[kernel, launches, bytes], ...] per step])."""
+    st = {}
+    for name, (layout, bands, piece, first) in STEP_PLAN_STREAMS.items():
+        sr, ch, each = LAYOUTS[layout]
+        st[name] = dict(sid=open_stream(native, ctx, layout, thr, 0.05, bands, True), at=0, pcm=rec(layout, STEP_PLAN_SECONDS), n=int(piece * sr),
+                        first=first, got=Got(ch if each else 1, ch, bands, True), lane_avg=[[] for _ in range(ch if each else 1)], closed=False)
+    table, rnd = [], 0
+    while not all(s["closed"] for s in st.values()):
+        for s in st.values():
+            if s["closed"] or rnd < s["first"]:
+                continue
+            n = min(s["n"], len(s["pcm"]) - s["at"])
+            ctx.stream_push(s["sid"], s["pcm"][s["at"]:s["at"] + n], frames=n)
+            s["at"] += n
+            if s["at"] == len(s["pcm"]):
+                ctx.stream_close(s["sid"]); s["closed"] = True
+        ctx.reset_stats()
+        ctx.stream_step()
+        table.append([[k["name"], int(k["launches"]), float(k["bytes"])] for k in ctx.kernel_stats()])
+        for s in st.values():
+            s["got"].take(ctx, s["sid"], rnd)
+            for c, lane in enumerate(s["lane_avg"]):
+                lane.append(ctx.stream_avg_channel(s["sid"], c)[0])
+        rnd += 1
+    for s in st.values():
+        assert ctx.stream_info(s["sid"])["finished"] == 1
+        ctx.stream_free(s["sid"])
+    return {name: (s["got"], s["lane_avg"]) for name, s in st.items()}, table
+
+
+def test_step_structure_chunk_4(native, ctxs):
+    ctx = ctxs("spread", "fp32", "chunk4", chunk=4, profile=True)
+    thr = step_plan_threshold(native, ctx)
+    got, table = step_plan_run(native, ctx, thr)
+    maps = [sum(n for name, n, _ in step if name == "stream_map_kernel") for step in table]
+    print("STREAM_STEP_PLAN steps:", len(table), "stream_map_kernel launches per step:", maps)
+    assert max(maps) >= 3                                              # band windows of one step over several passes
+    for name, (layout, bands, _, _) in STEP_PLAN_STREAMS.items():
+        (g, lane_avg), pcm = got[name], rec(layout, STEP_PLAN_SECONDS)
+        fid, n = add_whole(native, ctx, pcm, layout)
+        ctx.run(thr, 0.05)
+        assert g.regs == (ctx.regions_union(fid, n) if n > 1 else ctx.regions(fid)) and len(g.regs) >= 1, name
+        for c in range(n):                                            # the averages of every lane, bit for bit
+            a, i = ctx.avg(fid + c)
+            assert np.array_equal(np.concatenate(g.idx), i) and np.concatenate(lane_avg[c]).tobytes() == a.tobytes(), (name, c)
+        if bands:
+            assert_bytes(g, reference(native, ctx, pcm, layout, g.regs), name)
+    with open(STEP_PLAN_GOLDEN) as f:
+        want = json.load(f)["steps"]
+    assert len(table) == len(want)
+    for k, (a, b) in enumerate(zip(table, want)):
+        assert a == b, (k, a, b)
