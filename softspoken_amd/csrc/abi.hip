@@ -327,7 +327,7 @@ extern "C" int ss_separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, i
     std::string err;
     if ((rc = check_separation_params(params, err))) return fail(c, rc, "ss_separate_pcm: " + err);
     hipSetDevice(c->device);
-    return separate_pcm(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+    return separate_run(c, false, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 extern "C" int ss_separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
@@ -339,7 +339,7 @@ extern "C" int ss_separate_pcm_channels(ss_ctx* c, const void* pcm, int format, 
     std::string err;
     if ((rc = check_separation_params(params, err))) return fail(c, rc, "ss_separate_pcm_channels: " + err);
     hipSetDevice(c->device);
-    return separate_pcm_channels(c, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+    return separate_run(c, ch > 1, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 // the two in the recording's own encoding: the same checks in the same order, then the capacity
@@ -353,7 +353,7 @@ static int separate_source_call(ss_ctx* c, const char* who, bool each, const voi
     std::string err;
     if ((rc = check_separation_params(params, err))) return fail(c, rc, std::string(who) + ": " + err);
     hipSetDevice(c->device);
-    return separate_pcm_source(c, each && ch > 1, pcm, format, sr, ch, frames, regions, n_regions, params, out);
+    return separate_run(c, each && ch > 1, true, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 extern "C" int ss_separate_pcm_source(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,

@@ -4,11 +4,13 @@
 //                 (plan + enqueue / wait), the region scans of an ended run
 //   net.h         the network's graph, stated once: workspace tensors (ss::Act, kActs) and ResBlocks (kBlocks); the arrays below are indexed by it
 //   host.hip      host-only pieces of the path: WAV header walk, window plan, run merger (ss::RunMerger) and regions, CSV text
+//   sep_plan.h    the separation silencer's and the region bands' host plan (no HIP): the small rules host.hip and abi.hip call too
 //   abi.hip       the C ABI (include/softspoken.h): argument checks, arena, getters, measurement
 // Not part of the C ABI.
 #pragma once
 #include "../../include/softspoken.h"
 #include "hostdefs.h"
+#include "sep_plan.h"
 #include "kernels.h"
 #include "net.h"
 
@@ -76,13 +78,6 @@ struct FileRec {
 
 struct StreamSet;                                         // stream.hip: the context's streams and their step buffers
 struct SepState;                                          // separate.hip: the separation silencer's tables and buffers
-
-// separate.hip: ss_separation_plan's result (host only)
-struct SepPlan {
-    int N = 0, hop = 0;
-    int64_t W = 0, n_bins = 0, windows_run = 0;
-    std::vector<ss_separation_range> ranges;
-};
 
 // An activation workspace for `chunk` windows (engine.hip alloc_ws): what one pass of the network writes.  A context has two -- the main
 // one, and the second lane's of a run with several passes.
@@ -233,6 +228,18 @@ int ensure(ss_ctx* c, T** p, size_t* cap, size_t need_elems, bool keep = false) 
     return SS_OK;
 }
 
+// ... that frees itself with its owner (the streams' and the separation's state)
+template <typename T>
+struct DevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) hipFree(p); }
+    int reserve(ss_ctx* c, size_t n) { return ensure(c, &p, &cap, n); }
+    int reserve_bytes(ss_ctx* c, size_t bytes) { return reserve(c, bytes / sizeof(T)); }
+};
+
 // weights.hip
 int build_tables(ss_ctx* c, const Blob& bl);
 int build_model(ss_ctx* c, const Blob& bl);
@@ -263,28 +270,19 @@ int check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64
 int get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps);    // polyphase table of sr_in -> 22 050 Hz (cached)
 // stream.hip
 void free_streams(ss_ctx* c);
-// separate.hip
-int sep_fft_size(int sr);
-int check_separation_params(const ss_separation_params* p, std::string& err);
-ss_separation_params separation_defaults();
-void separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n_regions, SepPlan& pl);
+// separate.hip (sep_fft_size, check_separation_params, separation_defaults, separation_plan, check_band_args: sep_plan.h)
 int separation_maps(ss_ctx* c, int file_id, int64_t first_bin, int64_t n_bins, float* out);
-int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
-                 const ss_separation_params* params, int16_t* out);
-int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                          int64_t n_regions, const ss_separation_params* params, int16_t* out);
-// the two with their output in the recording's own encoding (frames x channels x bytes-per-sample bytes); each: one pass per channel
-int separate_pcm_source(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                        int64_t n_regions, const ss_separation_params* params, void* out);
+// each: every channel's gains from its own passes (ss_separate_pcm_channels, ch > 1); src: the output in the recording's own encoding
+// (frames x channels x bytes-per-sample bytes), otherwise int16
+int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                 int64_t n_regions, const ss_separation_params* params, void* out);
 void free_separation(ss_ctx* c);
 // separate.hip, region bands (include/softspoken.h "region bands")
-int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err);
 void band_edges(double* hz130);
 // maps == nullptr: the spec head on files fid .. fid + nsig - 1; otherwise the caller's maps of bins first_bin .. first_bin + n_bins - 1
 int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_bin, int64_t n_bins, const ss_region* regions, int64_t n,
                  const ss_band_params* params, ss_region_band* out, double* profile);
-// host.hip
-std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);
+// host.hip (and the rules of hostdefs.h)
 double now_ms();
 
 }  // namespace ss

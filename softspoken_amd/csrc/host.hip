@@ -1,5 +1,5 @@
 // Host-only pieces of the path (no device work): RIFF/WAVE header walk, window plan, threshold / run-length / gap-merge, the
-// reference's time strings and CSV text, silencer frame ranges, WAV header writer.  Reference lines are cited per function.
+// reference's time strings and CSV text, rule 1 of the region bands, silencer frame ranges, WAV header writer.  Reference lines are cited per function.
 #include "engine.h"
 
 #include <algorithm>
@@ -156,6 +156,22 @@ double ss::bin_time(int64_t idx) {    // float(f"{idx / (256 / 3):.4f}")  (NNDet
     char buf[64];
     snprintf(buf, sizeof buf, "%.4f", (double)idx / (256.0 / 3.0));
     return strtod(buf, nullptr);
+}
+
+// rule 1 of the region bands (include/softspoken.h "region bands"): the bins whose centres lie in [start, end), clamped to the bins [lo, hi)
+static int64_t band_edge_bin(double x, int64_t lo, int64_t hi) {
+#pragma clang fp contract(off)
+    const double s = (x + 3.0) * 256.0;
+    const double q = s / 3.0;
+    const double v = std::ceil(q - 0.5);
+    if (!(v > (double)lo)) return lo;
+    if (v >= (double)hi) return hi;
+    return (int64_t)v;
+}
+
+void ss::region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count) {
+    first = band_edge_bin(start, lo, hi);
+    count = std::max<int64_t>(0, band_edge_bin(end, lo, hi) - first);
 }
 
 // NNDetector.py:131-141 (gap merge), then worker.py:100 (the 3 s of padding in front leave the times)

@@ -1,6 +1,6 @@
 // Host-only rules and types the units of the library share: sample sizes, the run merger, bin times and window steps, rule 1 of the
-// region bands, the erase table's filter.  No HIP header: engine.h includes this, and so does stream_plan.h, which has to compile
-// without a device toolchain.  Defined in host.hip (region_bins: separate.hip).
+// region bands, the silencer's frame ranges, the erase table's filter.  No HIP header: engine.h includes this, and so do stream_plan.h
+// and sep_plan.h, which have to compile without a device toolchain.  Defined in host.hip.
 #pragma once
 #include "../../include/softspoken.h"
 
@@ -30,6 +30,7 @@ struct RunMerger {
 };
 
 void region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count);   // rule 1, clamped to [lo, hi)
+std::vector<int64_t> silence_ranges(const ss_region* regions, int64_t n, int sr, int64_t frames);   // merged frame ranges [begin, end) of a region table
 double bin_time(int64_t idx);                             // float(f"{idx / (256 / 3):.4f}")
 bool step_ok(double step_s);                              // a window step ss_set_window_step accepts
 int64_t step_samples(double step_s);                      // floor(22050 step): samples between window starts

@@ -1,8 +1,10 @@
 // The separation silencer (include/softspoken.h "separation silencer"): inside the erased intervals, an STFT at the file's native rate
 // whose bins are scaled by a gain from the network's spec head (pytorch_neural_nets.py:125-130,184-185, "env / speech separation";
 // NNDetector.py:84-101 returns it as speech_pred, worker.py:78-79 drops it); outside them, ss_silence_pcm's transcode.
+// Kernels and device runs only: each run asks sep_plan.h (host, no HIP) for its plan, grows its buffers, uploads, launches, downloads.
 //
-//   host   plan: merged intervals (silence_ranges) -> STFT frames -> averaged bins they read -> windows that cover those bins
+//   plan   separation_plan: merged intervals (silence_ranges) -> STFT frames -> averaged bins they read -> windows over those bins;
+//          plan_ranges + plan_maps: merged bins and windows, window slots, run list; plan_synthesis (behind step 1): frames, pieces, chunks
 //   1      spec head over those windows (forward_chunk, passes of ss_set_chunk_windows) -> sep_accumulate_kernel after each pass:
 //          float64 sums per (bin, channel, band) in ascending window order, carried in memory across passes
 //   2      sep_finalize_kernel: sum / count -> float32 maps, band gains G' (logistic of the log-power difference)
@@ -22,38 +24,27 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstring>
+#include <type_traits>
 
 namespace ss {
 
-struct SepFrame { int64_t k; int32_t cb0, cb1; float alpha; int32_t pad; };     // an STFT frame: centre k hop, gain rows cb0 / cb1
-struct SepSeg { int64_t a, b, s0, s1, k0, rec0, out0; };                          // an interval piece: interval [a, b), samples [s0, s1),
-                                                                                  // frames k0.. in records rec0.., first output slot out0
 struct SepBand { int32_t m0, m1; float w0, w1; };                                // STFT bin -> two mel bands and weights (m0 < 0: >= 8 kHz)
 
-struct BandSeg { int32_t cb0, n, out, pad; };         // (region, tile): compact bins cb0 .. cb0 + n - 1 of the piece's maps -> tile sum `out`
-struct BandRegion { int32_t seg0, nseg, n_bins, pad; };   // a region's tile sums seg0 .. seg0 + nseg - 1 (ascending tiles), its bins
-
-struct SepTables { int N = 0; float2* tw = nullptr; float* win = nullptr; SepBand* band = nullptr; };
+struct SepTables { int N = 0; DevBuf<float2> tw; DevBuf<float> win; DevBuf<SepBand> band; };
 
 struct SepState {
     std::map<int, SepTables> tables;                      // per sample rate
-    int32_t* d_cbin = nullptr; size_t cbin_cap = 0;
-    int32_t* d_slot = nullptr; size_t slot_cap = 0;
-    double* d_sum = nullptr; size_t sum_cap = 0;
-    int32_t* d_count = nullptr; size_t count_cap = 0;
-    float* d_map = nullptr; size_t map_cap = 0;
-    float* d_gain = nullptr; size_t gain_cap = 0;
-    SepFrame* d_frames = nullptr; size_t frames_cap = 0;
-    SepSeg* d_segs = nullptr; size_t segs_cap = 0;
-    float2* d_fout = nullptr; size_t fout_cap = 0;
+    DevBuf<int32_t> cbin, slot, count;
+    DevBuf<double> sum;
+    DevBuf<float> map, gain;
+    DevBuf<SepFrame> frames;
+    DevBuf<SepSeg> segs;
+    DevBuf<float2> fout;
     // region bands
-    BandSeg* d_bseg = nullptr; size_t bseg_cap = 0;
-    BandRegion* d_breg = nullptr; size_t breg_cap = 0;
-    double* d_bpart = nullptr; size_t bpart_cap = 0;
-    ss_region_band* d_bout = nullptr; size_t bout_cap = 0;
-    double* d_bprof = nullptr; size_t bprof_cap = 0;
-    double* d_hz = nullptr;
+    DevBuf<BandSeg> bseg;
+    DevBuf<BandRegion> breg;
+    DevBuf<double> bpart, bprof, hz;
+    DevBuf<ss_region_band> bout;
 };
 
 // =========================================================================================================
@@ -296,125 +287,28 @@ __device__ __forceinline__ float sep_blend_sample(const unsigned char* __restric
     return x + w * (p - x);
 }
 
-// The blend over `total` samples x channels, encoded as silence_encode_kernel encodes: lrintf(y * 32767), no clipping.
-__global__ __launch_bounds__(256) void sep_blend_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
-                                                        const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
-                                                        int npairs, const float2* __restrict__ fout, int64_t F, short* __restrict__ out) {
+// The blend over `total` samples x channels, launched (and recorded) as sep_blend_kernel (Out = short): encoded as silence_encode_kernel
+// encodes, lrintf(y * 32767), no clipping -- and as sep_blend_source_kernel (Out = unsigned char): the recording's own encoding (dsp.h
+// encode_sample: the decode's scale, saturated) over a copy of the PCM, whose bytes outside the intervals stay the input's.
+template <typename Out>
+__global__ __launch_bounds__(256) void sep_blend_form_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
+                                                             const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
+                                                             int npairs, const float2* __restrict__ fout, int64_t F, Out* __restrict__ out) {
 #pragma clang fp contract(off)
     const int64_t all = total * channels;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < all; idx += (int64_t)gridDim.x * 256) {
         int64_t at;
         const float y = sep_blend_sample(pcm, format, channels, segs, n_segs, hop, N, npairs, fout, F, idx, at);
-        out[at] = (short)__float2int_rn(y * 32767.0f);
-    }
-}
-
-// The same blend stored in the recording's own encoding (dsp.h encode_sample: the decode's scale, saturated), over a copy of the PCM:
-// the bytes outside the intervals stay the input's.
-__global__ __launch_bounds__(256) void sep_blend_source_kernel(const unsigned char* __restrict__ pcm, int format, int channels,
-                                                               const SepSeg* __restrict__ segs, int n_segs, int64_t total, int hop, int N,
-                                                               int npairs, const float2* __restrict__ fout, int64_t F,
-                                                               unsigned char* __restrict__ out) {
-    const int64_t all = total * channels;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < all; idx += (int64_t)gridDim.x * 256) {
-        int64_t at;
-        const float y = sep_blend_sample(pcm, format, channels, segs, n_segs, hop, N, npairs, fout, F, idx, at);
-        encode_sample(out, format, at, y);
+        if constexpr (std::is_same_v<Out, short>) out[at] = (short)__float2int_rn(y * 32767.0f);
+        else encode_sample(out, format, at, y);
     }
 }
 
 // =========================================================================================================
-// host: plan
+// host: device runs
 // =========================================================================================================
-static int64_t floordiv(int64_t a, int64_t b) { int64_t q = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) --q; return q; }
-static int64_t win_start(int64_t i) { return (512 * i + 5) / 10; }
-
-int sep_fft_size(int sr) {
-    const double l = std::log2((double)sr * 512.0 / 22050.0);
-    const long e = std::lround(l);
-    return 1 << std::min<long>(13, std::max<long>(8, e));
-}
-
-// W and covered bins of a file whose padded signal holds n_padded samples and whose header says duration_s (ss_run's plan)
-static void file_geometry(double duration_s, int64_t n_padded, int64_t& W, int64_t& n_bins) {
-    W = ss_plan_windows(duration_s, nullptr, 0);
-    while (W > 0 && (W - 1) * (int64_t)SS_STEP_SAMPLES + SS_WINDOW_SAMPLES > n_padded) --W;
-    const int64_t nb = (int64_t)std::nearbyint((double)n_padded / 22050.0 * 256.0 / 3.0);
-    n_bins = W > 0 ? std::min(nb, win_start(W - 1) + 256) : 0;
-}
-
-// the two bins around frame k's time k hop / sr (centres (j + 0.5) 3 / 256 - 3 s) and the weight of the second; exact integers:
-// u = (k hop / sr + 3) 256 / 3 - 0.5 = (512 (k hop + 3 sr) - 3 sr) / (6 sr).  Clamped to bins 0 .. n_bins - 1.
-static void frame_bins(int64_t k, int hop, int sr, int64_t n_bins, int64_t& j0, int64_t& j1, double& alpha) {
-    const int64_t num = 512 * (k * hop + 3 * (int64_t)sr) - 3 * (int64_t)sr, den = 6 * (int64_t)sr;
-    j0 = floordiv(num, den);
-    alpha = (double)(num - j0 * den) / (double)den;
-    if (j0 < 0) { j0 = j1 = 0; alpha = 0.0; }
-    else if (j0 >= n_bins - 1) { j0 = j1 = n_bins - 1; alpha = 0.0; }
-    else j1 = j0 + 1;
-}
-
-// windows (inclusive) that cover any bin of [b0, b1]
-static void covering_windows(int64_t b0, int64_t b1, int64_t W, int64_t& w0, int64_t& w1) {
-    w0 = std::max<int64_t>(0, (int64_t)((double)(b0 - 255) / 51.2) - 2);
-    while (w0 < W - 1 && win_start(w0) + 255 < b0) ++w0;
-    w1 = std::min<int64_t>(W - 1, (int64_t)((double)b1 / 51.2) + 2);
-    while (w1 > 0 && win_start(w1) > b1) --w1;
-}
-
-int check_separation_params(const ss_separation_params* p, std::string& err) {
-    if (!p) return SS_OK;
-    if (p->speech_channel != 0 && p->speech_channel != 1) { err = "speech_channel must be 0 or 1"; return SS_ERR_ARG; }
-    if (!(p->fade_s >= 0.0) || !std::isfinite(p->fade_s)) { err = "fade_s must be a finite value >= 0"; return SS_ERR_ARG; }
-    if (!(p->min_gain >= 0.0 && p->min_gain <= 1.0)) { err = "min_gain must lie in [0, 1]"; return SS_ERR_ARG; }
-    if (p->above_fmax != SS_ABOVE_FMAX_MUTE && p->above_fmax != SS_ABOVE_FMAX_KEEP) { err = "above_fmax must be SS_ABOVE_FMAX_MUTE or _KEEP"; return SS_ERR_ARG; }
-    return SS_OK;
-}
-
-ss_separation_params separation_defaults() { return ss_separation_params{0.01, 0.0, SS_ABOVE_FMAX_MUTE, 1}; }
-
-void separation_plan(int sr, int64_t frames, const ss_region* regions, int64_t n_regions, SepPlan& pl) {
-    pl.N = sep_fft_size(sr); pl.hop = pl.N / 4;
-    const int64_t n_padded = ss_resampled_length(frames, sr) + 2 * (int64_t)SS_WINDOW_SAMPLES;
-    file_geometry((double)frames / (double)sr, n_padded, pl.W, pl.n_bins);
-    pl.ranges.clear(); pl.windows_run = 0;
-    const std::vector<int64_t> r = silence_ranges(regions, n_regions, sr, frames);
-    int64_t last_win = -1;
-    for (size_t i = 0; i + 1 < r.size(); i += 2) {
-        ss_separation_range g{};
-        g.frame_begin = r[i]; g.frame_end = r[i + 1];
-        g.stft_first = floordiv(g.frame_begin - pl.N / 2, pl.hop) + 1;
-        g.stft_last = -floordiv(-(g.frame_end + pl.N / 2), pl.hop) - 1;
-        int64_t a0, a1, b0, b1; double al;
-        frame_bins(g.stft_first, pl.hop, sr, pl.n_bins, a0, a1, al);
-        frame_bins(g.stft_last, pl.hop, sr, pl.n_bins, b0, b1, al);
-        g.bin_first = a0; g.bin_last = b1;
-        covering_windows(g.bin_first, g.bin_last, pl.W, g.win_first, g.win_last);
-        const int64_t from = std::max(g.win_first, last_win + 1);
-        if (g.win_last >= from) pl.windows_run += g.win_last - from + 1;
-        last_win = std::max(last_win, g.win_last);
-        pl.ranges.push_back(g);
-    }
-}
-
-// =========================================================================================================
-// host: device work
-// =========================================================================================================
-static SepState& sep_state(ss_ctx* c) {
-    if (!c->sep) c->sep = new SepState();
-    return *c->sep;
-}
-
-void free_separation(ss_ctx* c) {
-    if (!c->sep) return;
-    SepState& s = *c->sep;
-    for (auto& kv : s.tables) { hipFree(kv.second.tw); hipFree(kv.second.win); hipFree(kv.second.band); }
-    void* p[] = {s.d_cbin, s.d_slot, s.d_sum, s.d_count, s.d_map, s.d_gain, s.d_frames, s.d_segs, s.d_fout,
-                 s.d_bseg, s.d_breg, s.d_bpart, s.d_bout, s.d_bprof, s.d_hz};
-    for (void* q : p) if (q) hipFree(q);
-    delete c->sep;
-    c->sep = nullptr;
-}
+static SepState& sep_state(ss_ctx* c) { return c->sep ? *c->sep : *(c->sep = new SepState()); }
+void free_separation(ss_ctx* c) { delete c->sep; c->sep = nullptr; }      // (every buffer of SepState frees itself)
 
 // HTK mel points of the front-end's filterbank recipe (weights.hip build_tables: torchaudio's, in float32)
 static std::vector<double> mel_points() {
@@ -429,9 +323,9 @@ static std::vector<double> mel_points() {
 }
 
 static int sep_tables(ss_ctx* c, int sr, SepTables** out) {
-    SepState& st = sep_state(c);
-    auto it = st.tables.find(sr);
-    if (it != st.tables.end()) { *out = &it->second; return SS_OK; }
+    SepTables& tb = sep_state(c).tables[sr];
+    *out = &tb;
+    if (tb.N) return SS_OK;                                       // (N is set behind the last upload)
     const int N = sep_fft_size(sr);
     const double PI = 3.14159265358979323846;
     std::vector<float2> tw(N);
@@ -457,51 +351,40 @@ static int sep_tables(ss_ctx* c, int sr, SepTables** out) {
         }
         band[q] = b;
     }
-    SepTables tb; tb.N = N;
-    HIPCHK(c, hipMalloc((void**)&tb.tw, N * sizeof(float2)));
-    HIPCHK(c, hipMalloc((void**)&tb.win, N * sizeof(float)));
-    HIPCHK(c, hipMalloc((void**)&tb.band, band.size() * sizeof(SepBand)));
-    HIPCHK(c, hipMemcpy(tb.tw, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.win, win.data(), N * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.band, band.data(), band.size() * sizeof(SepBand), hipMemcpyHostToDevice));
-    *out = &(st.tables[sr] = tb);
+    int rc;
+    if ((rc = tb.tw.reserve(c, N)) || (rc = tb.win.reserve(c, N)) || (rc = tb.band.reserve(c, band.size()))) return rc;
+    HIPCHK(c, hipMemcpy(tb.tw.p, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.win.p, win.data(), N * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.band.p, band.data(), band.size() * sizeof(SepBand), hipMemcpyHostToDevice));
+    tb.N = N;
     return SS_OK;
 }
 
 // Step 1 (+ 2): the spec head over the windows win_ranges (merged, ascending) of file fid, averaged over the bins bin_ranges (merged,
-// ascending) -> st.d_map [2][ncb][128]; with gains (params non-null): st.d_gain [ncb][128].  Returns SS_ERR_RANGE when an f16x2 pass
+// ascending) -> st.map [2][ncb][128]; with gains (params non-null): st.gain [ncb][128].  Returns SS_ERR_RANGE when an f16x2 pass
 // left the f16 range.  nsig > 1 (ss_separate_pcm_channels): the same for each of the files fid .. fid + nsig - 1, whose windows follow
-// one another in one run list -- a pass ends where the chunk is full, not where a signal ends -- -> d_map [nsig][2][ncb][128],
-// d_gain [nsig][ncb][128].
-static int sep_run_maps(ss_ctx* c, int fid, int nsig, int64_t W, const std::vector<std::pair<int64_t, int64_t>>& bin_ranges,
-                        const std::vector<std::pair<int64_t, int64_t>>& win_ranges, const ss_separation_params* params, int64_t& ncb_out) {
+// one another in one run list -- a pass ends where the chunk is full, not where a signal ends -- -> map [nsig][2][ncb][128],
+// gain [nsig][ncb][128].
+static int sep_run_maps(ss_ctx* c, int fid, int nsig, int64_t W, const Ranges& bin_ranges, const Ranges& win_ranges,
+                        const ss_separation_params* params, int64_t& ncb_out) {
     SepState& st = sep_state(c);
-    std::vector<int32_t> cbin, slot((size_t)W, -1);
-    for (auto& r : bin_ranges) for (int64_t j = r.first; j <= r.second; ++j) cbin.push_back((int32_t)j);
-    std::vector<int64_t> off;
-    for (int s = 0; s < nsig; ++s) {
-        const FileRec& f = c->files[fid + s];
-        int32_t t = 0;
-        for (auto& r : win_ranges)
-            for (int64_t i = r.first; i <= r.second; ++i) { slot[i] = t++; off.push_back(f.off + i * SS_STEP_SAMPLES); }
-    }
-    if (off.size() > (size_t)INT32_MAX) return fail(c, SS_ERR_ARG, "separation: too many windows");
-    const int ncb = (int)cbin.size(), nw_all = (int)off.size(), nw = nw_all / nsig;
+    std::vector<int64_t> sig_off;
+    for (int s = 0; s < nsig; ++s) sig_off.push_back(c->files[fid + s].off);
+    MapsPlan mp;
+    if (!plan_maps(bin_ranges, win_ranges, W, nsig, sig_off.data(), mp)) return fail(c, SS_ERR_ARG, "separation: too many windows");
+    const int ncb = mp.ncb, nw = mp.nw, nw_all = (int)mp.off.size();
     ncb_out = ncb;
     if (ncb == 0 || nw == 0) return SS_OK;
     const size_t ns = (size_t)nsig;
     int rc;
-    if ((rc = ensure(c, &st.d_cbin, &st.cbin_cap, (size_t)ncb))) return rc;
-    if ((rc = ensure(c, &st.d_slot, &st.slot_cap, (size_t)W))) return rc;
-    if ((rc = ensure(c, &st.d_sum, &st.sum_cap, ns * ncb * 256))) return rc;
-    if ((rc = ensure(c, &st.d_count, &st.count_cap, ns * ncb))) return rc;
-    if ((rc = ensure(c, &st.d_map, &st.map_cap, ns * ncb * 256))) return rc;
-    if (params && (rc = ensure(c, &st.d_gain, &st.gain_cap, ns * ncb * 128))) return rc;
-    HIPCHK(c, hipMemcpyAsync(st.d_cbin, cbin.data(), (size_t)ncb * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.d_slot, slot.data(), (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(st.d_sum, 0, ns * ncb * 256 * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(st.d_count, 0, ns * ncb * 4, c->stream));
-    if ((rc = upload_winoff(c, off))) return rc;                  // (synchronises: cbin, slot and off are free again)
+    if ((rc = st.cbin.reserve(c, (size_t)ncb)) || (rc = st.slot.reserve(c, (size_t)W)) || (rc = st.sum.reserve(c, ns * ncb * 256)) ||
+        (rc = st.count.reserve(c, ns * ncb)) || (rc = st.map.reserve(c, ns * ncb * 256)) || (params && (rc = st.gain.reserve(c, ns * ncb * 128))))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(st.cbin.p, mp.cbin.data(), (size_t)ncb * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.slot.p, mp.slot.data(), (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.sum.p, 0, ns * ncb * 256 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.count.p, 0, ns * ncb * 4, c->stream));
+    if ((rc = upload_winoff(c, mp.off))) return rc;               // (synchronises: the plan's vectors are free again)
     const int ch = std::min(nw_all, c->chunk);
     if ((rc = ensure_workspace(c, ch))) return rc;
     if ((rc = ensure(c, &c->d_logits, &c->logits_cap, (size_t)ch * 256))) return rc;
@@ -513,15 +396,15 @@ static int sep_run_maps(ss_ctx* c, int fid, int nsig, int64_t W, const std::vect
         if ((rc = forward_chunk(c, c->ws[0], c->stream, c->d_arena, c->d_winoff + p0, m, c->d_logits, c->d_spec))) return rc;
         ScopedLaunch sl(c, c->stream, "sep_accumulate_kernel", 256.0 * ncb * 6 * nsig, (double)ncb * 256 * 16 * nsig);
         hipLaunchKernelGGL(sep_accumulate_kernel, dim3((unsigned)((ncb + 255) / 256), 256, (unsigned)nsig), dim3(256), 0, c->stream, c->d_spec, p0, m,
-                           st.d_slot, (int)W, nw, st.d_cbin, ncb, st.d_sum, st.d_count);
+                           st.slot.p, (int)W, nw, st.cbin.p, ncb, st.sum.p, st.count.p);
         HIPCHK(c, hipGetLastError());
     }
     {
         const int sp = params ? params->speech_channel : 1;
         const double mg = params ? params->min_gain : 0.0;
         ScopedLaunch sl(c, c->stream, "sep_finalize_kernel", 0.0, (double)ncb * 128 * (16 + 8 + (params ? 4 : 0)) * nsig);
-        hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256), (unsigned)nsig), dim3(256), 0, c->stream, st.d_sum,
-                           st.d_count, ncb, st.d_map, params ? st.d_gain : nullptr, sp, mg);
+        hipLaunchKernelGGL(sep_finalize_kernel, dim3((unsigned)((ncb * 128 + 255) / 256), (unsigned)nsig), dim3(256), 0, c->stream, st.sum.p,
+                           st.count.p, ncb, st.map.p, params ? st.gain.p : nullptr, sp, mg);
         HIPCHK(c, hipGetLastError());
     }
     if (c->d_range_flag) {
@@ -544,42 +427,30 @@ int separation_maps(ss_ctx* c, int fid, int64_t first_bin, int64_t n_bins, float
     covering_windows(first_bin, first_bin + n_bins - 1, W, w0, w1);
     int rc = sep_run_maps(c, fid, 1, W, {{first_bin, first_bin + n_bins - 1}}, {{w0, w1}}, nullptr, ncb);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, sep_state(c).d_map, (size_t)n_bins * 256 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, sep_state(c).map.p, (size_t)n_bins * 256 * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
 
-// each: sep_stft_each_kernel<N> with the gain tables gain + c gain_cs; otherwise sep_stft_kernel<N> with the one table
-template <int N>
-static hipError_t launch_sep_stft(bool each, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
+// The STFT launch of FFT size N = 256 << i, from a table of the twelve instantiations.  each: sep_stft_each_kernel<N> with the gain
+// tables gain + c gain_cs; otherwise sep_stft_kernel<N> with the one table.
+struct SepStftForm { decltype(&sep_stft_form_kernel<256, false>) kernel[2]; int items, pitch; };
+template <int N> static constexpr SepStftForm sep_stft_form() { return {{sep_stft_form_kernel<N, false>, sep_stft_form_kernel<N, true>}, SepGeomT<N>::ITEMS, SepGeomT<N>::PITCH}; }
+static hipError_t launch_sep_stft(int N, bool each, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr, int hop,
                                   const float* gain, size_t gain_cs, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
-    using G = SepGeomT<N>;
-    const size_t lds = (size_t)G::ITEMS * (G::PITCH * sizeof(float2) + (each ? 256 : 128) * sizeof(float));
-    static std::atomic<uint64_t> attr_done{0}, attr_done_each{0};
-    const dim3 grid((unsigned)((n_fr + G::ITEMS - 1) / G::ITEMS), (unsigned)((channels + 1) / 2));
-    if (each) {
-        if (hipError_t e = allow_full_lds((const void*)sep_stft_form_kernel<N, true>, attr_done_each)) return e;
-        hipLaunchKernelGGL((sep_stft_form_kernel<N, true>), grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr,
-                           hop, gain, tb.band, tb.tw, tb.win, gain_hi, out, gain_cs);
-        return hipGetLastError();
-    }
-    if (hipError_t e = allow_full_lds((const void*)sep_stft_form_kernel<N, false>, attr_done)) return e;
-    hipLaunchKernelGGL((sep_stft_form_kernel<N, false>), grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr,
-                       hop, gain, tb.band, tb.tw, tb.win, gain_hi, out, (size_t)0);
+    static const SepStftForm forms[6] = {sep_stft_form<256>(), sep_stft_form<512>(), sep_stft_form<1024>(),
+                                         sep_stft_form<2048>(), sep_stft_form<4096>(), sep_stft_form<8192>()};
+    static std::atomic<uint64_t> attr_done[6][2];                 // (per device: kernels.h allow_full_lds), one per kernel
+    int i = 0;
+    while (i < 6 && (256 << i) != N) ++i;
+    if (i == 6) return hipErrorInvalidValue;
+    const SepStftForm& f = forms[i];
+    const size_t lds = (size_t)f.items * (f.pitch * sizeof(float2) + (each ? 256 : 128) * sizeof(float));
+    const dim3 grid((unsigned)((n_fr + f.items - 1) / f.items), (unsigned)((channels + 1) / 2));
+    if (hipError_t e = allow_full_lds((const void*)f.kernel[each], attr_done[i][each])) return e;
+    hipLaunchKernelGGL(f.kernel[each], grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr, hop, gain,
+                       tb.band.p, tb.tw.p, tb.win.p, gain_hi, out, each ? gain_cs : (size_t)0);
     return hipGetLastError();
-}
-
-static hipError_t launch_sep_stft_n(int N, bool each, const void* pcm, int format, int channels, int64_t frames, const SepFrame* fr, int n_fr,
-                                    int hop, const float* gain, size_t gain_cs, const SepTables& tb, float gain_hi, float2* out, hipStream_t s) {
-    switch (N) {
-        case 256: return launch_sep_stft<256>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        case 512: return launch_sep_stft<512>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        case 1024: return launch_sep_stft<1024>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        case 2048: return launch_sep_stft<2048>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        case 4096: return launch_sep_stft<4096>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        case 8192: return launch_sep_stft<8192>(each, pcm, format, channels, frames, fr, n_fr, hop, gain, gain_cs, tb, gain_hi, out, s);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes of resynthesised frames held at once (pieces / chunks)
@@ -587,8 +458,8 @@ static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes o
 // each (ss_separate_pcm_channels, ch > 1): the signals are the channels alone, every channel's STFT gets the gains of its own maps
 // src: the output in the recording's own encoding (out: frames x ch x bytes-per-sample bytes) -- a device copy of the PCM in place of
 // the transcode, sep_blend_source_kernel in place of sep_blend_kernel; otherwise out is int16
-static int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                        int64_t n_regions, const ss_separation_params* params, void* out) {
+int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
+                 int64_t n_regions, const ss_separation_params* params, void* out) {
     const ss_separation_params prm = params ? *params : separation_defaults();
     SepPlan pl;
     separation_plan(sr, frames, regions, n_regions, pl);
@@ -608,116 +479,61 @@ static int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int for
         ScopedLaunch sl(c, c->stream, "sep_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
         HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, nullptr, 0, c->d_sil_out, c->stream));
     }
+    SynthPlan sp;                                                 // (its frames and segments are uploaded from: alive until the last synchronise)
     if (!pl.ranges.empty()) {
+        const int N = pl.N, hop = pl.hop, npairs = (ch + 1) / 2;
         // steps 1 + 2 over the merged bin and window ranges
-        std::vector<std::pair<int64_t, int64_t>> br, wr;
-        std::vector<int64_t> cbase;                               // compact index of each interval's first bin
-        int64_t ncb_run = 0;
-        for (const auto& g : pl.ranges) {
-            if (!br.empty() && g.bin_first <= br.back().second + 1) {
-                const int64_t at = ncb_run - (br.back().second - br.back().first + 1);
-                cbase.push_back(at + (g.bin_first - br.back().first));
-                if (g.bin_last > br.back().second) { ncb_run += g.bin_last - br.back().second; br.back().second = g.bin_last; }
-            } else {
-                cbase.push_back(ncb_run);
-                br.emplace_back(g.bin_first, g.bin_last);
-                ncb_run += g.bin_last - g.bin_first + 1;
-            }
-            if (!wr.empty() && g.win_first <= wr.back().second + 1) wr.back().second = std::max(wr.back().second, g.win_last);
-            else wr.emplace_back(g.win_first, g.win_last);
-        }
+        const SepRanges rg = plan_ranges(pl);
         int64_t ncb = 0;
-        if ((rc = sep_run_maps(c, fid, each ? ch : 1, pl.W, br, wr, &prm, ncb))) return rc;
-        // step 3 + 4: pieces of at most `piece` samples, chunks of at most `budget` frames
+        if ((rc = sep_run_maps(c, fid, each ? ch : 1, pl.W, rg.br, rg.wr, &prm, ncb))) return rc;
+        // step 3 + 4, chunk by chunk of the frame buffer; the frames are planned here, behind the launches of the model passes
         SepTables* tb = nullptr;
         if ((rc = sep_tables(c, sr, &tb))) return rc;
-        const int N = pl.N, hop = pl.hop, npairs = (ch + 1) / 2;
+        int64_t budget = (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2)));
 #ifdef SS_DEVBUILD      // ss_debug_set_separation_budget: the tests move the piece and chunk cuts through short recordings
-        const int64_t budget = std::max<int64_t>(16, c->sep_budget > 0 ? c->sep_budget : (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2))));
-#else
-        const int64_t budget = std::max<int64_t>(16, (int64_t)(kSepFrameBytes / ((size_t)npairs * N * sizeof(float2))));
+        if (c->sep_budget > 0) budget = c->sep_budget;
 #endif
-        const int64_t piece = (budget - 8) * hop;
-        std::vector<SepFrame> fr;
-        std::vector<SepSeg> sg;
-        struct Chunk { size_t seg0, nseg, rec0, nrec; int64_t total; };
-        std::vector<Chunk> chunks;
-        for (size_t r = 0; r < pl.ranges.size(); ++r) {
-            const auto& g = pl.ranges[r];
-            for (int64_t s0 = g.frame_begin; s0 < g.frame_end; s0 += piece) {
-                const int64_t s1 = std::min(g.frame_end, s0 + piece);
-                const int64_t k0 = floordiv(s0 - N / 2, hop) + 1, k1 = -floordiv(-(s1 + N / 2), hop) - 1;
-                if (chunks.empty() || (int64_t)(fr.size() - chunks.back().rec0) + (k1 - k0 + 1) > budget)
-                    chunks.push_back(Chunk{sg.size(), 0, fr.size(), 0, 0});
-                Chunk& ck = chunks.back();
-                sg.push_back(SepSeg{g.frame_begin, g.frame_end, s0, s1, k0, (int64_t)(fr.size() - ck.rec0), ck.total});
-                for (int64_t k = k0; k <= k1; ++k) {
-                    int64_t j0, j1; double al;
-                    frame_bins(k, hop, sr, pl.n_bins, j0, j1, al);
-                    fr.push_back(SepFrame{k, (int32_t)(cbase[r] + (j0 - g.bin_first)), (int32_t)(cbase[r] + (j1 - g.bin_first)), (float)al, 0});
-                }
-                ck.nseg++; ck.nrec = fr.size() - ck.rec0; ck.total += s1 - s0;
-            }
-        }
-        if ((rc = ensure(c, &st.d_frames, &st.frames_cap, fr.size()))) return rc;
-        if ((rc = ensure(c, &st.d_segs, &st.segs_cap, sg.size()))) return rc;
-        size_t max_rec = 0;
-        for (const Chunk& ck : chunks) max_rec = std::max(max_rec, ck.nrec);
-        if ((rc = ensure(c, &st.d_fout, &st.fout_cap, max_rec * npairs * N))) return rc;
-        HIPCHK(c, hipMemcpyAsync(st.d_frames, fr.data(), fr.size() * sizeof(SepFrame), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(st.d_segs, sg.data(), sg.size() * sizeof(SepSeg), hipMemcpyHostToDevice, c->stream));
+        sp = plan_synthesis(pl, rg.cbase, sr, ch, std::max<int64_t>(16, budget));
+        if ((rc = st.frames.reserve(c, sp.fr.size())) || (rc = st.segs.reserve(c, sp.sg.size())) || (rc = st.fout.reserve(c, sp.fout_need))) return rc;
+        HIPCHK(c, hipMemcpyAsync(st.frames.p, sp.fr.data(), sp.fr.size() * sizeof(SepFrame), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.segs.p, sp.sg.data(), sp.sg.size() * sizeof(SepSeg), hipMemcpyHostToDevice, c->stream));
         const float gain_hi = prm.above_fmax == SS_ABOVE_FMAX_KEEP ? 1.0f : (float)prm.min_gain;
         const int64_t F = (int64_t)std::nearbyint(prm.fade_s * sr);
         const std::string stft_name = (each ? "sep_stft_each_kernel<" : "sep_stft_kernel<") + std::to_string(N) + ">";
-        for (const Chunk& ck : chunks) {
+        for (const SepChunk& ck : sp.chunks) {
             {
                 const double lg = std::log2((double)N);
                 ScopedLaunch sl(c, c->stream, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
                                 (double)ck.nrec * npairs * N * (2.0 * pcm_bytes_per_sample(format) + 8.0));
-                HIPCHK(c, launch_sep_stft_n(N, each, c->d_pcm, format, ch, frames, st.d_frames + ck.rec0, (int)ck.nrec, hop, st.d_gain,
-                                            (size_t)ncb * 128, *tb, gain_hi, st.d_fout, c->stream));
+                HIPCHK(c, launch_sep_stft(N, each, c->d_pcm, format, ch, frames, st.frames.p + ck.rec0, (int)ck.nrec, hop, st.gain.p,
+                                            (size_t)ncb * 128, *tb, gain_hi, st.fout.p, c->stream));
             }
             const int64_t all = ck.total * ch;
             const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
             if (src) {
                 ScopedLaunch sl(c, c->stream, "sep_blend_source_kernel", 0.0, (double)all * (16.0 + 2.0 * pcm_bytes_per_sample(format)));
-                hipLaunchKernelGGL(sep_blend_source_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
-                                   st.d_segs + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_src_out);
+                hipLaunchKernelGGL(sep_blend_form_kernel<unsigned char>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
+                                   st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_src_out);
                 HIPCHK(c, hipGetLastError());
                 continue;
             }
             ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
-            hipLaunchKernelGGL(sep_blend_kernel, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch, st.d_segs + ck.seg0,
-                               (int)ck.nseg, ck.total, hop, N, npairs, st.d_fout, F, c->d_sil_out);
+            hipLaunchKernelGGL(sep_blend_form_kernel<short>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
+                               st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_sil_out);
             HIPCHK(c, hipGetLastError());
         }
     }
     if (src) HIPCHK(c, hipMemcpyAsync(out, c->d_src_out, pcm_bytes, hipMemcpyDeviceToHost, c->stream));
     else HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                   // fr / sg and the caller's buffers are free again
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // the plan and the caller's buffers are free again
     return SS_OK;
-}
-
-int separate_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions, int64_t n_regions,
-                 const ss_separation_params* params, int16_t* out) {
-    return separate_run(c, false, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
-}
-
-int separate_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                          int64_t n_regions, const ss_separation_params* params, int16_t* out) {
-    return separate_run(c, ch > 1, false, pcm, format, sr, ch, frames, regions, n_regions, params, out);
-}
-
-int separate_pcm_source(ss_ctx* c, bool each, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
-                        int64_t n_regions, const ss_separation_params* params, void* out) {
-    return separate_run(c, each, true, pcm, format, sr, ch, frames, regions, n_regions, params, out);
 }
 
 // =========================================================================================================
 // region bands (include/softspoken.h "region bands"): the maps of step 1 reduced on the device to each region's band bounds
 //
-//   host   rule 1 per region -> the disjoint union of the regions' bin ranges (sep_run_maps' bin_ranges), cut at absolute tile
-//          boundaries into pieces of at most kBandsPieceBins bins -> segments (region, tile) over the piece that holds the tile
+//   plan   (sep_plan.h plan_bands) rule 1 per region -> the disjoint union of the regions' bin ranges (sep_run_maps' bin_ranges), cut at
+//          absolute tile boundaries into pieces of at most kBandsPieceBins bins -> segments (region, tile) over the piece that holds the tile
 //   per piece   sep_run_maps -> d_map [nsig][2][ncb][128];  band_profile_kernel: one tile sum [256] per (segment, signal)
 //   at the end  band_bounds_kernel: per (region, signal) the tile sums added in ascending tile order -> E, C, the bounds
 // =========================================================================================================
@@ -758,37 +574,6 @@ void band_edges(double* hz130) {
     for (int i = 0; i < 130; ++i) hz130[i] = (double)f[i];
 }
 
-// rule 1: the bins whose centres lie in [start, end), clamped to the bins [lo, hi)
-static int64_t band_edge_bin(double x, int64_t lo, int64_t hi) {
-#pragma clang fp contract(off)
-    const double s = (x + 3.0) * 256.0;
-    const double q = s / 3.0;
-    const double v = std::ceil(q - 0.5);
-    if (!(v > (double)lo)) return lo;
-    if (v >= (double)hi) return hi;
-    return (int64_t)v;
-}
-
-void region_bins(double start, double end, int64_t lo, int64_t hi, int64_t& first, int64_t& count) {
-    first = band_edge_bin(start, lo, hi);
-    count = std::max<int64_t>(0, band_edge_bin(end, lo, hi) - first);
-}
-
-int check_band_args(const ss_region* regions, int64_t n, const ss_band_params* p, std::string& err) {
-    if (n < 0 || (n > 0 && !regions)) { err = "bad region table"; return SS_ERR_ARG; }
-    if (n > (int64_t)1 << 24) { err = "too many regions"; return SS_ERR_ARG; }
-    if (p) {
-        if (!(p->q_low > 0.0 && p->q_low < p->q_high && p->q_high <= 1.0)) { err = "need 0 < q_low < q_high <= 1"; return SS_ERR_ARG; }
-        if (p->speech_channel != 0 && p->speech_channel != 1) { err = "speech_channel must be 0 or 1"; return SS_ERR_ARG; }
-    }
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(regions[i].start) || !std::isfinite(regions[i].end) || regions[i].end < regions[i].start) {
-            err = "region " + std::to_string(i) + " is not finite or ends before it starts";
-            return SS_ERR_ARG;
-        }
-    return SS_OK;
-}
-
 int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_bin, int64_t n_bins, const ss_region* regions, int64_t n,
                  const ss_band_params* params, ss_region_band* out, double* profile) {
     if (n == 0) return SS_OK;
@@ -803,118 +588,49 @@ int region_bands(ss_ctx* c, const float* maps, int fid, int nsig, int64_t first_
         file_geometry(f.duration, f.n_padded, W, hi);
         lo = 0;
     }
-    // rule 1, then the disjoint union of the non-empty ranges
-    std::vector<std::pair<int64_t, int64_t>> rb((size_t)n), un;       // [first, end) per region; union as inclusive pairs
-    for (int64_t i = 0; i < n; ++i) {
-        int64_t b0, cnt;
-        region_bins(regions[i].start, regions[i].end, lo, hi, b0, cnt);
-        rb[i] = {b0, b0 + cnt};
-        if (cnt > 0) un.emplace_back(b0, b0 + cnt - 1);
-    }
-    std::sort(un.begin(), un.end());
-    size_t nu = 0;
-    for (size_t i = 0; i < un.size(); ++i) {
-        if (nu && un[i].first <= un[nu - 1].second + 1) un[nu - 1].second = std::max(un[nu - 1].second, un[i].second);
-        else un[nu++] = un[i];
-    }
-    un.resize(nu);
-    // tile chunks of the union, gathered into pieces.  Caller's maps: one piece, compact bin = bin - first_bin.
-    struct Chunk { int64_t b0, b1; int piece; int64_t cb0; };       // bins [b0, b1) of one tile, at compact bin cb0 of its piece
-    struct Piece { std::vector<std::pair<int64_t, int64_t>> br; int64_t ncb = 0; size_t seg0 = 0, nseg = 0; };
-    std::vector<Chunk> chunks;
-    std::vector<Piece> pieces;
-    if (maps) {
-        pieces.emplace_back();
-        pieces[0].ncb = n_bins;
-        chunks.push_back(Chunk{lo, hi, 0, 0});
-    } else {
-        int64_t budget = kBandsPieceBins;
+    int64_t budget = kBandsPieceBins;
 #ifdef SS_DEVBUILD      // ss_debug_set_bands_budget: the tests move the cuts through a short recording
-        if (c->bands_budget > 0) budget = std::max<int64_t>(64, c->bands_budget);
+    if (c->bands_budget > 0) budget = std::max<int64_t>(64, c->bands_budget);
 #endif
-        for (const auto& u : un)
-            for (int64_t b = u.first; b <= u.second;) {
-                const int64_t e = std::min(u.second + 1, ((b >> 6) + 1) << 6);
-                if (pieces.empty() || pieces.back().ncb + (e - b) > budget) pieces.emplace_back();
-                Piece& pc = pieces.back();
-                chunks.push_back(Chunk{b, e, (int)pieces.size() - 1, pc.ncb});
-                if (!pc.br.empty() && pc.br.back().second + 1 == b) pc.br.back().second = e - 1;
-                else pc.br.emplace_back(b, e - 1);
-                pc.ncb += e - b;
-                b = e;
-            }
-    }
-    // segments: region by region, ascending tiles; every one lies inside one chunk's piece
-    std::vector<BandRegion> regs((size_t)n);
-    std::vector<std::vector<BandSeg>> psegs(pieces.size());
-    int64_t nseg_total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        regs[i] = BandRegion{(int32_t)nseg_total, 0, (int32_t)(rb[i].second - rb[i].first), 0};
-        for (int64_t b = rb[i].first; b < rb[i].second;) {
-            const int64_t e = std::min(rb[i].second, ((b >> 6) + 1) << 6);
-            size_t k = 0;
-            if (!maps) {
-                auto it = std::upper_bound(chunks.begin(), chunks.end(), b, [](int64_t v, const Chunk& ck) { return v < ck.b0; });
-                k = (size_t)(it - chunks.begin()) - 1;
-            }
-            const Chunk& ck = chunks[k];
-            psegs[ck.piece].push_back(BandSeg{(int32_t)(ck.cb0 + (b - ck.b0)), (int32_t)(e - b), (int32_t)nseg_total, 0});
-            ++nseg_total; ++regs[i].nseg;
-            b = e;
-        }
-        if (nseg_total > (int64_t)INT32_MAX / 2) return fail(c, SS_ERR_ARG, "ss_region_bands: too many region tiles");
-    }
-    std::vector<BandSeg> segs;
-    segs.reserve((size_t)nseg_total);
-    for (size_t p = 0; p < pieces.size(); ++p) {
-        pieces[p].seg0 = segs.size(); pieces[p].nseg = psegs[p].size();
-        segs.insert(segs.end(), psegs[p].begin(), psegs[p].end());
-    }
+    BandsPlan bp;
+    if (!plan_bands(regions, n, lo, hi, maps != nullptr, budget, W, bp)) return fail(c, SS_ERR_ARG, "ss_region_bands: too many region tiles");
     const size_t ns = (size_t)nsig;
     int rc;
-    if ((rc = ensure(c, &st.d_bseg, &st.bseg_cap, std::max<size_t>(segs.size(), 1)))) return rc;
-    if ((rc = ensure(c, &st.d_breg, &st.breg_cap, (size_t)n))) return rc;
-    if ((rc = ensure(c, &st.d_bpart, &st.bpart_cap, std::max<size_t>((size_t)nseg_total * ns * 256, 1)))) return rc;
-    if ((rc = ensure(c, &st.d_bout, &st.bout_cap, (size_t)n * ns))) return rc;
-    if (profile && (rc = ensure(c, &st.d_bprof, &st.bprof_cap, (size_t)n * ns * 256))) return rc;
-    if (!st.d_hz) {
+    if ((rc = st.bseg.reserve(c, std::max<size_t>(bp.segs.size(), 1))) || (rc = st.breg.reserve(c, (size_t)n)) ||
+        (rc = st.bpart.reserve(c, std::max<size_t>((size_t)bp.nseg_total * ns * 256, 1))) || (rc = st.bout.reserve(c, (size_t)n * ns)) ||
+        (profile && (rc = st.bprof.reserve(c, (size_t)n * ns * 256))))
+        return rc;
+    if (!st.hz.p) {
         double f[130];
         band_edges(f);
-        HIPCHK(c, hipMalloc((void**)&st.d_hz, sizeof f));
-        HIPCHK(c, hipMemcpy(st.d_hz, f, sizeof f, hipMemcpyHostToDevice));
+        if ((rc = st.hz.reserve(c, 130))) return rc;
+        HIPCHK(c, hipMemcpy(st.hz.p, f, sizeof f, hipMemcpyHostToDevice));
     }
-    if (!segs.empty()) HIPCHK(c, hipMemcpy(st.d_bseg, segs.data(), segs.size() * sizeof(BandSeg), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(st.d_breg, regs.data(), (size_t)n * sizeof(BandRegion), hipMemcpyHostToDevice));
-    for (const Piece& pc : pieces) {
+    if (!bp.segs.empty()) HIPCHK(c, hipMemcpy(st.bseg.p, bp.segs.data(), bp.segs.size() * sizeof(BandSeg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(st.breg.p, bp.regs.data(), (size_t)n * sizeof(BandRegion), hipMemcpyHostToDevice));
+    for (const BandPiece& pc : bp.pieces) {
         if (!pc.nseg) continue;
         int64_t ncb = pc.ncb;
         if (maps) {
-            if ((rc = ensure(c, &st.d_map, &st.map_cap, ns * (size_t)n_bins * 256))) return rc;
-            HIPCHK(c, hipMemcpyAsync(st.d_map, maps, ns * (size_t)n_bins * 256 * 4, hipMemcpyHostToDevice, c->stream));
+            if ((rc = st.map.reserve(c, ns * (size_t)n_bins * 256))) return rc;
+            HIPCHK(c, hipMemcpyAsync(st.map.p, maps, ns * (size_t)n_bins * 256 * 4, hipMemcpyHostToDevice, c->stream));
         } else {
-            std::vector<std::pair<int64_t, int64_t>> wr;
-            for (const auto& b : pc.br) {
-                int64_t w0, w1;
-                covering_windows(b.first, b.second, W, w0, w1);
-                if (!wr.empty() && w0 <= wr.back().second + 1) wr.back().second = std::max(wr.back().second, w1);
-                else wr.emplace_back(w0, w1);
-            }
-            if ((rc = sep_run_maps(c, fid, nsig, W, pc.br, wr, nullptr, ncb))) return rc;
+            if ((rc = sep_run_maps(c, fid, nsig, W, pc.br, pc.wr, nullptr, ncb))) return rc;
             if (ncb != pc.ncb) return fail(c, SS_ERR_HIP, "ss_region_bands: the maps do not hold the piece's bins");
         }
         ScopedLaunch sl(c, c->stream, "band_profile_kernel", 0.0, (double)pc.nseg * ns * (64.0 * 256 * 4 + 256 * 8));
-        hipLaunchKernelGGL(band_profile_kernel, dim3((unsigned)pc.nseg, (unsigned)nsig), dim3(256), 0, c->stream, st.d_map, (int)ncb,
-                           st.d_bseg + pc.seg0, (int)nseg_total, st.d_bpart);
+        hipLaunchKernelGGL(band_profile_kernel, dim3((unsigned)pc.nseg, (unsigned)nsig), dim3(256), 0, c->stream, st.map.p, (int)ncb,
+                           st.bseg.p + pc.seg0, (int)bp.nseg_total, st.bpart.p);
         HIPCHK(c, hipGetLastError());
     }
     {
-        ScopedLaunch sl(c, c->stream, "band_bounds_kernel", 0.0, (double)nseg_total * ns * 256 * 8 + (double)n * ns * (48 + (profile ? 2048 : 0)));
-        hipLaunchKernelGGL(band_bounds_kernel, dim3((unsigned)n, (unsigned)nsig), dim3(256), 0, c->stream, st.d_bpart, (int)nseg_total, st.d_breg,
-                           prm.speech_channel, prm.q_low, prm.q_high, st.d_hz, st.d_bout, profile ? st.d_bprof : nullptr);
+        ScopedLaunch sl(c, c->stream, "band_bounds_kernel", 0.0, (double)bp.nseg_total * ns * 256 * 8 + (double)n * ns * (48 + (profile ? 2048 : 0)));
+        hipLaunchKernelGGL(band_bounds_kernel, dim3((unsigned)n, (unsigned)nsig), dim3(256), 0, c->stream, st.bpart.p, (int)bp.nseg_total, st.breg.p,
+                           prm.speech_channel, prm.q_low, prm.q_high, st.hz.p, st.bout.p, profile ? st.bprof.p : nullptr);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(out, st.d_bout, (size_t)n * ns * sizeof(ss_region_band), hipMemcpyDeviceToHost, c->stream));
-    if (profile) HIPCHK(c, hipMemcpyAsync(profile, st.d_bprof, (size_t)n * ns * 256 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, st.bout.p, (size_t)n * ns * sizeof(ss_region_band), hipMemcpyDeviceToHost, c->stream));
+    if (profile) HIPCHK(c, hipMemcpyAsync(profile, st.bprof.p, (size_t)n * ns * 256 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }

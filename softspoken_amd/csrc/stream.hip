@@ -115,18 +115,8 @@ __global__ __launch_bounds__(256) void stream_band_kernel(const StreamBand* __re
 
 }  // namespace
 
-// A buffer a step grows to what its layout demands and the set releases with itself: device memory (ensure's growth, 1.5x) or pinned
-// host memory (need + need / 2, at least 64 KB).
-template <typename T>
-struct DevBuf {
-    T* p = nullptr; size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) hipFree(p); }
-    int reserve(ss_ctx* c, size_t n) { return ensure(c, &p, &cap, n); }
-    int reserve_bytes(ss_ctx* c, size_t bytes) { return reserve(c, bytes / sizeof(T)); }
-};
+// A buffer a step grows to what its layout demands and the set releases with itself: device memory (engine.h DevBuf: ensure's growth,
+// 1.5x) or pinned host memory (need + need / 2, at least 64 KB).
 struct PinBuf {
     unsigned char* p = nullptr; size_t cap = 0;
     PinBuf() = default;
