@@ -19,13 +19,14 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsoftspoken_hip.so")
 DEV_LIB = os.path.join(HERE, "libsoftspoken_hip_dev.so")
-SOURCES = ["conv2.hip", "conv2_ups.hip", "conv4.hip", "conv4_ups.hip", "conv1s.hip", "conv9s.hip", "conv9a.hip", "frontend.hip", "heads.hip", "weights.hip", "engine.hip", "host.hip", "abi.hip", "stream.hip", "separate.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("kernels.h", "engine.h", "dsp.h", "mfma_util.h", "conv4_forms.h", "stream16.h", "net.h", "bands.h", "hostdefs.h", "stream_desc.h", "stream_plan.h", "sep_plan.h")] + [os.path.join(os.path.dirname(HERE), "include", "softspoken.h")]
+SOURCES = ["conv2.hip", "conv2_ups.hip", "conv4.hip", "conv4_ups.hip", "conv1s.hip", "conv9s.hip", "conv9a.hip", "frontend.hip", "ingest.hip", "heads.hip", "weights.hip", "engine.hip", "host.hip", "abi.hip", "stream.hip", "separate.hip"]
+HEADERS = [os.path.join(CSRC, h) for h in ("kernels.h", "engine.h", "dsp.h", "mfma_util.h", "conv4_forms.h", "stream16.h", "net.h", "bands.h", "hostdefs.h", "stream_desc.h", "stream_plan.h", "sep_plan.h", "ingest_plan.h")] + [os.path.join(os.path.dirname(HERE), "include", "softspoken.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-unused-value"]
 # per-file additions.  frontend.hip: the SLP vectoriser turns the complex butterflies into v_pk_*_f32 and then spends a quarter of
 # the FFT loop's instructions on v_mov to pair registers for them; hand-packed code is shorter (measured on the GPU).
+# ingest.hip: frontend.hip's flag, under which its kernels were written and measured while they lived there.
 # conv4.hip: the same flag keeps v_pk_add_f32 out of the residual adds (packed fp32 beside MFMAs costs more than it saves): +0.6 %.
-EXTRA_FLAGS = {"frontend.hip": ["-fno-slp-vectorize"], "conv4.hip": ["-fno-slp-vectorize"], "conv4_ups.hip": ["-fno-slp-vectorize"],
+EXTRA_FLAGS = {"frontend.hip": ["-fno-slp-vectorize"], "ingest.hip": ["-fno-slp-vectorize"], "conv4.hip": ["-fno-slp-vectorize"], "conv4_ups.hip": ["-fno-slp-vectorize"],
                "conv1s.hip": ["-fno-slp-vectorize"], "conv9s.hip": ["-fno-slp-vectorize"], "conv9a.hip": ["-fno-slp-vectorize"]}
 # sources whose dev build differs from the product build (the others are shared between the two libraries)
 DEV_SOURCES = ("conv2.hip", "conv2_ups.hip", "conv4.hip", "conv4_ups.hip", "conv1s.hip", "frontend.hip", "engine.hip", "weights.hip", "abi.hip", "separate.hip")

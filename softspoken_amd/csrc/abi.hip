@@ -72,8 +72,8 @@ extern "C" void ss_destroy(ss_ctx* c) {
     for (void* p : c->user_dev) hipFree(p);
     for (void* p : c->user_host) hipHostFree(p);
     free_workspace(c);
-    for (auto& kv : c->taps) hipFree(kv.second.first);
-    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_batch, c->d_sil_out, c->d_sil_ranges, c->d_src_out, c->d_sx, c->d_sm, c->d_peaks};
+    for (auto& kv : c->taps) hipFree(kv.second);
+    void* singles[] = {c->d_arena, c->d_pcm, c->d_mono, c->d_winoff, c->d_logits, c->d_spec, c->d_avg, c->d_count, c->d_starts, c->d_avgfiles, c->d_desc, c->d_sil_out, c->d_sil_ranges, c->d_src_out, c->d_sx, c->d_sm, c->d_peaks};
     for (void* p : singles) if (p) hipFree(p);
     for (hipEvent_t ev : c->evpool) hipEventDestroy(ev);
     for (hipEvent_t ev : c->pass_ev) hipEventDestroy(ev);
@@ -126,98 +126,155 @@ extern "C" int ss_reset(ss_ctx* c) {
     return SS_OK;
 }
 
-static int arena_slot(ss_ctx* c, int64_t n, FileRec& fr, int64_t stored = -1, bool zero = true) {
-    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
-    fr.n = n < 0 ? 0 : n; fr.n_padded = stored >= 0 ? stored : n + 2 * (int64_t)SS_WINDOW_SAMPLES;
-    const size_t need = (size_t)fr.n_padded + 64;       // tail slack, keeps every slot 16-byte aligned
-    const size_t off = (c->arena_used + 3) & ~(size_t)3;
-    int rc = ensure(c, &c->d_arena, &c->arena_cap, off + need, true);
-    if (rc) return rc;
-    fr.off = (int64_t)off;
-    c->arena_used = off + need;
-    if (zero) HIPCHK(c, hipMemsetAsync(c->d_arena + off, 0, need * 4, c->stream));
-    return SS_OK;
-}
-
-// Kaiser-windowed sinc polyphase taps (the build's own design; oracle/oracle_np.py resample_plan states the same)
-static double bessel_i0(double x) {
-    double s = 1.0, t = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 200; ++k) { t *= q / ((double)k * k); s += t; if (t < s * 1e-17) break; }
-    return s;
-}
-
+// ------------------------------------------------------------------------------------------------------
+// ingest: voice_activity.py:32-69 (decode -> mono -> resample) + worker.py:58-62 (pad).  The plan of a call -- slots, route, descriptors,
+// geometries -- is ingest_plan.h's plan_ingest; ingest_run allocates, uploads and launches what it states.
+// ------------------------------------------------------------------------------------------------------
 int ss::get_taps(ss_ctx* c, int sr_in, int& L, int& M, int& half, float** d_taps) {
-    auto gcd = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
-    const int g = gcd(sr_in, SS_SAMPLE_RATE);
-    L = SS_SAMPLE_RATE / g; M = sr_in / g;
-    const double scale = std::min(1.0, (double)SS_SAMPLE_RATE / sr_in);
-    const double fc = 0.95 * scale, beta = 12.0;
-    half = (int)std::ceil(32.0 / scale);
-    auto key = std::make_pair(sr_in, 0);
-    auto it = c->taps.find(key);
-    if (it != c->taps.end()) { *d_taps = it->second.first; return SS_OK; }
-    const double PI = 3.14159265358979323846;
-    std::vector<float> t((size_t)L * 2 * half);
-    const double i0b = bessel_i0(beta);
-    for (int p = 0; p < L; ++p) {
-        const double frac = (double)(((int64_t)p * M) % L) / L;
-        for (int jj = 0; jj < 2 * half; ++jj) {
-            const double d = (double)(jj - half + 1) - frac;
-            const double xx = fc * d;
-            const double sinc = xx == 0.0 ? 1.0 : std::sin(PI * xx) / (PI * xx);
-            double w = 0.0;
-            if (std::fabs(d) <= half) { const double u = 1.0 - (d / half) * (d / half); w = bessel_i0(beta * std::sqrt(u < 0 ? 0 : u)) / i0b; }
-            t[(size_t)p * 2 * half + jj] = (float)(fc * sinc * w);
-        }
-    }
+    const ResampleRule r = resample_rule(sr_in);
+    L = r.L; M = r.M; half = r.half;
+    auto it = c->taps.find(sr_in);
+    if (it != c->taps.end()) { *d_taps = it->second; return SS_OK; }
+    const std::vector<float> t = design_taps(sr_in);
     float* dp = nullptr;
     HIPCHK(c, hipMalloc((void**)&dp, t.size() * 4));
     HIPCHK(c, hipMemcpy(dp, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    c->taps[key] = std::make_pair(dp, half);
+    c->taps[sr_in] = dp;
     *d_taps = dp;
     return SS_OK;
 }
 
-extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
-                                       int n_files, int* first_file_id);
-
-// one file == a batch of one (same kernels, same arithmetic)
-static int add_pcm_common(ss_ctx* c, const void* d_pcm, int format, int sr, int ch, int64_t frames, int* file_id) {
-    return ss_add_pcm_batch_device(c, d_pcm, format, sr, ch, &frames, 1, file_id);
-}
-
 int ss::check_pcm_args(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames) {
     if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
-    if ((!pcm && frames > 0) || format < SS_PCM_U8 || format > SS_PCM_F64BE || sr <= 0 || sr > 768000 || ch < 1 || ch > 64 || frames < 0 ||
-        frames > ((int64_t)1 << 36))          // (99 h at 192 kHz; keeps frames * channels * bytes and frames * 22050 inside 64 bits)
-        return fail(c, SS_ERR_ARG, "ss_add_pcm: bad argument");
+    if (!pcm_args_ok(pcm != nullptr, format, sr, ch, frames)) return fail(c, SS_ERR_ARG, "ss_add_pcm: bad argument");
     return SS_OK;
 }
 
-// voice_activity.py:32-69 (decode -> mono -> resample) + worker.py:58-62 (pad)
-extern "C" int ss_add_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, int* file_id) {
+// the caller's bytes -> c->d_pcm, on the compute stream
+static int stage_pcm(ss_ctx* c, const void* pcm, size_t bytes) {
+    if (int rc = ensure(c, (char**)&c->d_pcm, &c->pcm_cap, bytes + 16)) return rc;
+    if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    return SS_OK;
+}
+
+// One batch: the job has the plan's signals afterwards, or (any error) is as it was before the call
+static int ingest_run(ss_ctx* c, const IngestPlan& pl, const void* pcm_dev) {
+    if (c->copy_pending) {                                // the samples may still be crossing PCIe on the copy stream
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
+        c->copy_pending = false;
+    }
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    if (!pl.items_ok) return fail(c, SS_ERR_HIP, "ss_add_pcm: the batch takes more resampler items than one launch counts");
+    int rc;
+    if ((rc = ensure(c, &c->d_arena, &c->arena_cap, pl.arena_used, true))) return rc;
+    // one fill for the padding of the whole batch
+    HIPCHK(c, hipMemsetAsync(c->d_arena + pl.fill_off, 0, pl.fill_n * 4, c->stream));
+    if ((rc = ensure(c, &c->d_desc, &c->desc_cap, pl.desc.size()))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_desc, pl.desc.data(), pl.desc.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the plan is the caller's temporary
+    const ChanFile* d_cf = (const ChanFile*)(c->d_desc + pl.chan_off);
+    const BatchFile* d_bf = (const BatchFile*)(c->d_desc + pl.batch_off);
+    const ResampleRule r = pl.rule;
+    float* d_taps = nullptr;
+    if (pl.route != kRouteDecode) { int L, M, half; if ((rc = get_taps(c, pl.sr, L, M, half, &d_taps))) return rc; }
+    if (pl.route == kRoutePair && (rc = ensure(c, &c->d_mono, &c->mono_cap, pl.mono_n))) return rc;
+    float* decoded = pl.route == kRoutePair ? c->d_mono : c->d_arena;
+    if (pl.route == kRouteFused) {
+        // decode (+ mixdown) inside the resampler's LDS staging: one launch, no mono tensor
+        ScopedLaunch sl(c, c->stream, pl.each ? "resample_fused_channels" : "resample_fused", pl.fused.flops, pl.fused.bytes);
+        if (pl.each) HIPCHK(c, launch_resample_fused_channels(pcm_dev, pl.format, pl.ch, d_cf, pl.n_files, pl.res3, pl.items_per_file, r.L, r.M, r.half, d_taps, c->d_arena, c->num_cus, c->stream));
+        else HIPCHK(c, launch_resample_fused(pcm_dev, pl.format, pl.ch, d_bf, pl.n_files, pl.res3, pl.items_per_file, r.L, r.M, r.half, d_taps, c->d_arena, c->num_cus, c->stream));
+    } else {
+        ScopedLaunch sl(c, c->stream, pl.each ? "decode_channels_batch" : "decode_mono_batch", pl.decode.flops, pl.decode.bytes);
+        if (pl.each) HIPCHK(c, launch_decode_channels_batch(pcm_dev, pl.format, pl.ch, d_cf, pl.n_files, pl.max_frames, decoded, c->stream));
+        else HIPCHK(c, launch_decode_mono_batch(pcm_dev, pl.format, pl.ch, d_bf, pl.n_files, pl.max_frames, decoded, c->stream));
+    }
+    if (pl.route == kRoutePair) {
+        ScopedLaunch sl(c, c->stream, "resample_batch", pl.resample.flops, pl.resample.bytes);
+        HIPCHK(c, launch_resample_batch(c->d_mono, d_bf, (int)pl.n_batch, pl.max_out, pl.res, r.L, r.M, r.half, d_taps, c->d_arena, c->num_cus, c->stream));
+    }
+    c->files.insert(c->files.end(), pl.files.begin(), pl.files.end());
+    c->arena_used = pl.arena_used;
+    c->logits_valid = false;
+    return SS_OK;
+}
+
+// Many files of one format in one device buffer, back to back: one or two launches for the whole batch.  each: a signal per channel
+static int add_pcm_batch(ss_ctx* c, const char* who, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames, int n_files, bool each,
+                         int* first_file_id) {
+    if (!frames || n_files < 1) return fail(c, SS_ERR_ARG, std::string(who) + ": bad argument");
+    for (int i = 0; i < n_files; ++i)
+        if (int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames[i])) return rc;
+    if (each && !signal_count_ok(n_files, ch)) return fail(c, SS_ERR_ARG, std::string(who) + ": too many signals");
+    hipSetDevice(c->device);
+    const size_t first = c->files.size();
+    const IngestPlan pl = plan_ingest(format, sr, ch, frames, n_files, each, c->arena_used, dev_env("SOFTSPOKEN_RES3", 1) != 0);
+    if (int rc = ingest_run(c, pl, pcm_dev)) return rc;
+    if (first_file_id) *first_file_id = (int)first;
+    return SS_OK;
+}
+
+extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
+                                       int n_files, int* first_file_id) {
+    return add_pcm_batch(c, "ss_add_pcm_batch_device", pcm_dev, format, sr, ch, frames, n_files, false, first_file_id);
+}
+
+// per-channel ingest: a recording of `ch` channels -> `ch` signals, consecutive file ids, no mixdown (one channel: the mixdown call)
+extern "C" int ss_add_pcm_channels_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
+                                                int n_files, int* first_file_id) {
+    return add_pcm_batch(c, ch == 1 ? "ss_add_pcm_batch_device" : "ss_add_pcm_channels_batch_device", pcm_dev, format, sr, ch, frames, n_files, ch > 1,
+                         first_file_id);
+}
+
+// one file == a batch of one (same kernels, same arithmetic); the host-pointer forms stage the samples first
+static int add_pcm_one(ss_ctx* c, const void* pcm, bool on_host, bool each, int format, int sr, int ch, int64_t frames, int* file_id) {
     int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
     if (rc) return rc;
     hipSetDevice(c->device);
-    const size_t bps = pcm_bytes_per_sample(format);
-    const size_t bytes = (size_t)frames * ch * bps;
-    size_t cap_b = c->pcm_cap;
-    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
-    c->pcm_cap = cap_b;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
-    rc = add_pcm_common(c, c->d_pcm, format, sr, ch, frames, file_id);
+    if (on_host && (rc = stage_pcm(c, pcm, (size_t)frames * ch * pcm_bytes_per_sample(format)))) return rc;
+    const void* dev = on_host ? c->d_pcm : pcm;
+    rc = each ? ss_add_pcm_channels_batch_device(c, dev, format, sr, ch, &frames, 1, file_id) : ss_add_pcm_batch_device(c, dev, format, sr, ch, &frames, 1, file_id);
     if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // d_pcm / d_mono are reused by the next call
+    if (on_host) HIPCHK(c, hipStreamSynchronize(c->stream));     // d_pcm / d_mono are reused by the next call
     return SS_OK;
 }
 
-extern "C" int ss_add_pcm_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, int64_t frames, int* file_id) {
-    int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return add_pcm_common(c, pcm_dev, format, sr, ch, frames, file_id);
+extern "C" int ss_add_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, int* file_id) {
+    return add_pcm_one(c, pcm, true, false, format, sr, ch, frames, file_id);
 }
+extern "C" int ss_add_pcm_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, int64_t frames, int* file_id) {
+    return add_pcm_one(c, pcm_dev, false, false, format, sr, ch, frames, file_id);
+}
+extern "C" int ss_add_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, int* first_file_id) {
+    return add_pcm_one(c, pcm, true, true, format, sr, ch, frames, first_file_id);
+}
+extern "C" int ss_add_pcm_channels_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, int64_t frames, int* first_file_id) {
+    return add_pcm_one(c, pcm_dev, false, true, format, sr, ch, frames, first_file_id);
+}
+
+static int add_f32(ss_ctx* c, const float* s, int64_t n, bool padded, int* file_id) {
+    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
+    if ((!s && n > 0) || n < 0) return fail(c, SS_ERR_ARG, "ss_add_f32: bad argument");
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    hipSetDevice(c->device);
+    const int64_t core = padded ? n - 2 * (int64_t)SS_WINDOW_SAMPLES : n;
+    size_t used = c->arena_used;
+    FileRec fr = arena_slot(used, core, padded ? n : -1);
+    fr.duration = (double)(core < 0 ? 0 : core) / 22050.0;
+    if (int rc = ensure(c, &c->d_arena, &c->arena_cap, used, true)) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_arena + fr.off, 0, (used - (size_t)fr.off) * 4, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(c->d_arena + fr.off + (padded ? 0 : SS_WINDOW_SAMPLES), s, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->files.push_back(fr);
+    c->arena_used = used;
+    if (file_id) *file_id = (int)c->files.size() - 1;
+    c->logits_valid = false;
+    return SS_OK;
+}
+
+extern "C" int ss_add_f32_22k(ss_ctx* c, const float* s, int64_t n, int* file_id) { return add_f32(c, s, n, false, file_id); }
+extern "C" int ss_add_padded_f32_22k(ss_ctx* c, const float* s, int64_t n, int* file_id) { return add_f32(c, s, n, true, file_id); }
+
 extern "C" int ss_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                               int64_t n_regions, int16_t* out) {
     int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
@@ -228,12 +285,9 @@ extern "C" int ss_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, in
     const size_t bps = pcm_bytes_per_sample(format);
     const size_t bytes = (size_t)frames * ch * bps, total = (size_t)frames * ch;
     const std::vector<int64_t> ranges = silence_ranges(regions, n_regions, sr, frames);
-    size_t cap_b = c->pcm_cap;
-    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
-    c->pcm_cap = cap_b;
     if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
     if ((rc = ensure(c, &c->d_sil_ranges, &c->sil_ranges_cap, ranges.size() + 2))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_pcm(c, pcm, bytes))) return rc;
     if (!ranges.empty())
         HIPCHK(c, hipMemcpyAsync(c->d_sil_ranges, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice, c->stream));
     {
@@ -266,12 +320,9 @@ extern "C" int ss_silence_pcm_source(ss_ctx* c, const void* pcm, int format, int
     const size_t bytes = (size_t)(frames * fb);
     std::vector<int64_t> ranges = silence_ranges(regions, n_regions, sr, frames);
     for (int64_t& r : ranges) r *= fb;                        // byte ranges: the kernel knows no frames
-    size_t cap_b = c->pcm_cap;
-    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
-    c->pcm_cap = cap_b;
     if ((rc = ensure(c, &c->d_src_out, &c->src_out_cap, bytes + 16))) return rc;
     if ((rc = ensure(c, &c->d_sil_ranges, &c->sil_ranges_cap, ranges.size() + 2))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_pcm(c, pcm, bytes))) return rc;
     if (!ranges.empty())
         HIPCHK(c, hipMemcpyAsync(c->d_sil_ranges, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice, c->stream));
     {
@@ -432,207 +483,6 @@ extern "C" int ss_stft512_magnitude(ss_ctx* c, const float* samples, int64_t n, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
-// Many files of one format in one device buffer, back to back: two launches for the whole batch.
-extern "C" int ss_add_pcm_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
-                                       int n_files, int* first_file_id) {
-    if (!frames || n_files < 1) return fail(c, SS_ERR_ARG, "ss_add_pcm_batch_device: bad argument");
-    int64_t total_frames = 0, max_frames = 0, max_out = 0;
-    for (int i = 0; i < n_files; ++i) {
-        int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames[i]);
-        if (rc) return rc;
-        total_frames += frames[i]; max_frames = std::max(max_frames, frames[i]);
-    }
-    hipSetDevice(c->device);
-    if (c->copy_pending) {                                // ingest: the samples may still be crossing PCIe on the copy stream
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
-        c->copy_pending = false;
-    }
-    const size_t bps = pcm_bytes_per_sample(format);
-    int rc;
-    // reserve every arena slot first (the arena may move while it grows)
-    const size_t first = c->files.size();
-    const size_t arena_before = (c->arena_used + 3) & ~(size_t)3;
-    std::vector<BatchFile> bf(n_files);
-    int64_t pcm_off = 0, mono_off = 0;
-    for (int i = 0; i < n_files; ++i) {
-        FileRec fr;
-        fr.duration = (double)frames[i] / (double)sr;
-        const int64_t n22 = ss_resampled_length(frames[i], sr);
-        if ((rc = arena_slot(c, n22, fr, -1, false))) return rc;
-        c->files.push_back(fr);
-        bf[i].pcm_off = pcm_off; bf[i].frames = frames[i]; bf[i].mono_off = mono_off; bf[i].n_out = n22;
-        bf[i].out_off = fr.off + SS_WINDOW_SAMPLES;
-        pcm_off += frames[i] * ch * (int64_t)bps; mono_off += (frames[i] + 3) & ~(int64_t)3;
-        max_out = std::max(max_out, n22);
-    }
-    // one fill for the padding of the whole batch instead of one per file
-    HIPCHK(c, hipMemsetAsync(c->d_arena + arena_before, 0, (c->arena_used - arena_before) * 4, c->stream));
-    size_t cap = c->batch_cap;
-    if ((rc = ensure(c, &c->d_batch, &cap, (size_t)n_files))) return rc;
-    c->batch_cap = cap;
-    HIPCHK(c, hipMemcpyAsync(c->d_batch, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // bf is a host temporary
-    const double pcm_bytes = (double)total_frames * ch * bps;
-    if (sr == SS_SAMPLE_RATE) {
-        // decode straight into the arena: mono_off := out_off
-        for (int i = 0; i < n_files; ++i) bf[i].mono_off = bf[i].out_off;
-        HIPCHK(c, hipMemcpyAsync(c->d_batch, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ScopedLaunch sl(c, c->stream, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
-        HIPCHK(c, launch_decode_mono_batch(pcm_dev, format, ch, c->d_batch, n_files, max_frames, c->d_arena, c->stream));
-    } else {
-        int L, M, half; float* d_taps;
-        if ((rc = get_taps(c, sr, L, M, half, &d_taps))) return rc;
-        double n22sum = 0; for (auto& b : bf) n22sum += (double)b.n_out;
-        if (resample_fused_applies(L, M, half) && dev_env("SOFTSPOKEN_RES3", 1)) {
-            // decode + mixdown inside the resampler's LDS staging: one launch, no mono tensor
-            ScopedLaunch sl(c, c->stream, "resample_fused", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
-            HIPCHK(c, launch_resample_fused(pcm_dev, format, ch, c->d_batch, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
-        } else {
-            if ((rc = ensure(c, &c->d_mono, &c->mono_cap, (size_t)mono_off + 16))) return rc;
-            {
-                ScopedLaunch sl(c, c->stream, "decode_mono_batch", 0.0, pcm_bytes + 4.0 * total_frames);
-                HIPCHK(c, launch_decode_mono_batch(pcm_dev, format, ch, c->d_batch, n_files, max_frames, c->d_mono, c->stream));
-            }
-            ScopedLaunch sl(c, c->stream, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * total_frames + 4.0 * n22sum);
-            HIPCHK(c, launch_resample_batch(c->d_mono, c->d_batch, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
-        }
-    }
-    if (first_file_id) *first_file_id = (int)first;
-    c->logits_valid = false;
-    return SS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// per-channel ingest: a recording of `ch` channels -> `ch` signals, consecutive file ids, no mixdown
-// ------------------------------------------------------------------------------------------------------
-extern "C" int ss_add_pcm_channels_batch_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, const int64_t* frames,
-                                                int n_files, int* first_file_id) {
-    if (ch == 1) return ss_add_pcm_batch_device(c, pcm_dev, format, sr, ch, frames, n_files, first_file_id);
-    if (!frames || n_files < 1) return fail(c, SS_ERR_ARG, "ss_add_pcm_channels_batch_device: bad argument");
-    int64_t total_frames = 0, max_frames = 0, max_out = 0;
-    for (int i = 0; i < n_files; ++i) {
-        int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames[i]);
-        if (rc) return rc;
-        total_frames += frames[i]; max_frames = std::max(max_frames, frames[i]);
-    }
-    if ((int64_t)n_files * ch >= (int64_t)1 << 24) return fail(c, SS_ERR_ARG, "ss_add_pcm_channels_batch_device: too many signals");
-    hipSetDevice(c->device);
-    if (c->copy_pending) {                                // ingest: the samples may still be crossing PCIe on the copy stream
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
-        c->copy_pending = false;
-    }
-    const size_t bps = pcm_bytes_per_sample(format);
-    int rc;
-    // reserve every arena slot first (the arena may move while it grows); the slots of a recording's channels have one length, so they
-    // lie a constant stride apart
-    const size_t first = c->files.size();
-    const size_t arena_before = (c->arena_used + 3) & ~(size_t)3;
-    struct Rollback {                                     // any error below: the job keeps the files it had, no half-made signals
-        ss_ctx* c; size_t n_files, arena_used; bool done = false;
-        ~Rollback() { if (!done) { c->files.resize(n_files); c->arena_used = arena_used; } }
-    } rollback{c, first, c->arena_used};
-    std::vector<ChanFile> cf(n_files);
-    std::vector<BatchFile> bf;                            // the unfused pair's resampler: one entry per signal
-    int64_t pcm_off = 0, mono_off = 0;
-    double n22sum = 0;
-    for (int i = 0; i < n_files; ++i) {
-        const int64_t n22 = ss_resampled_length(frames[i], sr);
-        ChanFile& d = cf[i];
-        d.pcm_off = pcm_off; d.frames = frames[i]; d.mono_off = mono_off; d.n_out = n22; d.mono_stride = (frames[i] + 3) & ~(int64_t)3;
-        d.out_off = 0; d.out_stride = 0;
-        for (int k = 0; k < ch; ++k) {
-            FileRec fr;
-            fr.duration = (double)frames[i] / (double)sr;
-            if ((rc = arena_slot(c, n22, fr, -1, false))) return rc;
-            c->files.push_back(fr);
-            if (k == 0) d.out_off = fr.off + SS_WINDOW_SAMPLES;
-            else if (k == 1) d.out_stride = fr.off + SS_WINDOW_SAMPLES - d.out_off;
-            else if (fr.off + SS_WINDOW_SAMPLES != d.out_off + k * d.out_stride) return fail(c, SS_ERR_STATE, "ss_add_pcm_channels: arena slots are not evenly spaced");
-            bf.push_back(BatchFile{0, frames[i], d.mono_off + k * d.mono_stride, fr.off + SS_WINDOW_SAMPLES, n22});
-        }
-        pcm_off += frames[i] * ch * (int64_t)bps; mono_off += d.mono_stride * ch;
-        max_out = std::max(max_out, n22); n22sum += (double)n22 * ch;
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_arena + arena_before, 0, (c->arena_used - arena_before) * 4, c->stream));
-    const double pcm_bytes = (double)total_frames * ch * bps;
-    int L = 1, M = 1, half = 0; float* d_taps = nullptr;
-    if (sr != SS_SAMPLE_RATE && (rc = get_taps(c, sr, L, M, half, &d_taps))) return rc;
-    const bool fused = sr != SS_SAMPLE_RATE && resample_fused_applies(L, M, half) && dev_env("SOFTSPOKEN_RES3", 1);
-    if (sr == SS_SAMPLE_RATE)
-        for (ChanFile& d : cf) { d.mono_off = d.out_off; d.mono_stride = d.out_stride; }    // decode straight into the arena
-    // descriptors: the recordings' ChanFiles, then (unfused pair) the signals' BatchFiles, in one device buffer counted in BatchFiles
-    static_assert(sizeof(ChanFile) <= 2 * sizeof(BatchFile) && sizeof(BatchFile) % 8 == 0, "descriptor layout");
-    size_t cap = c->batch_cap;
-    if ((rc = ensure(c, &c->d_batch, &cap, (size_t)2 * n_files + bf.size()))) return rc;
-    c->batch_cap = cap;
-    ChanFile* d_cf = (ChanFile*)c->d_batch;
-    BatchFile* d_bf = c->d_batch + (size_t)2 * n_files;
-    HIPCHK(c, hipMemcpyAsync(d_cf, cf.data(), cf.size() * sizeof(ChanFile), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_bf, bf.data(), bf.size() * sizeof(BatchFile), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // cf / bf are host temporaries
-    if (sr == SS_SAMPLE_RATE) {
-        ScopedLaunch sl(c, c->stream, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
-        HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_arena, c->stream));
-    } else if (fused) {
-        // decode inside the resampler's LDS staging, the channels taking turns in the tile: one launch, no mono tensor
-        ScopedLaunch sl(c, c->stream, "resample_fused_channels", 2.0 * 2 * half * n22sum, pcm_bytes + 4.0 * n22sum);
-        HIPCHK(c, launch_resample_fused_channels(pcm_dev, format, ch, d_cf, n_files, max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
-    } else {
-        if ((rc = ensure(c, &c->d_mono, &c->mono_cap, (size_t)mono_off + 16))) return rc;
-        {
-            ScopedLaunch sl(c, c->stream, "decode_channels_batch", 0.0, pcm_bytes + 4.0 * ch * total_frames);
-            HIPCHK(c, launch_decode_channels_batch(pcm_dev, format, ch, d_cf, n_files, max_frames, c->d_mono, c->stream));
-        }
-        ScopedLaunch sl(c, c->stream, "resample_batch", 2.0 * 2 * half * n22sum, 4.0 * ch * total_frames + 4.0 * n22sum);
-        HIPCHK(c, launch_resample_batch(c->d_mono, d_bf, (int)bf.size(), max_out, L, M, half, d_taps, c->d_arena, c->num_cus, c->stream));
-    }
-    rollback.done = true;
-    if (first_file_id) *first_file_id = (int)first;
-    c->logits_valid = false;
-    return SS_OK;
-}
-
-extern "C" int ss_add_pcm_channels(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, int* first_file_id) {
-    int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    const size_t bytes = (size_t)frames * ch * pcm_bytes_per_sample(format);
-    size_t cap_b = c->pcm_cap;
-    if ((rc = ensure(c, (char**)&c->d_pcm, &cap_b, bytes + 16))) return rc;
-    c->pcm_cap = cap_b;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_pcm, pcm, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = ss_add_pcm_channels_batch_device(c, c->d_pcm, format, sr, ch, &frames, 1, first_file_id))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // d_pcm / d_mono are reused by the next call
-    return SS_OK;
-}
-
-extern "C" int ss_add_pcm_channels_device(ss_ctx* c, const void* pcm_dev, int format, int sr, int ch, int64_t frames, int* first_file_id) {
-    int rc = check_pcm_args(c, pcm_dev, format, sr, ch, frames);
-    if (rc) return rc;
-    return ss_add_pcm_channels_batch_device(c, pcm_dev, format, sr, ch, &frames, 1, first_file_id);
-}
-
-static int add_f32(ss_ctx* c, const float* s, int64_t n, bool padded, int* file_id) {
-    if (!c) return fail(nullptr, SS_ERR_ARG, "null context");
-    if ((!s && n > 0) || n < 0) return fail(c, SS_ERR_ARG, "ss_add_f32: bad argument");
-    hipSetDevice(c->device);
-    FileRec fr;
-    const int64_t core = padded ? n - 2 * (int64_t)SS_WINDOW_SAMPLES : n;
-    fr.duration = (double)(core < 0 ? 0 : core) / 22050.0;
-    int rc;
-    if ((rc = arena_slot(c, core, fr, padded ? n : -1))) return rc;
-    if (n) HIPCHK(c, hipMemcpyAsync(c->d_arena + fr.off + (padded ? 0 : SS_WINDOW_SAMPLES), s, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->files.push_back(fr);
-    if (file_id) *file_id = (int)c->files.size() - 1;
-    c->logits_valid = false;
-    return SS_OK;
-}
-
-extern "C" int ss_add_f32_22k(ss_ctx* c, const float* s, int64_t n, int* file_id) { return add_f32(c, s, n, false, file_id); }
-extern "C" int ss_add_padded_f32_22k(ss_ctx* c, const float* s, int64_t n, int* file_id) { return add_f32(c, s, n, true, file_id); }
-
 extern "C" int64_t ss_signal_length(ss_ctx* c, int file_id, int padded) {
     if (!c || file_id < 0 || file_id >= (int)c->files.size()) return -1;
     return padded ? c->files[file_id].n_padded : c->files[file_id].n;

@@ -5,6 +5,7 @@
 //   net.h         the network's graph, stated once: workspace tensors (ss::Act, kActs) and ResBlocks (kBlocks); the arrays below are indexed by it
 //   host.hip      host-only pieces of the path: WAV header walk, window plan, run merger (ss::RunMerger) and regions, CSV text
 //   sep_plan.h    the separation silencer's and the region bands' host plan (no HIP): the small rules host.hip and abi.hip call too
+//   ingest_plan.h the host plan of PCM ingest (no HIP): rate rule, tap table, resampler geometries, slot rule, plan_ingest
 //   abi.hip       the C ABI (include/softspoken.h): argument checks, arena, getters, measurement
 // Not part of the C ABI.
 #pragma once
@@ -67,14 +68,7 @@ struct ConvPlan {          // one launch of a ResBlock half
 
 struct BlockPlan { ConvPlan A, B; };    // the two launches of a ResBlock
 
-struct FileRec {
-    int64_t off = 0;        // arena offset of the padded signal
-    int64_t n = 0;          // samples at 22 050 Hz (unpadded)
-    int64_t n_padded = 0;
-    double duration = 0;    // header duration in seconds (frames / sample_rate)
-    int64_t W = 0, win_base = 0;                          // plan of the last ss_run_begin
-    int64_t bin_off = 0; int n_bins = 0;
-};
+// (FileRec, a signal's place in the arena: ingest_plan.h)
 
 struct StreamSet;                                         // stream.hip: the context's streams and their step buffers
 struct SepState;                                          // separate.hip: the separation silencer's tables and buffers
@@ -169,8 +163,8 @@ struct ss_ctx {
     unsigned char* d_src_out = nullptr; size_t src_out_cap = 0;  // source-encoding output (ss_silence_pcm_source, ss_separate_pcm*_source): bytes
     float* d_mono = nullptr; size_t mono_cap = 0;
     double* d_peaks = nullptr; size_t peaks_cap = 0;             // ss_get_region_peaks: results, then the regions' bin ranges and the channels' offsets
-    ss::BatchFile* d_batch = nullptr; size_t batch_cap = 0;
-    std::map<std::pair<int, int>, std::pair<float*, int>> taps;   // (sr_in) -> device taps, half
+    unsigned char* d_desc = nullptr; size_t desc_cap = 0;         // the descriptor image of the ingest call at work (IngestPlan::desc)
+    std::map<int, float*> taps;                                   // sr_in -> device taps (ingest_plan.h design_taps)
 
     // run state
     int64_t* d_winoff = nullptr; size_t winoff_cap = 0;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "stream_desc.h"
+#include "ingest_plan.h"
 
 namespace ss {
 
@@ -269,8 +270,8 @@ hipError_t launch_frontend(const float* arena, const int64_t* win_off, int n, co
                            int num_cus, hipStream_t s);
 
 // ---- decode / mixdown / resample ----------------------------------------------------------------------
-// batched: every file of a job in one launch; sr == 22050 files go mono -> arena directly (L == M == 1, half == 0)
-struct BatchFile { int64_t pcm_off; int64_t frames; int64_t mono_off; int64_t out_off; int64_t n_out; };
+// (ingest.hip; descriptors BatchFile / ChanFile: stream_desc.h; geometries Res3Geom / ResGeom: ingest_plan.h)
+// batched: every file of a job in one launch; sr == 22050 files go mono -> arena directly
 hipError_t launch_decode_mono_batch(const void* pcm, int format, int channels, const BatchFile* d_files, int n_files,
                                     int64_t max_frames, float* mono, hipStream_t s);
 // review-screen spectrogram: |STFT| with n_fft = win = 512, hop 256, centred, zero-padded -> [257][n_frames]
@@ -281,20 +282,18 @@ hipError_t launch_silence_encode(const void* pcm, int format, int channels, int6
 // source-encoding silencer: the nbytes of pcm with the bytes inside d_byte_ranges (disjoint ascending [begin, end) byte pairs) replaced
 // by the zero byte of `format`; pcm and out 16-byte aligned
 hipError_t launch_silence_source(const void* pcm, int64_t nbytes, const int64_t* d_byte_ranges, int n_ranges, int format, void* out, hipStream_t s);
-// decode + mixdown + polyphase resampling in one launch (no mono tensor); applies when resample_fused_applies says so
-bool resample_fused_applies(int L, int M, int half);
-hipError_t launch_resample_fused(const void* pcm, int format, int channels, const BatchFile* d_files, int n_files, int64_t max_out, int L, int M,
-                                 int half, const float* taps, float* arena, int num_cus, hipStream_t s);
-hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, int n_files, int64_t max_out, int L, int M, int half,
+// decode + mixdown + polyphase resampling in one launch (no mono tensor), where res3_geometry applies; ipf: items per file
+hipError_t launch_resample_fused(const void* pcm, int format, int channels, const BatchFile* d_files, int n_files, const Res3Geom& gm, int64_t ipf,
+                                 int L, int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s);
+hipError_t launch_resample_batch(const float* mono, const BatchFile* d_files, int n_files, int64_t max_out, const ResGeom& gm, int L, int M, int half,
                                  const float* taps, float* arena, int num_cus, hipStream_t s);
 // per-channel ingest (no mixdown): channel c of a recording is decoded to dst[mono_off + c mono_stride ..) / resampled to
 // arena[out_off + c out_stride ..); one descriptor per recording, the channels' planes a constant stride apart
-struct ChanFile { int64_t pcm_off; int64_t frames; int64_t mono_off; int64_t out_off; int64_t n_out; int64_t mono_stride; int64_t out_stride; };
 hipError_t launch_decode_channels_batch(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_frames,
                                         float* dst, hipStream_t s);
-// the fused form (resample_fused_applies): the PCM of a tile fetched once for two channels, the channels taking turns in the one LDS tile
-hipError_t launch_resample_fused_channels(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, int64_t max_out, int L,
-                                          int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s);
+// the fused form: the PCM of a tile fetched once for two channels, the channels taking turns in the one LDS tile
+hipError_t launch_resample_fused_channels(const void* pcm, int format, int channels, const ChanFile* d_files, int n_files, const Res3Geom& gm,
+                                          int64_t ipf, int L, int M, int half, const float* taps, float* arena, int num_cus, hipStream_t s);
 
 // ---- overlap averaging (NNDetector.py:153-190), double accumulation ---------------------------------
 // s_b: bins between window starts (window step x 256 / 3), from which a bin's candidate windows are bounded; starts: the windows' first bins

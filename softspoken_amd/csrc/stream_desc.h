@@ -1,11 +1,20 @@
 // The descriptors of the stream kernels (frontend.hip's stream_* kernels, stream.hip's stream_map_kernel and stream_band_kernel): one
-// launch per step for all streams, a descriptor per stream or lane.  Plain data, no HIP header: the host-only stages of a step
-// (stream_plan.h) build them, and tests/stream_extents.cpp checks what they address without a device.
+// launch per step for all streams, a descriptor per stream or lane; and those of the ingest kernels (ingest.hip), one per file or
+// recording of a batch.  Plain data, no HIP header: the host-only plans (stream_plan.h, ingest_plan.h) build them, and
+// tests/stream_extents.cpp and tests/ingest_plan_check.cpp check what they address without a device.
 #pragma once
 #include <cstdint>
 
 namespace ss {
 
+// ---- ingest ----
+// a file of a batch: its bytes at pcm + pcm_off; decoded (and mixed down) to mono[mono_off ..), resampled to arena[out_off .. + n_out)
+struct BatchFile { int64_t pcm_off; int64_t frames; int64_t mono_off; int64_t out_off; int64_t n_out; };
+// per-channel ingest (no mixdown): channel c of a recording is decoded to dst[mono_off + c mono_stride ..) / resampled to
+// arena[out_off + c out_stride ..); one descriptor per recording, the channels' planes a constant stride apart
+struct ChanFile { int64_t pcm_off; int64_t frames; int64_t mono_off; int64_t out_off; int64_t n_out; int64_t mono_stride; int64_t out_stride; };
+
+// ---- streams ----
 struct StreamCopy { const float* src; float* dst; int64_t n; };                       // src == nullptr: n zeros
 struct StreamDecode { int64_t pcm_off; int64_t frames; float* dst; int32_t format, channels; };
 // outputs [m0, m0 + n) -> out[0 .. n); input sample idx is mono[idx - mono_base] for mono_base <= idx < frames, zero past `frames`
