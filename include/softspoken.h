@@ -730,6 +730,74 @@ int64_t ss_stream_separate_limit(int sample_rate, int64_t frames_decoded, int64_
 /* Host only: D_sep in seconds; NaN on a bad argument. */
 double ss_stream_separate_latency(int sample_rate, double break_s, const ss_stream_erase* erase, const ss_separation_params* params);
 
+/* ---- band silencer: erase only each region's own frequency band ------------------------------------------------------------
+ * The third silencing method, between the other two: ss_silence_pcm zeroes the whole spectrum of a reviewed interval, ss_separate_pcm
+ * needs the network.  This one works from a table of boxes alone -- the region bands' side file, or boxes adjusted by hand --: inside
+ * each box's time range the box's own frequency band is removed and the rest of the spectrum stays.  No model pass; any context will
+ * do.  Definition (float64 restatement: tests/box_ref.py), step by step:
+ *  1. Time ranges.  Box i has the frame range [a_i, b_i): ss_silence_pcm's rounding (Python round of start x sample_rate and end x
+ *     sample_rate), clamped to the file; a box whose range is empty drops out.  The merged intervals are the merge of all [a_i, b_i),
+ *     on whichever channel they act, as ss_silence_pcm merges (overlapping and touching ranges join).
+ *  2. STFT.  Step 3 of the separation silencer, unchanged: N = the separation silencer's FFT size of the rate, hop N / 4, periodic Hann
+ *     for analysis and synthesis, the overlap-add divided by 1.5, frame k centred on sample k hop, zeros outside the file.  Only the
+ *     frames whose support meets a merged interval run.
+ *  3. Gains.  Frame k is active for box i when its support [k hop - N/2, k hop + N/2) meets [a_i, b_i): every sample inside a box has
+ *     all four of its frames active for that box.  With lo_b = low_hz N / sample_rate, hi_b = high_hz N / sample_rate (a NaN low_hz
+ *     counts as 0, a NaN high_hz as +infinity: "no estimate" erases the whole band), e_b = edge_hz N / sample_rate,
+ *     q_lo = ceil(lo_b) and q_hi = min(floor(hi_b), N/2) -- both decided on the host in double --, the profile of box i over the STFT
+ *     bins q = 0 .. N/2 is
+ *         v_i(q) = 1                                   for q_lo <= q <= q_hi,
+ *                  (1 + cos(pi d / e_b)) / 2           for q < q_lo with d = lo_b - q < e_b, and for q > q_hi with d = q - hi_b < e_b,
+ *                  0                                   otherwise (e_b = 0: the hard edge),
+ *     its gain g_i(q) = 1 - (1 - min_gain) v_i(q), and G_c(k, q) = the minimum of g_i(q) over the boxes active at k that act on channel
+ *     c (channel -1: on every channel), 1 when there is none.  The gain is real and even in q.
+ *  4. Blend and encode.  Step 4 of the separation silencer: y = x + w (p - x) with the raised-cosine ramp over round(fade_s x
+ *     sample_rate) samples at either end of a MERGED interval; lrintf(y x 32767) for the 16-bit call, the source output's encode for
+ *     the _source call.  Outside the merged intervals the output is ss_silence_pcm's transcode / the input's bytes.
+ * With a full-band box (low 0 or NaN, high >= sample_rate / 2 or NaN) on every channel, min_gain 0 and fade_s 0 the output is
+ * ss_silence_pcm's (ss_silence_pcm_source's), byte for byte.
+ * State: ss_silence_pcm's.  Any context (audio-only included); the job's files, results and streams are untouched; SS_ERR_STATE while a
+ * run is in flight.  SS_ERR_ARG: a start or end that is not finite, end < start, low_hz > high_hz (after the NaN rule), a negative
+ * high_hz, a channel outside -1 .. channels - 1, reserved != 0, fade_s or edge_hz negative or not finite, min_gain outside [0, 1].
+ * n_boxes == 0, or boxes that are all empty: the plain transcode / the input's bytes. */
+typedef struct ss_box {
+    double start, end;          /* seconds, as ss_region (the reference's "-3" applied) */
+    double low_hz, high_hz;     /* NaN low_hz: 0; NaN high_hz: +infinity */
+    int32_t channel;            /* -1: every channel; 0 .. channels - 1: that channel alone */
+    int32_t reserved;           /* 0 */
+} ss_box;                       /* 40 bytes */
+
+typedef struct ss_box_params {
+    double fade_s;              /* >= 0, default 0.01 */
+    double min_gain;            /* in [0, 1], default 0 */
+    double edge_hz;             /* >= 0, default 100: the raised-cosine roll-off outside [low_hz, high_hz] */
+} ss_box_params;                /* NULL params: the defaults */
+
+typedef struct ss_box_range {   /* one merged interval and the STFT frames whose support meets it */
+    int64_t frame_begin, frame_end;    /* [begin, end) */
+    int64_t stft_first, stft_last;     /* inclusive; stft_first may be negative */
+} ss_box_range;
+
+typedef struct ss_box_plan_info {
+    int32_t n_fft, hop;
+    int64_t n_frames;                  /* STFT frames whose support meets a merged interval, each counted once */
+    int64_t n_ranges;                  /* out: merged intervals */
+    int64_t cap_ranges;                /* in: room in `ranges` (SS_ERR_CAPACITY when smaller; n_ranges is set either way) */
+    ss_box_range* ranges;              /* in: caller's array (NULL when cap_ranges == 0) */
+} ss_box_plan_info;
+
+/* Host only: the plan of ss_box_silence_pcm for a file of `frames` frames at sample_rate (the limits of ss_add_pcm).  The channel field
+ * of a box is checked against -1 .. 255 here (the file's channel count is not an argument); everything else as the calls below. */
+int ss_box_plan(int sample_rate, int64_t frames, const ss_box* boxes, int64_t n_boxes, const ss_box_params* params, ss_box_plan_info* out);
+/* The band silencer (above): interleaved PCM in (any enum ss_pcm_format, rate and channel count ss_add_pcm takes), interleaved 16-bit
+ * PCM out (frames x channels int16, as ss_silence_pcm). */
+int ss_box_silence_pcm(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, const ss_box* boxes,
+                       int64_t n_boxes, const ss_box_params* params, int16_t* out);
+/* The same in the recording's own encoding (source output: `out` takes frames x channels x bytes per sample bytes, SS_ERR_CAPACITY
+ * when cap_bytes is smaller; every byte outside the merged intervals is the input's). */
+int ss_box_silence_pcm_source(ss_ctx* ctx, const void* pcm, int format, int sample_rate, int channels, int64_t frames, const ss_box* boxes,
+                              int64_t n_boxes, const ss_box_params* params, void* out, int64_t cap_bytes);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Enqueue-only variant of ss_run used by bench.py: same work, no host readback until ss_sync. */
 int ss_sync(ss_ctx* ctx);
@@ -747,7 +815,7 @@ int64_t ss_workspace_bytes(ss_ctx* ctx);
  * error; nth < 0 switches it off.  The context must come out of such a failure without a workspace (and allocate one afresh on
  * the next call), never with dangling tensors. */
 int ss_debug_fail_workspace_alloc(ss_ctx* ctx, int nth);
-/* ss_separate_pcm holds at most `frames` resynthesised STFT frames at once (never fewer than 16) in place of the number that fits its
+/* ss_separate_pcm (and ss_box_silence_pcm) holds at most `frames` resynthesised STFT frames at once (never fewer than 16) in place of the number that fits its
  * 256 MB frame buffer, so that a short recording meets the cuts of a long one: a chunk ends when the next piece would pass the number,
  * an interval is cut into pieces of (frames - 8) hops.  frames <= 0: the product's number again.  The bytes written must not depend on it. */
 int ss_debug_set_separation_budget(ss_ctx* ctx, int64_t frames);

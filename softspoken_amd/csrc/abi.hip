@@ -418,6 +418,50 @@ extern "C" int ss_separate_pcm_channels_source(ss_ctx* c, const void* pcm, int f
 }
 
 // ------------------------------------------------------------------------------------------------------
+// band silencer (separate.hip box_run): inside each box's time range, only the box's own frequency band is removed
+// ------------------------------------------------------------------------------------------------------
+extern "C" int ss_box_plan(int sr, int64_t frames, const ss_box* boxes, int64_t n_boxes, const ss_box_params* params, ss_box_plan_info* out) {
+    std::string err;
+    if (!out || sr <= 0 || sr > 768000 || frames < 0 || frames > ((int64_t)1 << 36) || (out->cap_ranges > 0 && !out->ranges) || out->cap_ranges < 0)
+        return fail(nullptr, SS_ERR_ARG, "ss_box_plan: bad argument");
+    if (int rc = check_box_args(boxes, n_boxes, 0, params, err)) return fail(nullptr, rc, "ss_box_plan: " + err);
+    BoxPlan bp;
+    plan_boxes(sr, frames, 1, boxes, n_boxes, params ? *params : box_defaults(), 0, bp);
+    out->n_fft = bp.N; out->hop = bp.hop; out->n_frames = bp.n_frames;
+    out->n_ranges = (int64_t)bp.ranges.size();
+    if (out->n_ranges > out->cap_ranges)
+        return fail(nullptr, SS_ERR_CAPACITY, "ss_box_plan: " + std::to_string(out->n_ranges) + " ranges, room for " + std::to_string(out->cap_ranges));
+    if (!bp.ranges.empty()) memcpy(out->ranges, bp.ranges.data(), bp.ranges.size() * sizeof(ss_box_range));
+    return SS_OK;
+}
+
+// the checks of both calls, in ss_silence_pcm's order; then the recording goes to c->d_pcm and box_run does the rest
+static int box_call(ss_ctx* c, const char* who, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_box* boxes,
+                    int64_t n_boxes, const ss_box_params* params, void* out, int64_t cap_bytes) {
+    int rc = check_pcm_args(c, pcm, format, sr, ch, frames);
+    if (rc) return rc;
+    if (c->run_pending) return fail(c, SS_ERR_STATE, "a run is in flight: ss_run_end first");
+    if (src) { if ((rc = check_source_out(c, who, format, ch, frames, out, cap_bytes))) return rc; }
+    else if (!out && frames > 0) return fail(c, SS_ERR_ARG, std::string(who) + ": bad argument");
+    std::string err;
+    if ((rc = check_box_args(boxes, n_boxes, ch, params, err))) return fail(c, rc, std::string(who) + ": " + err);
+    if (frames == 0) return SS_OK;
+    hipSetDevice(c->device);
+    if ((rc = stage_pcm(c, pcm, (size_t)frames * ch * pcm_bytes_per_sample(format)))) return rc;
+    return box_run(c, src, format, sr, ch, frames, boxes, n_boxes, params, out);
+}
+
+extern "C" int ss_box_silence_pcm(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_box* boxes, int64_t n_boxes,
+                                  const ss_box_params* params, int16_t* out) {
+    return box_call(c, "ss_box_silence_pcm", false, pcm, format, sr, ch, frames, boxes, n_boxes, params, out, 0);
+}
+
+extern "C" int ss_box_silence_pcm_source(ss_ctx* c, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_box* boxes,
+                                         int64_t n_boxes, const ss_box_params* params, void* out, int64_t cap_bytes) {
+    return box_call(c, "ss_box_silence_pcm_source", true, pcm, format, sr, ch, frames, boxes, n_boxes, params, out, cap_bytes);
+}
+
+// ------------------------------------------------------------------------------------------------------
 // region bands (separate.hip): each region's frequency extent from the spec head's speech map
 // ------------------------------------------------------------------------------------------------------
 extern "C" int ss_band_edges(double* hz130) {

@@ -271,6 +271,9 @@ int separation_maps(ss_ctx* c, int file_id, int64_t first_bin, int64_t n_bins, f
 int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, int sr, int ch, int64_t frames, const ss_region* regions,
                  int64_t n_regions, const ss_separation_params* params, void* out);
 void free_separation(ss_ctx* c);
+// separate.hip, band silencer (plan_boxes, check_box_args, box_defaults: sep_plan.h); the recording is in c->d_pcm
+int box_run(ss_ctx* c, bool src, int format, int sr, int ch, int64_t frames, const ss_box* boxes, int64_t n_boxes, const ss_box_params* params,
+            void* out);
 // separate.hip, region bands (include/softspoken.h "region bands")
 void band_edges(double* hz130);
 // maps == nullptr: the spec head on files fid .. fid + nsig - 1; otherwise the caller's maps of bins first_bin .. first_bin + n_bins - 1

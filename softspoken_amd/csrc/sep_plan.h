@@ -4,11 +4,13 @@
 //   small rules   FFT size, file geometry, a frame's two bins, the windows over a bin range, ss_separation_plan, argument checks
 //   plan_maps       merged bin and window ranges -> compact bins, window slots, the run list       (separate.hip sep_run_maps)
 //   plan_ranges, plan_synthesis  a SepPlan -> merged ranges; frames, interval pieces, chunks of a frame budget  (separate_run)
+//   plan_boxes      a box table -> merged intervals, box rows, each frame's active boxes; the same pieces and chunks  (box_run)
 //   plan_bands      regions -> rule 1, the disjoint union, pieces of a bin budget, tile segments   (region_bands)
 #pragma once
 #include "hostdefs.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <string>
 #include <utility>
@@ -149,11 +151,16 @@ struct SepRanges {
     Ranges br, wr;                                        // the intervals' bins and windows, merged: what the maps are made over
     std::vector<int64_t> cbase;                           // compact index of each interval's first bin
 };
-struct SynthPlan {
-    std::vector<SepFrame> fr;
+// The cuts of a frame budget, shared by the separation silencer and the band silencer (plan_boxes): interval pieces, their frame
+// records (counted here, laid out by the caller) and the chunks of the frame buffer
+struct SepCuts {
     std::vector<SepSeg> sg;
     std::vector<SepChunk> chunks;
-    size_t max_rec = 0, fout_need = 0;                    // most records of a chunk; the frame buffer [max_rec][npairs][N], in float2
+    size_t n_rec = 0, max_rec = 0;                        // records in all; most records of a chunk
+};
+struct SynthPlan : SepCuts {
+    std::vector<SepFrame> fr;
+    size_t fout_need = 0;                                 // the frame buffer [max_rec][npairs][N], in float2
 };
 
 inline SepRanges plan_ranges(const SepPlan& pl) {
@@ -174,31 +181,159 @@ inline SepRanges plan_ranges(const SepPlan& pl) {
     return p;
 }
 
-// pieces of at most (budget - 8) hop samples, chunks of at most `budget` frames (budget >= 16); cbase: plan_ranges' (made behind the maps' launches)
+// One merged interval [a, b) cut into pieces of at most (budget - 8) hop samples; a piece opens a new chunk when its frames would pass
+// `budget` records (budget >= 16).  A piece holds every frame over its samples, so neighbours recompute the three frames they share.
+// frame(k): called once per record, in record order -- the caller appends its own record for frame k.
+template <class Frame>
+inline void cut_interval(SepCuts& p, int N, int hop, int64_t budget, int64_t a, int64_t b, Frame&& frame) {
+    const int64_t piece = (budget - 8) * hop;
+    for (int64_t s0 = a; s0 < b; s0 += piece) {
+        const int64_t s1 = std::min(b, s0 + piece);
+        const int64_t k0 = floordiv(s0 - N / 2, hop) + 1, k1 = -floordiv(-(s1 + N / 2), hop) - 1;
+        if (p.chunks.empty() || (int64_t)(p.n_rec - p.chunks.back().rec0) + (k1 - k0 + 1) > budget)
+            p.chunks.push_back(SepChunk{p.sg.size(), 0, p.n_rec, 0, 0});
+        SepChunk& ck = p.chunks.back();
+        p.sg.push_back(SepSeg{a, b, s0, s1, k0, (int64_t)(p.n_rec - ck.rec0), ck.total});
+        for (int64_t k = k0; k <= k1; ++k) { frame(k); ++p.n_rec; }
+        ck.nseg++; ck.nrec = p.n_rec - ck.rec0; ck.total += s1 - s0;
+    }
+}
+inline void finish_cuts(SepCuts& p) { for (const SepChunk& ck : p.chunks) p.max_rec = std::max(p.max_rec, ck.nrec); }
+
+// pieces and chunks of a frame budget (cut_interval); cbase: plan_ranges' (made behind the maps' launches)
 inline SynthPlan plan_synthesis(const SepPlan& pl, const std::vector<int64_t>& cbase, int sr, int ch, int64_t budget) {
     SynthPlan p;
     const int N = pl.N, hop = pl.hop;
-    const int64_t piece = (budget - 8) * hop;
     for (size_t r = 0; r < pl.ranges.size(); ++r) {
         const auto& g = pl.ranges[r];
-        for (int64_t s0 = g.frame_begin; s0 < g.frame_end; s0 += piece) {
-            const int64_t s1 = std::min(g.frame_end, s0 + piece);
-            const int64_t k0 = floordiv(s0 - N / 2, hop) + 1, k1 = -floordiv(-(s1 + N / 2), hop) - 1;
-            if (p.chunks.empty() || (int64_t)(p.fr.size() - p.chunks.back().rec0) + (k1 - k0 + 1) > budget)
-                p.chunks.push_back(SepChunk{p.sg.size(), 0, p.fr.size(), 0, 0});
-            SepChunk& ck = p.chunks.back();
-            p.sg.push_back(SepSeg{g.frame_begin, g.frame_end, s0, s1, k0, (int64_t)(p.fr.size() - ck.rec0), ck.total});
-            for (int64_t k = k0; k <= k1; ++k) {
-                int64_t j0, j1; double al;
-                frame_bins(k, hop, sr, pl.n_bins, j0, j1, al);
-                p.fr.push_back(SepFrame{k, (int32_t)(cbase[r] + (j0 - g.bin_first)), (int32_t)(cbase[r] + (j1 - g.bin_first)), (float)al, 0});
-            }
-            ck.nseg++; ck.nrec = p.fr.size() - ck.rec0; ck.total += s1 - s0;
-        }
+        cut_interval(p, N, hop, budget, g.frame_begin, g.frame_end, [&](int64_t k) {
+            int64_t j0, j1; double al;
+            frame_bins(k, hop, sr, pl.n_bins, j0, j1, al);
+            p.fr.push_back(SepFrame{k, (int32_t)(cbase[r] + (j0 - g.bin_first)), (int32_t)(cbase[r] + (j1 - g.bin_first)), (float)al, 0});
+        });
     }
-    for (const SepChunk& ck : p.chunks) p.max_rec = std::max(p.max_rec, ck.nrec);
+    finish_cuts(p);
     p.fout_need = p.max_rec * (size_t)((ch + 1) / 2) * N;
     return p;
+}
+
+// ---- box plan: what box_stft_kernel<N> reads (include/softspoken.h "band silencer") ------------------------------------
+// a box's row: bins q_lo .. q_hi lie inside (q_lo clamped to 0 .. N/2 + 1, q_hi to -1 .. N/2; q_lo > q_hi: no bin inside).  The distances
+// of the roll-off are kept as an exact integer and a fraction, so that float32 holds them at every N: below q_lo, d = (q_lo - q) - lo_f
+// with lo_f = q_lo - lo_b; above q_hi, d = (q - q_hi) - hi_f with hi_f = hi_b - q_hi.  inv_e = 1 / e_b, 0 for the hard edge.
+struct BoxRow { int32_t q_lo, q_hi; float lo_f, hi_f, inv_e; int32_t channel; };
+struct BoxFrame { int64_t k; int32_t first, count; };     // frame k's active boxes: idx[first .. first + count - 1], ascending box index
+
+struct BoxPlan : SepCuts {
+    int N = 0, hop = 0;
+    std::vector<ss_box_range> ranges;                     // the merged intervals and their frames
+    int64_t n_frames = 0;                                 // distinct frames over them
+    std::vector<BoxRow> rows;                             // one per box of the table (a dropped box's row is read by no frame)
+    std::vector<BoxFrame> fr;                             // one per record
+    std::vector<int32_t> idx;
+    int32_t max_count = 0;                                // most active boxes of a frame
+    size_t fout_need = 0;
+};
+
+inline ss_box_params box_defaults() { return ss_box_params{0.01, 0.0, 100.0}; }
+
+// channels: the file's, or 0 when only the table is known (ss_box_plan: -1 .. 255)
+inline int check_box_args(const ss_box* boxes, int64_t n, int channels, const ss_box_params* p, std::string& err) {
+    if (n < 0 || (n > 0 && !boxes)) { err = "bad box table"; return SS_ERR_ARG; }
+    if (n > (int64_t)1 << 24) { err = "too many boxes"; return SS_ERR_ARG; }
+    if (p) {
+        if (!(p->fade_s >= 0.0) || !std::isfinite(p->fade_s)) { err = "fade_s must be a finite value >= 0"; return SS_ERR_ARG; }
+        if (!(p->min_gain >= 0.0 && p->min_gain <= 1.0)) { err = "min_gain must lie in [0, 1]"; return SS_ERR_ARG; }
+        if (!(p->edge_hz >= 0.0) || !std::isfinite(p->edge_hz)) { err = "edge_hz must be a finite value >= 0"; return SS_ERR_ARG; }
+    }
+    const int top = channels > 0 ? channels : 256;
+    for (int64_t i = 0; i < n; ++i) {
+        const ss_box& b = boxes[i];
+        const double lo = std::isnan(b.low_hz) ? 0.0 : b.low_hz, hi = std::isnan(b.high_hz) ? INFINITY : b.high_hz;
+        const char* what = nullptr;
+        if (!std::isfinite(b.start) || !std::isfinite(b.end) || b.end < b.start) what = "is not finite or ends before it starts";
+        else if (lo > hi) what = "has low_hz above high_hz";
+        else if (hi < 0.0) what = "has a negative high_hz";
+        else if (b.channel < -1 || b.channel >= top) what = "names a channel the file does not have";
+        else if (b.reserved != 0) what = "has a non-zero reserved field";
+        if (what) { err = "box " + std::to_string(i) + " " + what; return SS_ERR_ARG; }
+    }
+    return SS_OK;
+}
+
+inline BoxRow box_row(const ss_box& b, int N, int sr, double edge_hz) {
+    const double lo = std::isnan(b.low_hz) ? 0.0 : b.low_hz, hi = std::isnan(b.high_hz) ? INFINITY : b.high_hz;
+    const double lo_b = lo * (double)N / (double)sr, hi_b = hi * (double)N / (double)sr, e_b = edge_hz * (double)N / (double)sr;
+    const int half = N / 2;
+    BoxRow r{};
+    r.q_lo = lo_b > (double)half ? half + 1 : (int32_t)std::max(0.0, std::ceil(lo_b));
+    r.q_hi = hi_b >= (double)half ? half : (int32_t)std::floor(hi_b);
+    r.lo_f = (float)((double)r.q_lo - lo_b);
+    r.hi_f = hi_b >= (double)half ? 0.f : (float)(hi_b - (double)r.q_hi);
+    r.inv_e = e_b > 0.0 ? (float)(1.0 / e_b) : 0.f;
+    r.channel = b.channel;
+    return r;
+}
+
+// The table (checked: check_box_args) over a file of `frames` frames.  budget <= 0: the intervals and rows alone (ss_box_plan).
+// false: more active-box entries than an int32 counts.
+inline bool plan_boxes(int sr, int64_t frames, int ch, const ss_box* boxes, int64_t n, const ss_box_params& prm, int64_t budget, BoxPlan& p) {
+    p = BoxPlan();
+    const int N = p.N = sep_fft_size(sr), hop = p.hop = N / 4;
+    auto first_frame = [&](int64_t a) { return floordiv(a - N / 2, hop) + 1; };
+    auto last_frame = [&](int64_t b) { return -floordiv(-(b + N / 2), hop) - 1; };
+    // rule 1 per box (silence_ranges' rounding and clamp), the merge of all
+    std::vector<ss_region> reg((size_t)n);
+    std::vector<int64_t> ka((size_t)n, 0), kb((size_t)n, -1);             // a box's active frames ka .. kb (none: an empty box)
+    std::vector<int64_t> at((size_t)n, -1);                               // its first sample
+    p.rows.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        reg[i] = ss_region{boxes[i].start, boxes[i].end};
+        p.rows[i] = box_row(boxes[i], N, sr, prm.edge_hz);
+        const std::vector<int64_t> r = silence_ranges(&reg[i], 1, sr, frames);
+        if (r.empty()) continue;
+        at[i] = r[0]; ka[i] = first_frame(r[0]); kb[i] = last_frame(r[1]);
+    }
+    const std::vector<int64_t> iv = silence_ranges(reg.data(), n, sr, frames);
+    int64_t last_k = INT64_MIN;
+    for (size_t r = 0; r + 1 < iv.size(); r += 2) {
+        const ss_box_range g{iv[r], iv[r + 1], first_frame(iv[r]), last_frame(iv[r + 1])};
+        p.n_frames += g.stft_last - std::max(g.stft_first, last_k + 1) + 1;
+        last_k = g.stft_last;
+        p.ranges.push_back(g);
+    }
+    if (budget <= 0 || p.ranges.empty()) return true;
+    // the boxes of every interval, ascending box index
+    std::vector<std::vector<int32_t>> members(p.ranges.size());
+    for (int64_t i = 0; i < n; ++i) {
+        if (at[i] < 0) continue;
+        auto it = std::upper_bound(p.ranges.begin(), p.ranges.end(), at[i], [](int64_t v, const ss_box_range& g) { return v < g.frame_begin; });
+        members[(size_t)(it - p.ranges.begin()) - 1].push_back((int32_t)i);
+    }
+    std::vector<int32_t> cand;
+    for (size_t r = 0; r < p.ranges.size(); ++r) {
+        const ss_box_range& g = p.ranges[r];
+        // a frame of this interval may also lie over a box of a neighbour: the intervals whose frames meet this one's
+        size_t r0 = r, r1 = r;
+        while (r0 > 0 && p.ranges[r0 - 1].stft_last >= g.stft_first) --r0;
+        while (r1 + 1 < p.ranges.size() && p.ranges[r1 + 1].stft_first <= g.stft_last) ++r1;
+        cand.clear();
+        for (size_t t = r0; t <= r1; ++t) cand.insert(cand.end(), members[t].begin(), members[t].end());
+        std::sort(cand.begin(), cand.end());
+        bool ok = true;
+        cut_interval(p, N, hop, budget, g.frame_begin, g.frame_end, [&](int64_t k) {
+            BoxFrame f{k, (int32_t)p.idx.size(), 0};
+            for (int32_t i : cand)
+                if (ka[i] <= k && k <= kb[i]) { p.idx.push_back(i); ++f.count; }
+            if (p.idx.size() > (size_t)INT32_MAX / 2) ok = false;
+            p.max_count = std::max(p.max_count, f.count);
+            p.fr.push_back(f);
+        });
+        if (!ok) return false;
+    }
+    finish_cuts(p);
+    p.fout_need = p.max_rec * (size_t)((ch + 1) / 2) * N;
+    return true;
 }
 
 // ---- bands plan: what band_profile_kernel and band_bounds_kernel read -----------------------------------------------

@@ -13,6 +13,8 @@
 //   4      sep_blend_kernel: per output sample of an interval, the four overlapping frames gathered in ascending order, blended with
 //          the decoded sample over the fade ramps, encoded as ss_silence_pcm encodes
 // Everything else of the file is the transcode (silence_encode_kernel with no ranges), launched first.
+// The band silencer (ss_box_silence_pcm, box_run below) is steps 3 and 4 alone: box_stft_kernel<N> shares step 3's frame body and takes
+// its gains from a table of boxes instead of the maps.
 //
 // ss_separate_pcm_channels ("per-channel separation"): the signals of step 1 are the channels alone (ss_add_pcm_channels), their windows
 // in one run list; sums, maps and gains carry a signal dimension, and step 3 runs as sep_stft_each_kernel<N>, which gives the two
@@ -40,6 +42,10 @@ struct SepState {
     DevBuf<SepFrame> frames;
     DevBuf<SepSeg> segs;
     DevBuf<float2> fout;
+    // band silencer
+    DevBuf<BoxFrame> bframes;
+    DevBuf<int32_t> bidx;
+    DevBuf<BoxRow> brows;
     // region bands
     DevBuf<BandSeg> bseg;
     DevBuf<BandRegion> breg;
@@ -181,13 +187,59 @@ __device__ __forceinline__ void sep_fft(float2* buf, int lt, const float2* __res
     for (int s = 0; s < SepGeomT<N>::LOG2 / 4; ++s) { sep_stage<N, 16>(buf, lt, Ns, tw); Ns *= 16; }
 }
 
+// The frame body every STFT kernel shares: channels c0 / c1 of the frame centred on sample k hop, decoded and windowed into the padded
+// buffer -> FFT -> gains(): the kernel's own gain source scales the spectrum in place and leaves it conjugated (the inverse FFT is
+// conj(FFT(conj(.))) / N) -> FFT -> synthesis window / (1.5 N) -> o[N].  Every thread of the block calls it (barriers); an item without
+// a frame (!valid) transforms zeros and stores nothing.
+template <int N, class Gains>
+__device__ __forceinline__ void sep_frame_body(const unsigned char* pcm, int format, int channels, int64_t frames, int64_t k, bool valid, int hop,
+                                               int c0, int c1, float2* buf, int lt, const float2* tw, const float* win, float2* o,
+                                               Gains&& gains) {   // (no __restrict__ here: the kernels' own arguments carry it; repeated on
+                                                                  // the inlined body it cost the existing forms 12 to 32 registers)
+    using G = SepGeomT<N>;
+    const int64_t base = k * hop - N / 2;
+    for (int n = lt; n < N; n += G::T) {
+        const int64_t s = base + n;
+        float x0 = 0.f, x1 = 0.f;
+        if (valid && s >= 0 && s < frames) {
+            x0 = decode_sample(pcm, format, s * channels + c0);
+            if (c1 < channels) x1 = decode_sample(pcm, format, s * channels + c1);
+        }
+        const float w = win[n];
+        buf[sep_pad(n)] = make_float2(x0 * w, x1 * w);
+    }
+    __syncthreads();
+    sep_fft<N>(buf, lt, tw);
+    gains();
+    __syncthreads();
+    sep_fft<N>(buf, lt, tw);
+    if (!valid) return;
+    constexpr float kScale = 1.0f / (1.5f * (float)N);
+    for (int n = lt; n < N; n += G::T) {
+        const float2 Y = buf[sep_pad(n)];
+        const float sc = win[n] * kScale;
+        o[n] = make_float2(Y.x * sc, -Y.y * sc);
+    }
+}
+
+// The pair (q, N - q) of Z = A + iB under the channels' own real, even gains ga / gb, in place and conjugated (q = 0 and N / 2 pair with
+// themselves): Ga A + Gb iB = S Z[q] + D conj(Z[N - q]),  S = (ga + gb) / 2,  D = (ga - gb) / 2
+template <int N>
+__device__ __forceinline__ void sep_pair_gains(float2* buf, int q, float ga, float gb) {
+    const float S = 0.5f * (ga + gb), D = 0.5f * (ga - gb);
+    const int r = (N - q) & (N - 1);
+    const float2 Zq = buf[sep_pad(q)], Zr = buf[sep_pad(r)];
+    buf[sep_pad(q)] = make_float2(S * Zq.x + D * Zr.x, -(S * Zq.y - D * Zr.y));
+    if (r != q) buf[sep_pad(r)] = make_float2(S * Zr.x + D * Zq.x, -(S * Zr.y - D * Zq.y));
+}
+
 // Block = ITEMS frames of one channel pair (blockIdx.y): channels 2p and 2p + 1 ride as the real and imaginary parts of one complex FFT
 // (the gain is real and even in q, so the two stay apart).  out[rec][pair][N] = synthesis-windowed frame / (1.5 N), ready to gather.
 //
 // EACH (ss_separate_pcm_channels): the two channels have gains of their own, Ga and Gb, from the tables gain + c gain_cs; both are real and
 // even in q, so with A, B the channels' spectra, Z = A + iB and A[q] = (Z[q] + conj(Z[N - q])) / 2, iB[q] = (Z[q] - conj(Z[N - q])) / 2:
 //   Ga A + Gb iB = S Z[q] + D conj(Z[N - q]),  S = (Ga + Gb) / 2,  D = (Ga - Gb) / 2
-// -- one thread per pair (q, N - q), in place (q = 0 and N / 2 pair with themselves).  Ga == Gb: D = 0 adds an exact zero, S = Ga, the
+// -- one thread per pair (q, N - q), in place (sep_pair_gains).  Ga == Gb: D = 0 adds an exact zero, S = Ga, the
 // frame is the mix form's.  An unpaired last channel takes Gb := Ga.  LDS: two rows of band gains per frame in place of one.
 // The two forms are launched (and recorded) as sep_stft_kernel<N> and sep_stft_each_kernel<N>; gain_cs is unused by the first.
 template <int N, bool EACH>
@@ -215,48 +267,85 @@ __global__ __launch_bounds__(256) void sep_stft_form_kernel(const unsigned char*
         for (int m = lt; m < 128; m += G::T)
             gt[128 + m] = valid ? (1.0f - f.alpha) * gain1[(size_t)f.cb0 * 128 + m] + f.alpha * gain1[(size_t)f.cb1 * 128 + m] : 0.f;
     }
-    const int64_t base = f.k * hop - N / 2;
-    for (int n = lt; n < N; n += G::T) {
-        const int64_t s = base + n;
-        float x0 = 0.f, x1 = 0.f;
-        if (valid && s >= 0 && s < frames) {
-            x0 = decode_sample(pcm, format, s * channels + c0);
-            if (c1 < channels) x1 = decode_sample(pcm, format, s * channels + c1);
+    sep_frame_body<N>(pcm, format, channels, frames, f.k, valid, hop, c0, c1, buf, lt, tw, win, out + ((size_t)rec * npairs + pair) * N, [&]() {
+        if constexpr (EACH) {
+            for (int q = lt; q <= N / 2; q += G::T) {            // one thread per pair (q, N - q)
+                const SepBand bd = band[q];
+                const float ga = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
+                const float gb = bd.m0 < 0 ? gain_hi : bd.w0 * gt[128 + bd.m0] + bd.w1 * gt[128 + bd.m1];
+                sep_pair_gains<N>(buf, q, ga, gb);
+            }
+        } else {
+            for (int q = lt; q < N; q += G::T) {                 // X[q] g(q), conjugated
+                const SepBand bd = band[q <= N / 2 ? q : N - q];
+                const float g = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
+                const float2 X = buf[sep_pad(q)];
+                buf[sep_pad(q)] = make_float2(X.x * g, -X.y * g);
+            }
         }
-        const float w = win[n];
-        buf[sep_pad(n)] = make_float2(x0 * w, x1 * w);
+    });
+}
+
+// The band silencer's STFT (include/softspoken.h "band silencer", step 3): the frame body above with the gains of a table of boxes.
+// fr[rec]: the frame and its active boxes idx[first .. first + count - 1] (rows of `rows`).  The rows are staged into LDS kBoxStage
+// at a time, `rounds` times (the host's ceil(most active boxes of a frame / kBoxStage): uniform, so the barriers are); each thread
+// keeps the minimum over them for its own pairs (q, N - q), q = lt + t T, in registers, for channel c0 (ga) and c1 (gb; an unpaired
+// last channel takes gb := ga), then applies the channel-pair form.  omg = 1 - min_gain.
+constexpr int kBoxStage = 64;
+
+__device__ __forceinline__ float box_gain(const BoxRow& b, int q, float omg) {
+    float v = 1.f;
+    if (q < b.q_lo || q > b.q_hi) {
+        const float d = q < b.q_lo ? (float)(b.q_lo - q) - b.lo_f : (float)(q - b.q_hi) - b.hi_f;
+        const float t = d * b.inv_e;
+        v = (b.inv_e > 0.f && t < 1.f) ? 0.5f + 0.5f * cospif(t) : 0.f;
     }
-    __syncthreads();
-    sep_fft<N>(buf, lt, tw);
-    if constexpr (EACH) {
-        for (int q = lt; q <= N / 2; q += G::T) {                // the pair (q, N - q), conjugated as below
-            const SepBand bd = band[q];
-            const float ga = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
-            const float gb = bd.m0 < 0 ? gain_hi : bd.w0 * gt[128 + bd.m0] + bd.w1 * gt[128 + bd.m1];
-            const float S = 0.5f * (ga + gb), D = 0.5f * (ga - gb);
-            const int r = (N - q) & (N - 1);
-            const float2 Zq = buf[sep_pad(q)], Zr = buf[sep_pad(r)];
-            buf[sep_pad(q)] = make_float2(S * Zq.x + D * Zr.x, -(S * Zq.y - D * Zr.y));
-            if (r != q) buf[sep_pad(r)] = make_float2(S * Zr.x + D * Zq.x, -(S * Zr.y - D * Zq.y));
+    return 1.f - omg * v;
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void box_stft_kernel(const unsigned char* __restrict__ pcm, int format, int channels, int64_t frames,
+                                                       const BoxFrame* __restrict__ fr, int n_fr, int hop, const int32_t* __restrict__ idx,
+                                                       const BoxRow* __restrict__ rows, int rounds, float omg, const float2* __restrict__ tw,
+                                                       const float* __restrict__ win, float2* __restrict__ out) {
+    using G = SepGeomT<N>;
+    extern __shared__ float2 sep_lds[];
+    constexpr int NQ = (N / 2) / G::T + 1;                        // pairs per thread (the last one: lt == 0 alone)
+    const int item = threadIdx.x / G::T, lt = threadIdx.x % G::T;
+    float2* buf = sep_lds + item * G::PITCH;
+    BoxRow* stage = (BoxRow*)(sep_lds + G::ITEMS * G::PITCH) + item * kBoxStage;
+    const int64_t rec = (int64_t)blockIdx.x * G::ITEMS + item;
+    const bool valid = rec < n_fr;
+    const int pair = blockIdx.y, npairs = gridDim.y, c0 = 2 * pair, c1 = 2 * pair + 1;
+    BoxFrame f{0, 0, 0};
+    if (valid) f = fr[rec];
+    sep_frame_body<N>(pcm, format, channels, frames, f.k, valid, hop, c0, c1, buf, lt, tw, win, out + ((size_t)rec * npairs + pair) * N, [&]() {
+        float ga[NQ], gb[NQ];
+#pragma unroll
+        for (int t = 0; t < NQ; ++t) ga[t] = gb[t] = 1.f;
+        for (int r = 0; r < rounds; ++r) {
+            const int n = min(max(f.count - r * kBoxStage, 0), kBoxStage);
+            for (int j = lt; j < n; j += G::T) stage[j] = rows[idx[f.first + r * kBoxStage + j]];
+            __syncthreads();
+            for (int j = 0; j < n; ++j) {
+                const BoxRow b = stage[j];
+                const bool ona = b.channel < 0 || b.channel == c0;
+                const bool onb = c1 < channels ? (b.channel < 0 || b.channel == c1) : ona;
+#pragma unroll
+                for (int t = 0; t < NQ; ++t) {
+                    const float g = box_gain(b, lt + t * G::T, omg);
+                    if (ona) ga[t] = fminf(ga[t], g);
+                    if (onb) gb[t] = fminf(gb[t], g);
+                }
+            }
+            __syncthreads();
         }
-    } else {
-        for (int q = lt; q < N; q += G::T) {                     // X[q] g(q), conjugated: the inverse FFT is conj(FFT(conj(.))) / N
-            const SepBand bd = band[q <= N / 2 ? q : N - q];
-            const float g = bd.m0 < 0 ? gain_hi : bd.w0 * gt[bd.m0] + bd.w1 * gt[bd.m1];
-            const float2 X = buf[sep_pad(q)];
-            buf[sep_pad(q)] = make_float2(X.x * g, -X.y * g);
+#pragma unroll
+        for (int t = 0; t < NQ; ++t) {
+            const int q = lt + t * G::T;
+            if (q <= N / 2) sep_pair_gains<N>(buf, q, ga[t], gb[t]);
         }
-    }
-    __syncthreads();
-    sep_fft<N>(buf, lt, tw);
-    if (!valid) return;
-    constexpr float kScale = 1.0f / (1.5f * (float)N);
-    float2* o = out + ((size_t)rec * npairs + pair) * N;
-    for (int n = lt; n < N; n += G::T) {
-        const float2 Y = buf[sep_pad(n)];
-        const float sc = win[n] * kScale;
-        o[n] = make_float2(Y.x * sc, -Y.y * sc);
-    }
+    });
 }
 
 // Output sample `idx` (of total x channels) of the pieces in segs (out0 ascending): p = the four frames over the sample, added in
@@ -455,6 +544,27 @@ static hipError_t launch_sep_stft(int N, bool each, const void* pcm, int format,
 
 static constexpr size_t kSepFrameBytes = (size_t)256 << 20;      // most bytes of resynthesised frames held at once (pieces / chunks)
 
+// Step 4 over one chunk's segments (uploaded to st.segs) and the frame buffer: sep_blend_kernel into d_sil_out, or (src)
+// sep_blend_source_kernel into d_src_out.  The band silencer launches it as the separation silencer does.
+static int launch_sep_blend(ss_ctx* c, bool src, int format, int ch, const SepChunk& ck, int hop, int N, int64_t F) {
+    SepState& st = sep_state(c);
+    const int npairs = (ch + 1) / 2;
+    const int64_t all = ck.total * ch;
+    const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
+    if (src) {
+        ScopedLaunch sl(c, c->stream, "sep_blend_source_kernel", 0.0, (double)all * (16.0 + 2.0 * pcm_bytes_per_sample(format)));
+        hipLaunchKernelGGL(sep_blend_form_kernel<unsigned char>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
+                           st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_src_out);
+        HIPCHK(c, hipGetLastError());
+        return SS_OK;
+    }
+    ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
+    hipLaunchKernelGGL(sep_blend_form_kernel<short>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
+                       st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_sil_out);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
 // each (ss_separate_pcm_channels, ch > 1): the signals are the channels alone, every channel's STFT gets the gains of its own maps
 // src: the output in the recording's own encoding (out: frames x ch x bytes-per-sample bytes) -- a device copy of the PCM in place of
 // the transcode, sep_blend_source_kernel in place of sep_blend_kernel; otherwise out is int16
@@ -508,19 +618,85 @@ int separate_run(ss_ctx* c, bool each, bool src, const void* pcm, int format, in
                 HIPCHK(c, launch_sep_stft(N, each, c->d_pcm, format, ch, frames, st.frames.p + ck.rec0, (int)ck.nrec, hop, st.gain.p,
                                             (size_t)ncb * 128, *tb, gain_hi, st.fout.p, c->stream));
             }
-            const int64_t all = ck.total * ch;
-            const unsigned gx = (unsigned)std::min<int64_t>((all + 255) / 256, 16384);
-            if (src) {
-                ScopedLaunch sl(c, c->stream, "sep_blend_source_kernel", 0.0, (double)all * (16.0 + 2.0 * pcm_bytes_per_sample(format)));
-                hipLaunchKernelGGL(sep_blend_form_kernel<unsigned char>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
-                                   st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_src_out);
-                HIPCHK(c, hipGetLastError());
-                continue;
+            if ((rc = launch_sep_blend(c, src, format, ch, ck, hop, N, F))) return rc;
+        }
+    }
+    if (src) HIPCHK(c, hipMemcpyAsync(out, c->d_src_out, pcm_bytes, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(c, hipMemcpyAsync(out, c->d_sil_out, total * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // the plan and the caller's buffers are free again
+    return SS_OK;
+}
+
+// =========================================================================================================
+// band silencer (include/softspoken.h "band silencer"): separate_run without the model -- the gains come from the box table
+//
+//   plan   (sep_plan.h plan_boxes) merged intervals, a row per box, every frame's active boxes; plan_synthesis' pieces and chunks
+//   per chunk   box_stft_kernel<N> -> the frame buffer;  sep_blend_kernel / sep_blend_source_kernel as separate_run launches them
+// The recording is in c->d_pcm already (the caller staged it, as ss_silence_pcm does); the job's files and streams are not touched.
+// =========================================================================================================
+static hipError_t launch_box_stft(int N, const void* pcm, int format, int channels, int64_t frames, const BoxFrame* fr, int n_fr, int hop,
+                                  const int32_t* idx, const BoxRow* rows, int rounds, float omg, const SepTables& tb, float2* out, hipStream_t s) {
+    using Kernel = decltype(&box_stft_kernel<256>);
+    static const Kernel forms[6] = {box_stft_kernel<256>, box_stft_kernel<512>, box_stft_kernel<1024>,
+                                    box_stft_kernel<2048>, box_stft_kernel<4096>, box_stft_kernel<8192>};
+    static const int items[6] = {SepGeomT<256>::ITEMS, SepGeomT<512>::ITEMS, SepGeomT<1024>::ITEMS, SepGeomT<2048>::ITEMS, SepGeomT<4096>::ITEMS, SepGeomT<8192>::ITEMS};
+    static std::atomic<uint64_t> attr_done[6];                    // (per device: kernels.h allow_full_lds)
+    int i = 0;
+    while (i < 6 && (256 << i) != N) ++i;
+    if (i == 6) return hipErrorInvalidValue;
+    const size_t lds = (size_t)items[i] * ((size_t)(N + N / 16) * sizeof(float2) + kBoxStage * sizeof(BoxRow));
+    const dim3 grid((unsigned)((n_fr + items[i] - 1) / items[i]), (unsigned)((channels + 1) / 2));
+    if (hipError_t e = allow_full_lds((const void*)forms[i], attr_done[i])) return e;
+    hipLaunchKernelGGL(forms[i], grid, dim3(256), lds, s, (const unsigned char*)pcm, format, channels, frames, fr, n_fr, hop, idx, rows, rounds, omg,
+                       tb.tw.p, tb.win.p, out);
+    return hipGetLastError();
+}
+
+int box_run(ss_ctx* c, bool src, int format, int sr, int ch, int64_t frames, const ss_box* boxes, int64_t n_boxes, const ss_box_params* params,
+            void* out) {
+    const ss_box_params prm = params ? *params : box_defaults();
+    const int npairs = (ch + 1) / 2;
+    int64_t budget = (int64_t)(kSepFrameBytes / ((size_t)npairs * sep_fft_size(sr) * sizeof(float2)));
+#ifdef SS_DEVBUILD      // ss_debug_set_separation_budget moves these cuts as it moves separate_run's
+    if (c->sep_budget > 0) budget = c->sep_budget;
+#endif
+    BoxPlan bp;                                                   // (uploaded from: alive until the last synchronise)
+    if (!plan_boxes(sr, frames, ch, boxes, n_boxes, prm, std::max<int64_t>(16, budget), bp))
+        return fail(c, SS_ERR_ARG, "band silencer: too many boxes lie over one another");
+    SepState& st = sep_state(c);
+    const size_t total = (size_t)frames * ch, pcm_bytes = total * pcm_bytes_per_sample(format);
+    int rc;
+    if (src) {   // the recording's own bytes: what ss_silence_pcm_source writes outside its ranges
+        if ((rc = ensure(c, &c->d_src_out, &c->src_out_cap, pcm_bytes + 16))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_src_out, c->d_pcm, pcm_bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {     // the transcode of the whole file: what ss_silence_pcm writes outside its ranges
+        if ((rc = ensure(c, &c->d_sil_out, &c->sil_out_cap, total + 8))) return rc;
+        ScopedLaunch sl(c, c->stream, "box_transcode/silence_encode_kernel", 0.0, (double)total * pcm_bytes_per_sample(format) + 2.0 * (double)total);
+        HIPCHK(c, launch_silence_encode(c->d_pcm, format, ch, frames, nullptr, 0, c->d_sil_out, c->stream));
+    }
+    if (!bp.chunks.empty()) {
+        const int N = bp.N, hop = bp.hop;
+        SepTables* tb = nullptr;
+        if ((rc = sep_tables(c, sr, &tb))) return rc;
+        if ((rc = st.bframes.reserve(c, bp.fr.size())) || (rc = st.bidx.reserve(c, bp.idx.size())) || (rc = st.brows.reserve(c, bp.rows.size())) ||
+            (rc = st.segs.reserve(c, bp.sg.size())) || (rc = st.fout.reserve(c, bp.fout_need)))
+            return rc;
+        HIPCHK(c, hipMemcpyAsync(st.bframes.p, bp.fr.data(), bp.fr.size() * sizeof(BoxFrame), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.bidx.p, bp.idx.data(), bp.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.brows.p, bp.rows.data(), bp.rows.size() * sizeof(BoxRow), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.segs.p, bp.sg.data(), bp.sg.size() * sizeof(SepSeg), hipMemcpyHostToDevice, c->stream));
+        const int64_t F = (int64_t)std::nearbyint(prm.fade_s * sr);
+        const int rounds = (bp.max_count + kBoxStage - 1) / kBoxStage;
+        const std::string stft_name = "box_stft_kernel<" + std::to_string(N) + ">";
+        for (const SepChunk& ck : bp.chunks) {
+            {
+                const double lg = std::log2((double)N);
+                ScopedLaunch sl(c, c->stream, stft_name, 2.0 * (double)ck.nrec * npairs * (5.0 * N * lg + 8.0 * N),
+                                (double)ck.nrec * npairs * N * (2.0 * pcm_bytes_per_sample(format) + 8.0));
+                HIPCHK(c, launch_box_stft(N, c->d_pcm, format, ch, frames, st.bframes.p + ck.rec0, (int)ck.nrec, hop, st.bidx.p, st.brows.p, rounds,
+                                            (float)(1.0 - prm.min_gain), *tb, st.fout.p, c->stream));
             }
-            ScopedLaunch sl(c, c->stream, "sep_blend_kernel", 0.0, (double)all * (16.0 + pcm_bytes_per_sample(format) + 2.0));
-            hipLaunchKernelGGL(sep_blend_form_kernel<short>, dim3(gx), dim3(256), 0, c->stream, (const unsigned char*)c->d_pcm, format, ch,
-                               st.segs.p + ck.seg0, (int)ck.nseg, ck.total, hop, N, npairs, st.fout.p, F, c->d_sil_out);
-            HIPCHK(c, hipGetLastError());
+            if ((rc = launch_sep_blend(c, src, format, ch, ck, hop, N, F))) return rc;
         }
     }
     if (src) HIPCHK(c, hipMemcpyAsync(out, c->d_src_out, pcm_bytes, hipMemcpyDeviceToHost, c->stream));

@@ -97,6 +97,24 @@ class RegionBand(C.Structure):
 REGION_BAND_DTYPE = np.dtype([("low_hz", "<f8"), ("high_hz", "<f8"), ("peak_hz", "<f8"), ("speech_share", "<f8"),
                               ("band_low", "<i4"), ("band_high", "<i4"), ("band_peak", "<i4"), ("n_bins", "<i4")])
 
+
+
+class BoxParams(C.Structure):
+    _fields_ = [("fade_s", C.c_double), ("min_gain", C.c_double), ("edge_hz", C.c_double)]
+
+
+class BoxRange(C.Structure):
+    _fields_ = [("frame_begin", C.c_int64), ("frame_end", C.c_int64), ("stft_first", C.c_int64), ("stft_last", C.c_int64)]
+
+
+class BoxPlanInfo(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_frames", C.c_int64), ("n_ranges", C.c_int64), ("cap_ranges", C.c_int64),
+                ("ranges", C.POINTER(BoxRange))]
+
+
+# struct ss_box as a numpy record (40 bytes): a time range, its frequency band (NaN: no estimate) and the channel it acts on (-1: all)
+BOX_DTYPE = np.dtype([("start", "<f8"), ("end", "<f8"), ("low_hz", "<f8"), ("high_hz", "<f8"), ("channel", "<i4"), ("reserved", "<i4")])
+
 ABOVE_FMAX = {"mute": 0, "keep": 1}      # SS_ABOVE_FMAX_MUTE / _KEEP
 
 
@@ -200,6 +218,9 @@ _SIGS = {
     "ss_separate_pcm_channels_source": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64,
                                                   C.POINTER(SeparationParams), _P, C.c_int64]),
     "ss_wav_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
+    "ss_box_plan": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(BoxParams), C.POINTER(BoxPlanInfo)]),
+    "ss_box_silence_pcm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(BoxParams), _P]),
+    "ss_box_silence_pcm_source": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(BoxParams), _P, C.c_int64]),
     "ss_band_edges": (C.c_int, [_P]),
     "ss_region_bins": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ss_region_bands": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(BandParams), _P, _P]),
@@ -421,6 +442,34 @@ def separation_plan(sr: int, frames: int, regions, **params) -> dict:
     return out
 
 
+def boxes_array(boxes) -> np.ndarray:
+    """A BOX_DTYPE array from one, or from rows (start_s, end_s, low_hz, high_hz[, channel]): None or NaN edges mean "no estimate" (the
+    whole band), a missing or None channel every channel (-1)."""
+    if isinstance(boxes, np.ndarray) and boxes.dtype == BOX_DTYPE:
+        return np.ascontiguousarray(boxes)
+    out = np.zeros(len(boxes), dtype=BOX_DTYPE)
+    for i, b in enumerate(boxes):
+        s, e, lo, hi = b[:4]
+        ch = b[4] if len(b) > 4 else None
+        out[i] = (float(s), float(e), float("nan") if lo is None else float(lo), float("nan") if hi is None else float(hi),
+                  -1 if ch is None else int(ch), 0)
+    return out
+
+
+def box_plan(sr: int, frames: int, boxes, fade_s: float = 0.01, min_gain: float = 0.0, edge_hz: float = 100.0) -> dict:
+    """ss_box_plan (host only): n_fft, hop, n_frames and the merged ranges (frame_begin, frame_end, stft_first, stft_last) as dicts."""
+    arr = boxes_array(boxes)
+    p = BoxParams(float(fade_s), float(min_gain), float(edge_hz))
+    cap = max(1, len(arr))
+    rng = (BoxRange * cap)()
+    info = BoxPlanInfo()
+    info.cap_ranges, info.ranges = cap, C.cast(rng, C.POINTER(BoxRange))
+    _check(lib().ss_box_plan(int(sr), int(frames), _ptr(arr) if len(arr) else None, len(arr), C.byref(p), C.byref(info)))
+    out = {k: int(getattr(info, k)) for k in ("n_fft", "hop", "n_frames")}
+    out["ranges"] = [{f: int(getattr(rng[i], f)) for f, _ in BoxRange._fields_} for i in range(info.n_ranges)]
+    return out
+
+
 def band_edges() -> np.ndarray:
     """The 130 HTK mel points f of the region bands (ss_band_edges, host only): band m's triangle spans f[m] .. f[m + 2] Hz."""
     out = np.empty(130, dtype=np.float64)
@@ -594,6 +643,31 @@ class Context:
         """separate_pcm_channels in the recording's own encoding (ss_separate_pcm_channels_source)."""
         return self._separate_source(lib().ss_separate_pcm_channels_source, pcm, fmt, sr, channels, frames, regions, fade_s, min_gain,
                                      above_fmax, speech_channel)
+
+    def box_silence_pcm(self, pcm: np.ndarray, fmt: int, sr: int, channels: int, boxes, *, fade_s: float = 0.01, min_gain: float = 0.0,
+                        edge_hz: float = 100.0, encoding: str = "pcm16", frames: int | None = None) -> np.ndarray:
+        """The band silencer (ss_box_silence_pcm / _source): inside each box's time range only the box's own frequency band is removed.
+        boxes: boxes_array's input.  encoding "pcm16": interleaved int16 (frames, channels), the rest as silence_pcm writes it; "source":
+        uint8 (frames, channels x bytes per sample), the input's bytes outside the boxes.  frames: the whole buffer's when not given.
+        No model pass; the context's files, results and streams stay as they are."""
+        if encoding not in ("pcm16", "source"):
+            raise ValueError(f'encoding must be "pcm16" or "source", not {encoding!r}')
+        pcm = np.ascontiguousarray(pcm)
+        if frames is None:
+            if fmt not in _BPS or int(channels) < 1:
+                raise ValueError(f"unknown PCM format code {fmt} or channel count {channels}")
+            frames = pcm.nbytes // (int(channels) * _BPS[fmt])
+        self._need_bytes(pcm, fmt, channels, frames)
+        arr = boxes_array(boxes)
+        p = BoxParams(float(fade_s), float(min_gain), float(edge_hz))
+        bp = _ptr(arr) if len(arr) else None
+        if encoding == "source":
+            out = np.empty((frames, channels * _BPS[fmt]), dtype=np.uint8)
+            self._ck(lib().ss_box_silence_pcm_source(self._h, _ptr(pcm), fmt, sr, channels, frames, bp, len(arr), C.byref(p), _ptr(out), out.nbytes))
+        else:
+            out = np.empty((frames, channels), dtype=np.int16)
+            self._ck(lib().ss_box_silence_pcm(self._h, _ptr(pcm), fmt, sr, channels, frames, bp, len(arr), C.byref(p), _ptr(out)))
+        return out
 
     def separation_maps(self, fid: int, first_bin: int, n_bins: int) -> np.ndarray:
         """Averaged spec-head maps of bins [first_bin, first_bin + n_bins) of file fid: float32 [2, n_bins, 128]."""
